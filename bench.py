@@ -2,16 +2,22 @@
 """Headline benchmark: (user,item) pairs/s of one NeuMF training step at batch 65 536, dim 64
 (BASELINE.json configs[1]: NeuMF embed_dim=64, synthetic 1M users x 100K items, 1 x MI355X).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = embedding gather -> GMF dot + MLP tower (fp32 MFMA) -> sigmoid-BCE -> backward ->
 dedup of the per-pair row gradients -> Keras-Adam on the four tables and the dense parameters,
 on one synthetic batch already resident in HBM.  Default optimizer = "adam_dense": Keras'
 NON-lazy sparse Adam (every row of every table decays m, v and moves each step [TF-sem]) — the
-reference's semantics; the lazy-row variant is timed too and reported under "adam_lazy".
+reference's semantics; with --full the lazy-row variant is timed too and reported under "adam_lazy".
 
-Rank 0 prints ONE JSON line (metric/value/... + "roofline" for the kernel that takes the most time
+A plain run does what the headline needs and no more: set up, prime the tables with one pass over the
+batch cycle (plus the untimed steps of --full's profiling pass, unprobed: both then time the same
+batches), capture the step, warm up, time K steps (the whole step as hipGraph replay, 4 steps per
+graph launch), write --dump-outputs, print the line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR: what the last timed step left for its caller, as .npy files (dump_outputs).
+
+With --full, rank 0 prints ONE JSON line (metric/value/... + "roofline" for the kernel that takes the most time
 per step - chosen from the per-kernel HIP-event table of an eager pass, then bracketed by events on the
 launch stream INSIDE the timed region - + "kernels": one entry per kernel, + "legs": the plain 4-table
 gather (north_star's HBM-read target), Zipf(1.05) ids, the BPR step (config 3) and the TwoTower
@@ -386,6 +392,40 @@ def cpu_baseline(args, spec_dim):
                       f"{dt:.1f} s; oracle/torch_ref.py::NFCPlainCpuStep"}
 
 
+DUMP_ROWS = 8192        # rows of each fused table sampled by --dump-outputs
+DUMP_PAIRS = 1 << 18    # per-pair outputs of a larger batch are sampled down to this many pairs
+
+
+def dump_outputs(eng, out_dir, B):
+    """--dump-outputs: what the last timed step left for the caller of the training step, one .npy per array (float32, metric sums
+    float64): that step's logits and probabilities, the metric sums since the engine was built, the dense parameters with their Adam
+    moments and the BatchNorm moving statistics, and a fixed, seeded sample of DUMP_ROWS rows of each fused [mlp | mf] table with
+    their Adam moments as a flush leaves them (and the sampled row ids, float64).  Deferred tables are brought up to date on COPIES of the sampled rows (brAdamFlush works
+    row by row), so the engine's lag state - and whatever --full measures after the timed region - stays as it was."""
+    import numpy as np
+    _lib = importlib.import_module("binary-recommendation_amd._lib")
+    ops = importlib.import_module("binary-recommendation_amd.ops")
+    lib, cfg = _lib.load(), eng.cfg
+    g = torch.Generator().manual_seed(20261016)
+    sample = lambda n, k: (torch.arange(n) if n <= k else torch.randperm(n, generator=g)[:k].sort().values).to(eng.device)
+    pairs = sample(B, DUMP_PAIRS)
+    out = {"logit": eng.logit[:B][pairs], "prob": eng.prob[:B][pairs], "metric_sums": eng.msums.sum(dim=0),
+           "dense_params": eng.theta.buf, "dense_adam_m": eng.adam_m.buf, "dense_adam_v": eng.adam_v.buf, "bn_moving": eng.moving_buf}
+    for k in ("user", "item"):
+        idx = sample(eng.fused[k].shape[0], DUMP_ROWS)
+        tab, m, v = (x[idx].contiguous() for x in (eng.fused[k], eng.fused_m[k], eng.fused_v[k]))
+        if eng.deferred:
+            last = eng.last[k][idx].contiguous()
+            _lib.check(lib.brAdamFlush(tab.data_ptr(), m.data_ptr(), v.data_ptr(), last.data_ptr(), tab.shape[0], tab.shape[1],
+                                       eng.step_state.data_ptr(), cfg.beta1, cfg.beta2, cfg.adam_eps, ops._stream()), "brAdamFlush")
+        out[k + "_rows"], out[k + "_rows_m"], out[k + "_rows_v"], out[k + "_row_ids"] = tab, m, v, idx.double()
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    return sorted(out)
+
+
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -422,6 +462,11 @@ def main():
                          "batch cycle (seed_steady_state) - the state a table far larger than steps x batch is in after a long run")
     ap.add_argument("--since-flush", type=int, default=700, help="--steady-state-lags: steps since the engine's last periodic flush (caps the lags)")
     ap.add_argument("--replay", default=None, choices=["fast", "exact"], help="form of the deferred replay (NeuMFConfig.replay; default fast)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel table and roofline (eager profiling pass, probed graph), whole-step graph "
+                         "sub-legs, deferred flush, adam_dense sweep / adam_lazy, the gather / Zipf / BPR / TwoTower legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; dump_outputs)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -500,8 +545,11 @@ def main():
     loc_users, loc_items = eng.local_rows("user_mf"), eng.local_rows("item_mf")
     deferred_mode = bool(getattr(eng, "deferred", False))
     fused_rows = deferred_mode and ctx is None      # the pair launch forms the MF-row gradients itself (neumf_step.cpp fuse_mf)
-    uniq_u = sum(int(torch.unique(b[0]).numel()) for b in batches) / len(batches)
-    uniq_i = sum(int(torch.unique(b[1]).numel()) for b in batches) / len(batches)
+    # unique rows per batch: the algorithmic bytes of --full's per-kernel table and the seeded lags of --steady-state-lags
+    uniq_u = uniq_i = 0.0
+    if args.full or args.steady_state_lags:
+        uniq_u = sum(int(torch.unique(b[0]).numel()) for b in batches) / len(batches)
+        uniq_i = sum(int(torch.unique(b[1]).numel()) for b in batches) / len(batches)
     # deferred lookup: a pair whose row was NOT updated in the previous step also reads the row's m and v (the replay needs them): measured
     # on the primed tables for the batch the cursor stands at (steady state: ~94 % of the user rows, ~52 % of the item rows at config 2)
     lag_u = lag_i = 0.0      # (measured behind the timed region, where the tables are in steady state)
@@ -588,7 +636,10 @@ def main():
         cands = [(share[t], inv[t]) for t in share if inv.get(t) in SPEC and SPEC[inv[t]][0][2] is not None]
         return max(cands)[1] if cands else None
 
+    S_MULTI = args.steps_per_launch if (ctx is None and args.steps_per_launch > 1 and row0 == 0 and batch_total == B) else 1
     if use_graph:
+        # the eager profiling pass of --full; a plain run takes the same untimed steps unprobed, so both time the same batches of the
+        # cycle on tables in the same state (and --dump-outputs writes the same arrays with or without --full)
         np_ = max(1, min(args.profile_steps, args.steps))
         aux = eng.step_struct.aux_stream
         eng.step_struct.aux_stream = None        # dedup sorts on the launch stream: every kernel alone between its two events
@@ -596,10 +647,25 @@ def main():
         #  kernel's first launch loads its code object - milliseconds that would sit in a 10-step mean)
         run_steps(eng, batches, 2, row0, batch_total)
         torch.cuda.synchronize()
-        if lib.brProbeEnable(64 * np_) != 0:
+        if args.full and lib.brProbeEnable(64 * np_) != 0:
             raise RuntimeError(lib.brGetLastError().decode())
         dte = timed(eng, batches, np_, 0, ctx, row0, batch_total)
         eng.step_struct.aux_stream = aux
+    if use_graph and not args.full:
+        # plain run: the step as a training loop replays it (S_MULTI steps per graph launch) - no event-record nodes
+        try:
+            if S_MULTI > 1:
+                make_groups(batches, S_MULTI)
+                eng.enable_graph_multi(B, S_MULTI)
+            else:
+                eng.enable_graph(B)
+            run_steps(eng, batches, max(2, args.warmup), row0, batch_total)
+        except Exception as exc:  # noqa: BLE001  - a driver / runtime that cannot capture this step: time the eager sequence
+            log(f"hipGraph capture failed ({type(exc).__name__}: {exc}); falling back to eager launches")
+            eng.disable_graph()
+            use_graph = False
+            graph_error = f"{type(exc).__name__}: {exc}"
+    if use_graph and args.full:
         per_tag = read_probe(lib)
         lib.brProbeEnable(0)
         eager_profile = {"steps": np_, "ms_per_step": dte / np_ * 1e3, "value": B * np_ / dte, "unit": "pairs/s",
@@ -614,7 +680,6 @@ def main():
         # launches and the staging launch are paid once per S steps); the record nodes then sit around the LAST step's launch of every
         # second group.
         PROBE_EVERY = 4
-        S_MULTI = args.steps_per_launch if (ctx is None and args.steps_per_launch > 1 and row0 == 0 and batch_total == B) else 1
         graph_exec = g_probe = g_plain = gm_probe = gm_plain = None
         try:
             if S_MULTI > 1:
@@ -650,7 +715,10 @@ def main():
             eng.disable_graph()
             use_graph = False
             graph_error = f"{type(exc).__name__}: {exc}"
-    if use_graph and graph_exec is not None and S_MULTI > 1:
+    if not args.full:
+        dt = timed(eng, batches, args.steps, 0, ctx, row0, batch_total)
+        per_tag, probe_src = {}, {}     # no per-kernel table: the --full-only figures below stay empty
+    elif use_graph and graph_exec is not None and S_MULTI > 1:
         probed, seen = [], [0]
 
         def arm_group(k):
@@ -727,8 +795,10 @@ def main():
     eng.check_ids()
     log(f"timed region done: {dt / args.steps * 1e3:.3f} ms/step")
     pairs_per_s = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {', '.join(dump_outputs(eng, args.dump_outputs, B))}")
 
-    if deferred_mode and ctx is None and hasattr(eng, "last"):
+    if args.full and deferred_mode and ctx is None and hasattr(eng, "last"):
         ub, ib, _ = batches[_CURSOR.get(id(batches), 0) % len(batches)]
         lag_u = float((eng.last["user"][ub.long()].long() + 1 < eng.t + 1).float().mean().item())      # the next step is t + 1: rows must hold steps <= t
         lag_i = float((eng.last["item"][ib.long()].long() + 1 < eng.t + 1).float().mean().item())
@@ -783,7 +853,7 @@ def main():
         dom_key = None
 
     lazy = sweep_leg = flush_info = full_graph = None
-    if use_graph:
+    if args.full and use_graph:
         # the same graph without the two event-record nodes (what a training loop runs)
         try:
             if S_MULTI > 1:
@@ -807,7 +877,7 @@ def main():
         except Exception as exc:  # noqa: BLE001
             log(f"whole-step graph leg failed: {exc}")
             eng.disable_graph()
-    if deferred_mode and ctx is None and seeded is None:
+    if args.full and deferred_mode and ctx is None and seeded is None:
         # the deferred tables must be flushed at least every BR_ALPHA_RING-8 steps: run up to that point and
         # time the flush a long job pays there (worst case: every row replays a full ring of steps)
         period = eng.ALPHA_RING - 8
@@ -840,7 +910,7 @@ def main():
         del e2
         return {"value": B * world * args.steps / d2, "unit": "pairs/s", "ms_per_step": d2 / args.steps * 1e3}
 
-    if not args.no_lazy and args.optimizer == "adam_dense" and ctx is None:     # the extra legs are single-GPU information
+    if args.full and not args.no_lazy and args.optimizer == "adam_dense" and ctx is None:     # the extra legs are single-GPU information
         del eng
         if deferred_mode:
             sweep_leg = extra_leg("adam_dense", "sweep")
@@ -858,7 +928,7 @@ def main():
         del eng2
 
     legs = None
-    if rank == 0 and ctx is None and not args.no_legs:
+    if args.full and rank == 0 and ctx is None and not args.no_legs:
         ops = importlib.import_module("binary-recommendation_amd.ops")
         try:
             del eng
@@ -889,11 +959,23 @@ def main():
         torch.cuda.empty_cache()
 
     cpu = None
-    if rank == 0 and ctx is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and ctx is None and not args.no_cpu_baseline:
         log("cpu baseline start")
         cpu = cpu_baseline(args, D)
         log("cpu baseline done")
 
+    if use_graph and not args.full:
+        launch_mode = (f"hipGraph replay, {S_MULTI} consecutive steps per graph launch (NeuMFEngine.enable_graph_multi; the group's ids / labels staged by one launch)"
+                       if S_MULTI > 1 else "hipGraph replay of the whole step, one graph per step")
+    elif use_graph:
+        launch_mode = (((f"hipGraph replay, {S_MULTI} consecutive steps per graph launch (NeuMFEngine.enable_graph_multi; the group's ids / labels staged by one launch); "
+                         f"{dom_key} bracketed by event-record nodes around the last step of every 2nd group (a HIP event pair each)") if S_MULTI > 1 else
+                        f"hipGraph replay of the whole step, one graph per step; {dom_key} bracketed by event-record nodes inside every 4th replay (a HIP event pair each)")
+                       if graph_exec is not None else f"hipGraph replay (graph A -> eager {dom_key} with HIP events -> graph B)")
+    else:
+        launch_mode = (("sharded step incl. its RCCL collectives as one hipGraph per step" if sharded_graph is not None and sharded_graph.graph_active
+                        else "eager launches (brNeumfStepRun phases + torch.distributed collectives)" + (f" [graph refused: {sharded_graph._sgraph['refused']}]" if sharded_graph is not None and sharded_graph._sgraph else ""))
+                       if ctx is not None else "eager launches (brNeumfStepRun)")
     if rank == 0:
         line = {
             "metric": "(user,item) pairs/sec at batch 65536 dim 64", "value": pairs_per_s, "unit": "pairs/s",
@@ -906,18 +988,13 @@ def main():
                        "global_batch": batch_total, "parallelism": "single GPU" if ctx is None else f"row-sharded tables x{world} + dp{world}, {'global' if args.sync_bn else 'per-replica'} BatchNorm",
                        "steps_per_graph_launch": (S_MULTI if use_graph else None),
                        "optimizer": args.optimizer + (f" ({'deferred replay' if deferred_mode else 'per-step sweep'})" if args.optimizer == "adam_dense" else "")},
-            "roofline": roofline, "cpu_baseline": cpu, "legs": legs, "adam_lazy": lazy, "adam_dense_sweep": sweep_leg, "whole_step_graph": full_graph, "deferred_flush": flush_info, "gpu_kernel_us_per_step": gpu_us_per_step,
-            "unique_rows_per_batch": {"user": uniq_u, "item": uniq_i}, "lagging_rows_per_batch": {"user": lag_u, "item": lag_i}, "steady_state_lags": seeded,
-            "launch_mode": ((((f"hipGraph replay, {S_MULTI} consecutive steps per graph launch (NeuMFEngine.enable_graph_multi; the group's ids / labels staged by one launch); "
-                              f"{dom_key} bracketed by event-record nodes around the last step of every 2nd group (a HIP event pair each)") if S_MULTI > 1 else
-                             f"hipGraph replay of the whole step, one graph per step; {dom_key} bracketed by event-record nodes inside every 4th replay (a HIP event pair each)")
-                             if graph_exec is not None else f"hipGraph replay (graph A -> eager {dom_key} with HIP events -> graph B)") if use_graph
-                            else (("sharded step incl. its RCCL collectives as one hipGraph per step" if sharded_graph is not None and sharded_graph.graph_active
-                                   else "eager launches (brNeumfStepRun phases + torch.distributed collectives)" + (f" [graph refused: {sharded_graph._sgraph['refused']}]" if sharded_graph is not None and sharded_graph._sgraph else ""))
-                                  if ctx is not None else "eager launches (brNeumfStepRun)")),
-            "eager": eager_profile, "graph_error": graph_error,
-            "kernels": kernels,
+            "steady_state_lags": seeded,
+            "launch_mode": launch_mode, "graph_error": graph_error,
         }
+        if args.full:
+            line.update({"roofline": roofline, "cpu_baseline": cpu, "legs": legs, "adam_lazy": lazy, "adam_dense_sweep": sweep_leg, "whole_step_graph": full_graph,
+                         "deferred_flush": flush_info, "gpu_kernel_us_per_step": gpu_us_per_step, "unique_rows_per_batch": {"user": uniq_u, "item": uniq_i},
+                         "lagging_rows_per_batch": {"user": lag_u, "item": lag_i}, "eager": eager_profile, "kernels": kernels})
         print(json.dumps(line), file=json_out, flush=True)
     if ctx is not None:
         sys.stdout.flush(); sys.stderr.flush()

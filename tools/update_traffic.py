@@ -16,7 +16,7 @@ for k, b in by_full.items():
 commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=root, capture_output=True, text=True).stdout.strip()
 dirty = bool(subprocess.run(["git", "status", "--porcelain", "--", "binary-recommendation_amd", "bench.py"], cwd=root, capture_output=True, text=True).stdout.strip())
 out = {"hbm_bytes_per_launch": by_sym, "by_instantiation": by_full, "commit": commit + ("+uncommitted changes" if dirty else ""),
-       "source": f"{kept}: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 20 --warmup 5 --no-cpu-baseline "
+       "source": f"{kept}: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "
                  "--no-lazy --no-legs`; bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 correction, MI355X_MICROARCH.md HBM)"}
 json.dump(out, open(os.path.join(root, "profiles", "traffic_latest.json"), "w"), indent=1)
 os.makedirs(os.path.dirname(os.path.join(root, kept)), exist_ok=True)
