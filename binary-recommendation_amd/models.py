@@ -273,6 +273,7 @@ class NeuMFModel(RModel):
         from sklearn.model_selection import train_test_split
         numItem, numUser, df = self.readData(path, rowLimit)
         trainSplit, testSplit = train_test_split(df, test_size=self.testSize)
+        self._seen = (trainSplit.CUSTOMER_ID.to_numpy(), trainSplit.PRODUCT_ID.to_numpy())     # what recommendForUsers leaves out
         self._products = testSplit.PRODUCT_ID.unique().tolist()
         self._users = testSplit.CUSTOMER_ID.unique().tolist()
         bs = 128 if distributedConfig is None else self.batchSize     # NeuMFModel.py:43-48
@@ -297,12 +298,35 @@ class NeuMFModel(RModel):
     def getPredictableUsers(self) -> list:
         return list(self._users)
 
-    def predictForUser(self, customerId, numberOfItem=5, sort="float"):
-        """NeuMFModel.py:133-150 -> [(item, score)] as strings, best first.
+    def recommendForUsers(self, customerIds, numberOfItem=5, excludeSeen=True):
+        """predictForUser for a list of customers in one fused launch (NeuMFEngine.recommend): per customer [(item, score)] as strings,
+        best first (ties: the earlier product of getPredictableUsers' product list).  excludeSeen: leave out the products the customer
+        has in the training split (prepareToTrain)."""
+        from .topk_metrics import seen_csr
+        eng = self.model.engine
+        users = [int(u) for u in customerIds]
+        items = [int(i) for i in self._products]
+        ex = None
+        if excludeSeen:
+            su, si = getattr(self, "_seen", ((), ()))
+            ex = seen_csr(users, items, su.tolist() if hasattr(su, "tolist") else su, si.tolist() if hasattr(si, "tolist") else si, eng.device)
+        k = max(1, min(int(numberOfItem), 256))
+        ts, ti = eng.recommend(torch.tensor(users, dtype=eng.id_dtype, device=eng.device), k,
+                               items=torch.tensor(items, dtype=eng.id_dtype, device=eng.device), exclude=ex)
+        eng.check_ids()
+        ts, ti = ts.cpu().numpy(), ti.cpu().numpy()
+        return [[(str(items[int(ti[n, j])]), str(ts[n, j])) for j in range(min(k, int(numberOfItem))) if ti[n, j] >= 0]
+                for n in range(len(users))]
+
+    def predictForUser(self, customerId, numberOfItem=5, sort="float", excludeSeen=False):
+        """NeuMFModel.py:133-150 -> [(item, score)] as strings, best first.  excludeSeen=True: the customer's training-split products
+        are left out, through recommendForUsers (the fused catalogue top-k); the default keeps the reference's path below.
         The reference sorts the STRING scores (`sorted(extractFeatures.items(), key=lambda x: x[1], reverse=True)`, :150).
         For sigmoid outputs printed in positional notation ("0.73...") that is the numeric order; it differs only where str()
         switches to scientific notation (scores < 1e-4: "9.5e-05" sorts above "0.9").  sort="float" (default) ranks by value -
         what the endpoint means; sort="str" reproduces the reference's lexicographic order exactly."""
+        if excludeSeen:
+            return self.recommendForUsers([customerId], numberOfItem, excludeSeen=True)[0]
         items = np.asarray(self._products)
         p = self.model.predict({"user": np.full(len(items), customerId), "item": items}).reshape(-1)
         if sort == "str":
@@ -526,7 +550,8 @@ class TwoTowerModel:
 
     predict = call
 
-    def topk(self, usersId, itemsId, k):
+    def topk(self, usersId, itemsId, k, exclude=None):
+        """exclude: (off, idx) CSR over usersId of candidate positions never returned (topk_metrics.seen_csr); (-inf, -1) pads."""
         self.setCandidates(itemsId, k)
         q = self.engine.user_tower(self.userTowerIn(usersId, self.device))
-        return ops.topk_rows(ops.score_matrix(q, self._cand), k)
+        return ops.topk_rows(ops.score_matrix(q, self._cand), k, exclude=exclude)

@@ -686,6 +686,34 @@ class NeuMFEngine:
             out[s:e].copy_(self.prob[:e - s])
         return out
 
+    def recommend(self, users, k, items=None, exclude=None, dump_logits=None):
+        """The k best items of every user of `users` in inference mode (the sigmoid output predict returns), without scoring pairs
+        one by one: the first layer is split into a user and an item projection, BatchNorm folded into the next layer, and one fused
+        launch scores, masks and selects (csrc/recommend.hip).  items: the candidate ids (None: every item row); exclude: (off, idx)
+        CSR over `users` of candidate POSITIONS never to return (ops.truth_csr; topk_metrics.seen_csr maps raw ids).
+        -> (scores (U, k) float32, index (U, k) int32 positions into `items`) on the device, best first, ties to the lower position;
+        slots past the remaining candidates are (-inf, -1).  dump_logits=True also returns every pair's head logit (U x I)."""
+        if self.sharded:
+            raise NotImplementedError("recommend() on the row-sharded engine is not supported: the catalogue scoring needs every table "
+                                      "row on one device (DESIGN.md §7); score with a single-device engine")
+        cfg, dev = self.cfg, self.device
+        D, (n1, n2, n3) = cfg.dim, cfg.hidden
+        self.flush()                         # deferred-Adam rows lag until then (as _infer)
+        users = torch.as_tensor(users, device=dev)
+        if users.dtype not in (torch.int32, torch.int64):
+            users = users.to(self.id_dtype)
+        if items is None:
+            items = torch.arange(self.num_item_rows, dtype=users.dtype, device=dev)
+        items = torch.as_tensor(items, device=dev)
+        if items.dtype != users.dtype:
+            items = items.to(users.dtype)
+        users, items = users.contiguous(), items.contiguous()
+        th = {name: self.theta.view(name) for name in self.theta.offsets}
+        tower = ops.neumf_catalog_fold(th, self.moving, n1, n2, n3, cfg.mf_first, cfg.bn_eps)
+        pu = ops.neumf_catalog_project(self.fused["user"], users, th["W1"], n1, D, cfg.item_first, True, b1=th["b1"], err_flag=self.err)
+        pit = ops.neumf_catalog_project(self.fused["item"], items, th["W1"], n1, D, cfg.item_first, False, col_major=True, err_flag=self.err)
+        return ops.neumf_catalog_topk(pu, pit, tower, D, (n1, n2, n3), cfg.act, k, exclude=exclude, dump_logits=bool(dump_logits))
+
     def evaluate_batch(self, users, items, labels):
         """inference-mode forward + loss/metric sums accumulated into self.msums (no grads)."""
         self._infer(users, items, labels, users.shape[0])

@@ -559,13 +559,90 @@ def score_matrix(Q, C, out=None):
     return out
 
 
-def topk_rows(scores, k):
-    """stable top-k per row: descending, ties keep the lower column (topKmetrics.py:59,68)."""
+def topk_rows(scores, k, exclude=None):
+    """stable top-k per row: descending, ties keep the lower column (topKmetrics.py:59,68).  exclude = (off, idx), the CSR of
+    truth_csr over the rows: those columns are never returned and slots past the remaining columns are (-inf, -1)
+    (brTopKRowsExclude); exclude=None keeps brTopKRows."""
     U, I = scores.shape
     os_ = torch.empty(U, k, dtype=torch.float32, device=scores.device)
     oi = torch.empty(U, k, dtype=torch.int32, device=scores.device)
-    check(_lib.load().brTopKRows(_f32(scores, "scores").data_ptr(), U, I, int(k), os_.data_ptr(), oi.data_ptr(), _stream()), "brTopKRows")
+    if exclude is None:
+        check(_lib.load().brTopKRows(_f32(scores, "scores").data_ptr(), U, I, int(k), os_.data_ptr(), oi.data_ptr(), _stream()), "brTopKRows")
+        return os_, oi
+    off, idx = _csr(exclude, U, "exclude")
+    check(_lib.load().brTopKRowsExclude(_f32(scores, "scores").data_ptr(), U, I, int(k), off.data_ptr(), idx.data_ptr(), os_.data_ptr(),
+                                        oi.data_ptr(), _stream()), "brTopKRowsExclude")
     return os_, oi
+
+
+def _csr(csr, n_rows: int, name: str):
+    off, idx = csr
+    if (off.dtype != torch.int64 or idx.dtype != torch.int32 or not off.is_cuda or not idx.is_cuda or not off.is_contiguous()
+            or not idx.is_contiguous() or off.dim() != 1 or off.shape[0] != n_rows + 1):
+        raise TypeError(f"{name}: expected (off int64 [{n_rows + 1}], idx int32) contiguous device tensors (ops.truth_csr)")
+    if idx.numel() == 0:          # a valid pointer for an empty list
+        idx = torch.zeros(1, dtype=torch.int32, device=off.device)
+    return off, idx
+
+
+# ------------------------------------------------------------------------------ NeuMF catalogue top-k (csrc/recommend.hip)
+def neumf_catalog_fold(theta, moving, n1: int, n2: int, n3: int, mf_first: int, bn_eps: float, out=None):
+    """theta / moving: the engine's named views (W2 b2 g1 be1 W3 b3 g2 be2 W4 b4; mm1 mv1 mm2 mv2) -> the folded tower (BatchNorm into the
+    next layer, head in a fixed order) that neumf_catalog_topk reads."""
+    lib = _lib.load()
+    n = int(lib.brNeumfCatalogTowerFloats(n1, n2, n3))
+    if n < 0:
+        raise ValueError(f"tower widths n1, n2 <= 128 and n3 <= 32 (got {n1}, {n2}, {n3})")
+    dev = theta["W2"].device
+    out = torch.empty(n, dtype=torch.float32, device=dev) if out is None else out
+    t = [_f32(theta[k], k) for k in ("W2", "b2", "g1", "be1")] + [_f32(moving[k], k) for k in ("mm1", "mv1")]
+    t += [_f32(theta[k], k) for k in ("W3", "b3", "g2", "be2")] + [_f32(moving[k], k) for k in ("mm2", "mv2")]
+    t += [_f32(theta[k], k) for k in ("W4", "b4")]
+    check(lib.brNeumfCatalogFold(*[x.data_ptr() for x in t], n1, n2, n3, int(mf_first), float(bn_eps), out.data_ptr(), _stream()),
+          "brNeumfCatalogFold")
+    return out
+
+
+def neumf_catalog_project(table, ids, W1, n1: int, dim: int, item_first: int, user_side: bool, b1=None, col_major=False, err_flag=None):
+    """[mlp | mf] rows of `ids` -> (len(ids) x (n1 + dim)) row-major, or ((n1 + dim) x len(ids)) with col_major: the row's half of the first
+    layer (+ b1) followed by its mf half."""
+    ids, id_type = _ids(ids, "ids")
+    n = ids.shape[0]
+    out = torch.empty((n1 + dim, n) if col_major else (n, n1 + dim), dtype=torch.float32, device=table.device)
+    check(_lib.load().brNeumfCatalogProject(_f32(table, "table").data_ptr(), table.stride(0), table.shape[0], ids.data_ptr(), id_type, n, dim,
+                                            _f32(W1, "W1").data_ptr(), n1, int(item_first), int(bool(user_side)), _p(b1), 1,
+                                            out.data_ptr(), out.stride(0), int(bool(col_major)), _p(err_flag), _stream()),
+          "brNeumfCatalogProject")
+    return out
+
+
+def neumf_catalog_topk(pu, pit, tower, dim: int, hidden, act: str, k: int, exclude=None, dump_logits=False, dump_probs=False):
+    """pu (U x (n1 + dim)) and pit ((n1 + dim) x I) from neumf_catalog_project, tower from neumf_catalog_fold -> (scores (U, k) float32,
+    index (U, k) int32 positions into the item list) [, logits (U, I)] [, probs (U, I)]."""
+    n1, n2, n3 = hidden
+    U, I = pu.shape[0], pit.shape[1]
+    dev = pu.device
+    lib = _lib.load()
+    if not 1 <= int(k) <= 256:
+        raise ValueError(f"k = {k}: 1 <= k <= 256")
+    ws_bytes = int(lib.brNeumfCatalogTopKWorkspaceBytes(U, I, int(k)))
+    if ws_bytes < 0:
+        raise ValueError(f"neumf_catalog_topk: bad sizes U={U} I={I} k={k}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    os_ = torch.empty(U, k, dtype=torch.float32, device=dev)
+    oi = torch.empty(U, k, dtype=torch.int32, device=dev)
+    dl = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_logits else None
+    dp = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_probs else None
+    off, idx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
+    check(lib.brNeumfCatalogTopK(_f32(pu, "pu").data_ptr(), pu.stride(0), _f32(pit, "pit").data_ptr(), pit.stride(0), U, I, dim, n1, n2, n3,
+                                 ACT[act], _f32(tower, "tower").data_ptr(), _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(), _p(dl),
+                                 _p(dp), ws.data_ptr(), ws_bytes, _stream()), "brNeumfCatalogTopK")
+    out = (os_, oi)
+    if dump_logits:
+        out += (dl,)
+    if dump_probs:
+        out += (dp,)
+    return out
 
 
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts

@@ -14,12 +14,22 @@ import torch
 from . import ops
 
 
-def topk_scores_neumf(engine, user_ids, item_ids, k, users_per_chunk=None):
-    """Score every (user, item) pair of user_ids x item_ids through `engine.predict` and keep the k best
-    per user.  -> (scores (U,k) float32, index into item_ids (U,k) int32), both on the device."""
+def topk_scores_neumf(engine, user_ids, item_ids, k, users_per_chunk=None, method="pairs", exclude=None):
+    """Score every (user, item) pair of user_ids x item_ids and keep the k best per user.
+    -> (scores (U,k) float32, index into item_ids (U,k) int32), both on the device.
+    method="pairs": every pair through `engine.predict`, then brTopKRows over the score rows (the reference's protocol, the default);
+    method="fused": engine.recommend - the separable first layer, BatchNorm folded, scoring and selection in one launch
+    (csrc/recommend.hip; nothing per pair is written).  exclude: (off, idx) CSR over user_ids of item POSITIONS never returned
+    (seen_csr); slots past the remaining items are then (-inf, -1)."""
     dev = engine.device
     users = torch.as_tensor(np.asarray(user_ids), device=dev).to(engine.id_dtype)
     items = torch.as_tensor(np.asarray(item_ids), device=dev).to(engine.id_dtype)
+    if method == "fused":
+        out = engine.recommend(users, k, items=items, exclude=exclude)
+        engine.check_ids()
+        return out
+    if method != "pairs":
+        raise ValueError(f"method must be 'pairs' or 'fused', got {method!r}")
     U, I = users.shape[0], items.shape[0]
     if users_per_chunk is None:
         users_per_chunk = max(1, min(U, (1 << 22) // max(1, I)))
@@ -30,22 +40,49 @@ def topk_scores_neumf(engine, user_ids, item_ids, k, users_per_chunk=None):
         uu = users[s:e].repeat_interleave(I).contiguous()      # index plumbing only
         ii = items.repeat(e - s).contiguous()
         scores = engine.predict(uu, ii).view(e - s, I)
-        ts, ti = ops.topk_rows(scores, k)
+        ex = None
+        if exclude is not None:                                 # the chunk's rows of the CSR (index plumbing)
+            off, idx = exclude
+            o = off[s:e + 1]
+            ex = ((o - o[0]).contiguous(), idx[int(o[0]):int(o[-1])].contiguous())
+        ts, ti = ops.topk_rows(scores, k, exclude=ex)
         out_s[s:e], out_i[s:e] = ts, ti
     return out_s, out_i
 
 
-def topKRatings(k, model, usersId, itemsId, mtype=None):
+def seen_csr(usersId, itemsId, seen_users, seen_items, device=None):
+    """The "already seen" pairs (seen_users[j], seen_items[j]) (raw ids) as the exclusion CSR of topKRatings / recommend: one row per
+    entry of usersId (a user listed twice gets its list twice), columns = positions in itemsId, ascending.  Pairs whose user or item
+    is not in the lists are ignored.  Built on ops.truth_csr (host-side index plumbing)."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    col = {}
+    for j, i in enumerate(itemsId):
+        col.setdefault(i, j)
+    by_user = {}
+    for u, i in zip(seen_users, seen_items):
+        c = col.get(i)
+        if c is not None:
+            by_user.setdefault(u, []).append(c)
+    rows = [n for n, u in enumerate(usersId) for _ in by_user.get(u, ())]
+    cols = [c for u in usersId for c in by_user.get(u, ())]
+    return ops.truth_csr(len(usersId), rows, cols, device)
+
+
+def topKRatings(k, model, usersId, itemsId, mtype=None, *, method="pairs", exclude=None):
     """trainers/topKmetrics.py:17-43.  `model` is a NeuMF engine / Keras-like wrapper (mtype "NFC"), or
-    any object with `topk(users, items, k) -> (scores, index)` (TwoTower BruteForce)."""
+    any object with `topk(users, items, k) -> (scores, index)` (TwoTower BruteForce).  method / exclude: see topk_scores_neumf
+    (exclude also reaches a model's topk); excluded items never appear, so a list can be shorter than k."""
     engine = getattr(model, "engine", model)
     if mtype == "NFC" or hasattr(engine, "predict"):
-        ts, ti = topk_scores_neumf(engine, usersId, itemsId, k)
+        ts, ti = topk_scores_neumf(engine, usersId, itemsId, k, method=method, exclude=exclude)
+    elif exclude is not None:
+        ts, ti = model.topk(usersId, itemsId, k, exclude=exclude)
     else:
         ts, ti = model.topk(usersId, itemsId, k)
     ts, ti = ts.cpu().numpy(), ti.cpu().numpy()
     items = list(itemsId)
-    return [(u, [(float(ts[n, j]), items[int(ti[n, j])]) for j in range(ts.shape[1])]) for n, u in enumerate(usersId)]
+    return [(u, [(float(ts[n, j]), items[int(ti[n, j])]) for j in range(ts.shape[1]) if ti[n, j] >= 0]) for n, u in enumerate(usersId)]
 
 
 def topKMetrics(predictions, positives, usersId, itemsId):

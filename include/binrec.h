@@ -413,6 +413,45 @@ int brScoreMatrix(const float* Q, const float* C, int64_t n_q, int64_t n_c, int 
  * (strict '>' in __topk, topKmetrics.py:59,68).  out_scores/out_index: (U x k). */
 int brTopKRows(const float* scores, int64_t n_users, int64_t n_items, int k, float* out_scores,
                int32_t* out_index, brStream stream);
+/* brTopKRows with the seen items masked (src/models/bpr.py / twoTower.py candidate scoring, "unseen only"): excl_off (n_users + 1)
+ * int64 / excl_idx int32 = per user the ascending COLUMN indices that must not be returned (the CSR of brFullAuc; both NULL: none).
+ * Where fewer than k columns remain, the trailing slots are (-inf, -1).  k >= 1 (may exceed n_items). */
+int brTopKRowsExclude(const float* scores, int64_t n_users, int64_t n_items, int k, const int64_t* excl_off,
+                      const int32_t* excl_idx, float* out_scores, int32_t* out_index, brStream stream);
+
+/* ---- Catalogue top-k for NeuMF: csrc/recommend.hip ------------------------------------------------------------------------------
+ * Stands in for trainers/topKmetrics.py:17-43 (topKRatings / __topk: every (user, item) pair through model.predict, then a
+ * python insertion sort per user) and src/models/NeuMFModel.py:133-150 (predictForUser: one user against the product list), with
+ * the user's seen items optionally excluded.  Inference mode: BatchNorm on the moving statistics, no dropout.
+ * The first layer is separable, z1 = Pu[user] + Pi[item] (b1 on the user side), and each BatchNorm folds into the next layer:
+ * brNeumfCatalogFold: theta + moving -> the folded tower (brNeumfCatalogTowerFloats(n1, n2, n3) floats, layout private to the
+ *   library): W2' = diag(g1 rstd1) W2, b2' = b2 + (be1 - g1 mm1 rstd1) W2, the same for layer 3, and the head weights in the
+ *   order of mf_first (concat [dot, tower] when 1, [tower, dot] when 0).  rstd = 1 / sqrt(moving_var + bn_eps).
+ * brNeumfCatalogProject: out[n] = table[ids[n], 0:dim] . W1[half] (+ b1 when b1 != NULL), then (copy_mf) the row's mf half
+ *   table[ids[n], dim:2*dim] in columns n1 .. n1 + dim.  table = a fused [mlp | mf] table, row stride ld.  half = the user or the
+ *   item rows of W1 (2*dim x n1) for the concat order item_first (A: [item, user], B: [user, item]).  col_major = 0: out[n][c]
+ *   (row stride ld_out); 1: out[c][n] (column stride ld_out; the item side of brNeumfCatalogTopK).  ids outside [0, rows) set
+ *   BR_ERRFLAG_RANGE in *err_flag and produce zeros.
+ * brNeumfCatalogTopK: pu [n_users][ld_u] = projected users with their mf rows (row-major, copy_mf), pit [n1 + dim][ld_i] = projected
+ *   items with their mf rows (col_major, copy_mf); per user the k best candidate positions by the head's sigmoid output (the value
+ *   predict returns) -> out_scores / out_index (n_users x k, int32 positions into the item list), descending, ties keep the LOWER
+ *   position (brTopKRows).  excl_off / excl_idx (optional, the CSR of brTopKRowsExclude): positions never returned; where fewer than k
+ *   remain the trailing slots are (-inf, -1).  dump_logits / dump_probs (optional, n_users x n_items): every pair's head logit /
+ *   probability (tests).  act = BR_ACT_*.  Limits: 2*dim <= 256, n1, n2 <= 128, n3 <= 32, 1 <= k <= 256, n_items < 2^31; anything
+ *   else is BR_ERR_ARG before any launch.  ws: brNeumfCatalogTopKWorkspaceBytes(n_users, n_items, k) bytes (the per-split lists). */
+int64_t brNeumfCatalogTowerFloats(int n1, int n2, int n3);
+int brNeumfCatalogFold(const float* W2, const float* b2, const float* g1, const float* be1, const float* mm1, const float* mv1,
+                       const float* W3, const float* b3, const float* g2, const float* be2, const float* mm2, const float* mv2,
+                       const float* W4, const float* b4, int n1, int n2, int n3, int mf_first, float bn_eps, float* tower,
+                       brStream stream);
+int brNeumfCatalogProject(const float* table, int64_t ld, int64_t rows, const void* ids, int id_type, int64_t n, int dim,
+                          const float* W1, int n1, int item_first, int user_side, const float* b1, int copy_mf, float* out,
+                          int64_t ld_out, int col_major, int* err_flag, brStream stream);
+int64_t brNeumfCatalogTopKWorkspaceBytes(int64_t n_users, int64_t n_items, int k);
+int brNeumfCatalogTopK(const float* pu, int64_t ld_u, const float* pit, int64_t ld_i, int64_t n_users, int64_t n_items, int dim,
+                       int n1, int n2, int n3, int act, const float* tower, const int64_t* excl_off, const int32_t* excl_idx, int k,
+                       float* out_scores, int32_t* out_index, float* dump_logits, float* dump_probs, void* ws, int64_t ws_bytes,
+                       brStream stream);
 
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
