@@ -20,6 +20,7 @@ import os
 import torch
 
 from . import _lib, ops
+from .row_adam import RowAdam
 
 DENSE_ORDER = ("W1", "b1", "g1", "be1", "W2", "b2", "g2", "be2", "W3", "b3", "W4", "b4")
 TABLES = ("user_mlp", "item_mlp", "user_mf", "item_mf")
@@ -96,7 +97,7 @@ class _Flat:
         return self.buf[o0:o1 + n1]
 
 
-class NeuMFEngine:
+class NeuMFEngine(RowAdam):
     def __init__(self, cfg: NeuMFConfig, num_user_rows: int, num_item_rows: int, device, max_batch: int,
                  id_dtype=torch.int32, init_seed: int = 0, dist=None):
         self.cfg, self.device, self.max_batch, self.id_dtype = cfg, torch.device(device), int(max_batch), id_dtype
@@ -112,9 +113,6 @@ class NeuMFEngine:
         dev = self.device
         g = torch.Generator(device="cpu").manual_seed(init_seed)
         # [TF-sem] Embedding init U(-0.05, 0.05); Dense glorot-uniform; bias 0; BN gamma 1 beta 0
-        self.deferred = cfg.optimizer == "adam_dense" and cfg.dense_impl == "deferred"
-        self._stale = False                   # deferred: rows lag behind self.t until flush()
-        self._flush_t = 0
         self._init_tables(g, init_seed)
         self.theta = _Flat(cfg.dense_shapes(), dev)
         for k, (_, _, shp) in self.theta.offsets.items():
@@ -138,7 +136,6 @@ class NeuMFEngine:
                        "mm2": self.moving_buf[2 * n1:2 * n1 + n2], "mv2": self.moving_buf[2 * n1 + n2:]}
         self.moving["mv1"].fill_(1.0)
         self.moving["mv2"].fill_(1.0)
-        self.t = 0
         self._alloc(self.max_batch)
 
     def local_rows(self, name: str) -> int:
@@ -183,18 +180,6 @@ class NeuMFEngine:
         self.flush()
         return self._tab_v
 
-    def flush(self):
-        """Deferred dense Adam: apply the pending g = 0 steps to every row (brAdamFlush).  No-op otherwise."""
-        if not (self.deferred and self._stale):
-            return
-        cfg, lib = self.cfg, _lib.load()
-        for k in ("user", "item"):
-            t = self.fused[k]
-            _lib.check(lib.brAdamFlush(t.data_ptr(), self.fused_m[k].data_ptr(), self.fused_v[k].data_ptr(), self.last[k].data_ptr(),
-                                       t.shape[0], t.shape[1], self.step_state.data_ptr(), cfg.beta1, cfg.beta2, cfg.adam_eps, ops._stream()),
-                       "brAdamFlush")
-        self._stale, self._flush_t = False, self.t
-
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B):
         cfg, dev = self.cfg, self.device
@@ -234,6 +219,8 @@ class NeuMFEngine:
         self._keep_for = None                  # (step, row0) whose masks the planes hold (a training step prefetches the next one's)
         self.err = ops.new_err_flag(dev)
         self._alloc_sparse(B)
+        self._init_row_adam({k: (self.fused[k], self.fused_m[k], self.fused_v[k]) for k in ("user", "item")}, cfg.optimizer, cfg.dense_impl,
+                            cfg.lr, cfg.beta1, cfg.beta2, cfg.adam_eps, cfg.replay)
         self._build_step_struct()
 
     # ------------------------------------------------------------------ C step driver
@@ -266,7 +253,7 @@ class NeuMFEngine:
         st.user_tab, st.user_m, st.user_v = P(self.fused["user"]), P(self.fused_m["user"]), P(self.fused_v["user"])
         st.item_tab, st.item_m, st.item_v = P(self.fused["item"]), P(self.fused_m["item"]), P(self.fused_v["item"])
         if st.adam_dense == 1:
-            st.user_mark, st.item_mark = P(self.user_mark), P(self.item_mark)
+            st.user_mark, st.item_mark = P(self.mark["user"]), P(self.mark["item"])
         if self.deferred:
             if not self.sharded:
                 st.user_last, st.item_last = P(self.last["user"]), P(self.last["item"])
@@ -324,20 +311,12 @@ class NeuMFEngine:
         dev = self.device
         self.user_index = ops.RowIndex(B, self.id_dtype, dev)
         self.item_index = ops.RowIndex(B, self.id_dtype, dev)
-        if self.deferred:
-            self.last = {k: torch.zeros(self.local_rows(k + "_mf"), dtype=torch.int32, device=dev) for k in ("user", "item")}
-        elif self.cfg.optimizer == "adam_dense":
-            self.user_mark = torch.zeros(self.local_rows("user_mf"), dtype=torch.uint8, device=dev)
-            self.item_mark = torch.zeros(self.local_rows("item_mf"), dtype=torch.uint8, device=dev)
 
     def _alloc_step_state(self, st):
-        """device step state (include/binrec.h brStepStateBytes): {step, alpha_t, alpha ring}."""
-        if getattr(self, "step_state", None) is None:
-            self.step_state = ops.new_step_state(self.device, self.cfg.beta1, self.cfg.beta2, self.cfg.adam_eps, self.cfg.replay)
-        st.lr, st.step_state = self.cfg.lr, self.step_state.data_ptr()
-        self._sync_step_state()
+        """the device step state (made on first use: sweep and lazy tables need it only under graph replay) in the step struct, at t"""
+        st.lr, st.step_state = self.cfg.lr, self._step_state().data_ptr()
+        self._set_step_state()
 
-    ALPHA_RING = _lib.parse_enums()["BR_ALPHA_RING"]
     sharded = False   # the row-sharded subclass runs its own embed exchange (parallel.py)
 
     def _embed_forward(self, users, items, B):
@@ -358,10 +337,7 @@ class NeuMFEngine:
                 raise ValueError("empty local batch in a data-parallel step: give every rank at least one pair (pad or drop the ragged tail)")
             return
         batch_total = B if batch_total is None else batch_total
-        if self.deferred:
-            if self.t + 1 - self._flush_t >= self.ALPHA_RING - 8:      # the replay reads alpha_j from a ring
-                self.flush()
-            self._stale = True
+        self.begin_steps(1)
         self.t += 1
         if self._graph is not None and B == self._graph["batch"] and row0 == 0 and batch_total == B:
             self._replay(users, items, labels)
@@ -380,11 +356,10 @@ class NeuMFEngine:
         d, sync = self.dist, cfg.sync_bn
         emb = 0 if self.sharded else PH["EMBED"]
         if self.sharded:
-            if getattr(self, "step_state", None) is not None:
+            if self.step_state is not None:
                 # the lookup below replays against the device step counter: advance it first (the driver only does
                 # so in a call that holds FWD1|EMBED); the same launch clears the step's double scratch
-                _lib.check(_lib.load().brStepStateAdvance(self.step_state.data_ptr(), cfg.lr, cfg.beta1, cfg.beta2, self.dstat.data_ptr(),
-                                                          self.dstat.numel(), ops._stream()), "brStepStateAdvance")
+                self._advance_step_state(self.dstat)
             self._embed_forward(users, items, B)
         if not sync:
             # per-replica BatchNorm (what MirroredStrategy does with a plain BatchNormalization [TF-sem]): no collective
@@ -443,7 +418,7 @@ class NeuMFEngine:
         # the model state is put back afterwards
         keep = self._snapshot_for_dry_run()
         keep_sums = self.msums.clone()
-        self._sync_step_state()
+        self._set_step_state()
         self._set_batch(self.in_users, self.in_items, self.in_labels, B, True, 0, B)
         self._run(PH["ALL"])
         torch.cuda.synchronize(dev)
@@ -476,7 +451,7 @@ class NeuMFEngine:
             graphs.append(g)
         parts = [ph for ph, _ in parts]
         # the capture itself executes nothing, but the dry run above advanced the device step counter
-        self._sync_step_state()
+        self._set_step_state()
         self._keep_for = None                 # the dry run above left another step's planes
         self._graph = {"batch": B, "parts": parts, "graphs": graphs}
 
@@ -536,10 +511,7 @@ class NeuMFEngine:
             raise ValueError(f"train_steps: {S} batches of {B} pairs expected")
         self._check_batch(users, items, labels)
         cfg = self.cfg
-        if self.deferred:
-            if self.t + S - self._flush_t >= self.ALPHA_RING - 8:      # the replay reads alpha_j from a ring
-                self.flush()
-            self._stale = True
+        self.begin_steps(S)
         if users.data_ptr() != self.in_users_m.data_ptr() or items.data_ptr() != self.in_items_m.data_ptr() or labels.data_ptr() != self.in_labels_m.data_ptr():
             _lib.check(_lib.load().brStageBatch(self.in_users_m.data_ptr(), self.in_items_m.data_ptr(), self.in_labels_m.data_ptr(), users.data_ptr(),
                                                 items.data_ptr(), labels.data_ptr(), self.step_struct.id_type, S * B, ops._stream()), "brStageBatch")
@@ -557,10 +529,9 @@ class NeuMFEngine:
         would flush the tables: 42 GB cloned and every lag reset at config 5's shard size)."""
         if self.cfg.optimizer == "adam_dense" and not self.deferred:
             return {"full": {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.state_dict().items()}}
-        snap = {"rows": {}, "host": (self.t, self._flush_t, self._stale)}
-        for k, ids in (("user", self.in_users), ("item", self.in_items)):
-            idx = torch.unique(ids).long().clamp_(0, self.fused[k].shape[0] - 1)
-            snap["rows"][k] = (idx, self.fused[k][idx], self.fused_m[k][idx], self.fused_v[k][idx], self.last[k][idx] if self.deferred else None)
+        ids = {"user": self.in_users, "item": self.in_items}
+        snap = {"rows": self._snapshot_rows({k: torch.unique(i).long().clamp_(0, self.fused[k].shape[0] - 1) for k, i in ids.items()}),
+                "host": (self.t, self._flush_t, self._stale)}
         snap["dense"] = [t.clone() for t in (self.theta.buf, self.adam_m.buf, self.adam_v.buf, self.moving_buf)]
         return snap
 
@@ -568,20 +539,11 @@ class NeuMFEngine:
         if "full" in snap:
             self.load_state_dict(snap["full"])
             return
-        for k, (idx, th, m, v, last) in snap["rows"].items():
-            self.fused[k][idx] = th; self.fused_m[k][idx] = m; self.fused_v[k][idx] = v
-            if last is not None:
-                self.last[k][idx] = last
+        self._restore_rows(snap["rows"])
         for dst, src in zip((self.theta.buf, self.adam_m.buf, self.adam_v.buf, self.moving_buf), snap["dense"]):
             dst.copy_(src)
         self.t, self._flush_t, self._stale = snap["host"]
-        self._sync_step_state()
-
-    def _sync_step_state(self):
-        """device step state := (self.t, alpha_t, beta^t) (after enable_graph / load_state_dict)."""
-        if getattr(self, "step_state", None) is not None:
-            cfg = self.cfg
-            _lib.check(_lib.load().brStepStateSet(self.step_state.data_ptr(), self.t, cfg.lr, cfg.beta1, cfg.beta2, ops._stream()), "brStepStateSet")
+        self._set_step_state()
 
     def _replay(self, users, items, labels):
         if users.data_ptr() != self.in_users.data_ptr() or items.data_ptr() != self.in_items.data_ptr() or labels.data_ptr() != self.in_labels.data_ptr():
@@ -637,9 +599,6 @@ class NeuMFEngine:
         replayed: stream -> the fused rows as this step's deferred gather wrote them, by the same positions (a row-sharded owner:
         the rows it served) - the optimizer then replays the moments only."""
         cfg, D = self.cfg, self.cfg.dim
-        a = ops.adam_alpha(cfg.lr, self.t, cfg.beta1, cfg.beta2)
-        hp = dict(beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.adam_eps)
-        dense = cfg.optimizer == "adam_dense" and not self.deferred      # per-step sweep of the untouched rows
         if (self.deferred and replayed is not None and rg["user"][2] is None and rg["item"][2] is None
                 and self.user_index.n == self.item_index.n and rg["user"][1] == rg["item"][1] == 2 * D
                 and replayed["user"].stride(0) == replayed["item"].stride(0)):
@@ -648,21 +607,12 @@ class NeuMFEngine:
             ops.adam_rows_sorted_deferred_pair_replayed(
                 self.fused["user"], self.fused_m["user"], self.fused_v["user"], self.last["user"], self.user_index, rg["user"][0], replayed["user"],
                 self.fused["item"], self.fused_m["item"], self.fused_v["item"], self.last["item"], self.item_index, rg["item"][0], replayed["item"],
-                D, self.step_state, **hp)
+                D, self.step_state, cfg.beta1, cfg.beta2, cfg.adam_eps)
             return
-        for stream in ("user", "item"):
-            idx = self.user_index if stream == "user" else self.item_index
-            mark = (self.user_mark if stream == "user" else self.item_mark) if dense else None
-            g0, ld0, g1, ld1 = rg[stream]
-            if self.deferred:
-                ops.adam_rows_sorted_deferred(self.fused[stream], self.fused_m[stream], self.fused_v[stream], self.last[stream], idx, g0, ld0,
-                                              self.step_state, row_grads_hi=g1, ldg_hi=ld1, split=D if g1 is not None else 0,
-                                              replayed=None if replayed is None else replayed[stream], **hp)
-                continue
-            ops.adam_rows_sorted(self.fused[stream], self.fused_m[stream], self.fused_v[stream], idx, g0, ld0, a, mark=mark,
-                                 row_grads_hi=g1, ldg_hi=ld1, split=D if g1 is not None else 0, **hp)
-            if dense:
-                ops.adam_dense_sweep(self.fused[stream], self.fused_m[stream], self.fused_v[stream], a, mark=mark, **hp)
+        for k, idx in (("user", self.user_index), ("item", self.item_index)):
+            g0, ld0, g1, ld1 = rg[k]
+            self._adam_rows(k, idx, g0, ld0, g1, ld1, D if g1 is not None else 0, None if replayed is None else replayed[k])
+            self._adam_sweep(k)
 
     # ------------------------------------------------------------------ inference
     def _infer(self, users, items, labels, n):
@@ -747,11 +697,7 @@ class NeuMFEngine:
             self.fused[k].copy_(sd["table." + k]); self.fused_m[k].copy_(sd["table." + k + ".m"]); self.fused_v[k].copy_(sd["table." + k + ".v"])
         for k in self.moving:
             self.moving[k].copy_(sd[k])
-        if self.deferred:                   # a checkpoint holds flushed tables: every row includes step t
-            for k in ("user", "item"):
-                self.last[k].fill_(self.t)
-            self._stale, self._flush_t = False, self.t
-        self._sync_step_state()
+        self._reset_lags()
 
     def load_numpy_params(self, p: dict):
         """Load a parameter dict in the oracle's naming (tests / golden fixtures)."""

@@ -278,6 +278,30 @@ class RowIndex:
         return self
 
 
+class SideIndexes:
+    """Dedup indexes built on side streams of their own beside a step's other launches: start() forks them off `main` behind what is
+    already on it (the previous step's readers of the indexes), join() makes `main` wait for them.  Streams made once, on first use."""
+
+    def __init__(self, device):
+        self.device, self.streams = device, None
+
+    def start(self, main, jobs):
+        """jobs: (RowIndex, ids, id upper bound) per side stream"""
+        if self.streams is None:
+            self.streams = tuple(torch.cuda.Stream(device=self.device) for _ in jobs)
+            self.forked, self.built = torch.cuda.Event(), tuple(torch.cuda.Event() for _ in jobs)
+        self.forked.record(main)
+        for s, built, (idx, ids, upper) in zip(self.streams, self.built, jobs):
+            s.wait_event(self.forked)
+            with torch.cuda.stream(s):
+                idx.build(ids, upper)
+                built.record(s)
+
+    def join(self, main):
+        for built in self.built:
+            main.wait_event(built)
+
+
 def row_index_build_pair(idx_a: RowIndex, ids_a, upper_a: int, idx_b: RowIndex, ids_b, upper_b: int):
     """both dedup indexes of a step in shared launches (brRowIndexBuildPair); ids of equal length and type."""
     ta, ty = _ids(ids_a, "ids_a"); tb, tyb = _ids(ids_b, "ids_b")

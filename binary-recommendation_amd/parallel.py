@@ -378,11 +378,6 @@ def make_sharded_engine(base_cls):
             # an owner can receive more than B ids in a step; indexes are (re)grown on demand
             self._idx_cap = 0
             self._grow_index(2 * B)
-            if self.deferred:
-                self.last = {k: torch.zeros(self.local_rows(k + "_mf"), dtype=torch.int32, device=self.device) for k in ("user", "item")}
-            elif self.cfg.optimizer == "adam_dense":
-                self.user_mark = torch.zeros(self.local_rows("user_mf"), dtype=torch.uint8, device=self.device)
-                self.item_mark = torch.zeros(self.local_rows("item_mf"), dtype=torch.uint8, device=self.device)
 
         def _grow_index(self, n):
             if n > self._idx_cap:
@@ -423,7 +418,7 @@ def make_sharded_engine(base_cls):
                     W, cap = x.W, x.cap
                     for k, stream in enumerate(("user", "item")):
                         ids_k = rid.view(W, 2, cap)[:, k].contiguous().view(-1)
-                        rows_k = self._serve_rows(stream, ids_k)
+                        rows_k = self.rows_as_of_previous_step(stream, ids_k)
                         x.served.view(W, 2, cap, 2 * D)[:, k].copy_(rows_k.view(W, cap, 2 * D))
                 else:
                     ops.gather_rows_pair_seg(self.fused["user"], self.fused["item"], rid, x.served, S, x.seg, err_flag=self.err)
@@ -441,8 +436,8 @@ def make_sharded_engine(base_cls):
             ru, ri = xu.send_ids(), xi.send_ids()      # all-to-all #1
             empty = torch.empty(0, 2 * D, device=self.device)
             # owner-side G1 on the fused [mlp | mf] rows (512 B at dim 64)
-            gu = self._serve_rows("user", ru) if ru.numel() else empty
-            gi = self._serve_rows("item", ri) if ri.numel() else empty
+            gu = self.rows_as_of_previous_step("user", ru) if ru.numel() else empty
+            gi = self.rows_as_of_previous_step("item", ri) if ri.numel() else empty
             self._served = {"user": gu, "item": gi}    # kept for the optimizer: this rank's rows replayed to step t-1, by received slot
             self.r_user, self.r_item = xu.return_rows(gu), xi.return_rows(gi)      # all-to-all #2
             self.pos_u = xu.inv.to(self.id_dtype)
@@ -489,9 +484,7 @@ def make_sharded_engine(base_cls):
             _lib.check(_lib.load().brStageBatch(self.in_users.data_ptr(), self.in_items.data_ptr(), self.in_labels.data_ptr(), users.data_ptr(), items.data_ptr(),
                                                 labels.data_ptr(), self.step_struct.id_type, B, ops._stream()), "brStageBatch")
             if g["graph"] is not None and g["key"] == (row0, bt):
-                if self.t + 1 - self._flush_t >= self.ALPHA_RING - 8:
-                    self.flush()
-                self._stale = True
+                self.begin_steps(1)
                 self.t += 1
                 g["graph"].replay()
                 return
@@ -546,14 +539,6 @@ def make_sharded_engine(base_cls):
         def _infer(self, users, items, labels, n):
             self.sync_moving_stats()
             return super()._infer(users, items, labels, n)
-
-        def _serve_rows(self, stream, local_ids, out=None):
-            """owner side of the lookup: rows of this rank's shard for the ids its peers asked for."""
-            if self.deferred:      # rows as of the previous step, replayed in registers (binrec.h "Deferred dense Adam")
-                cfg = self.cfg
-                return ops.gather_rows_deferred(self.fused[stream], self.fused_m[stream], self.fused_v[stream], self.last[stream], local_ids,
-                                                self.step_state, cfg.beta1, cfg.beta2, cfg.adam_eps, out=out, err_flag=self.err)
-            return ops.gather_rows([self.fused[stream]], [local_ids], None if out is None else [out], err_flag=self.err)[0]
 
         def _embed_backward_apply(self, users, items, B):
             cfg, D = self.cfg, self.cfg.dim
@@ -709,8 +694,9 @@ def make_sharded_bpr(base_cls):
             if B > self.max_batch:
                 raise ValueError("batch exceeds max_batch")
             ctx, D = self.ctx, self.dim
+            self.begin_steps(1)
             if self.deferred:
-                self._advance()                                      # device step counter / alpha ring (the owner-side replay reads them)
+                self._advance_step_state()                           # device step counter / alpha ring (the owner-side replay reads them)
             self.t += 1
             bt = B * ctx.world if batch_total is None else batch_total
             ids2 = self.item_ids[:2 * B]
@@ -720,18 +706,8 @@ def make_sharded_bpr(base_cls):
             xu.exchange_counts(xi)                                   # the step's one host sync
             ru, ri = xu.send_ids(), xi.send_ids()
             empty = torch.empty(0, D, device=self.device)
-            hp = (self.BETA1, self.BETA2, self.EPS)
-
-            def serve(tab, m, v, last, ids):
-                """owner side of the lookup; deferred: rows as of the previous step, replayed in registers"""
-                if not ids.numel():
-                    return empty
-                if self.deferred:
-                    return ops.gather_rows_deferred(tab, m, v, last, ids, self.step_state, *hp, err_flag=self.err)
-                return ops.gather_rows([tab], [ids], err_flag=self.err)[0]
-
-            gu = serve(self._user, self.user_m, self.user_v, getattr(self, "user_last", None), ru)
-            gi = serve(self._item, self.item_m, self.item_v, getattr(self, "item_last", None), ri)
+            gu = self.rows_as_of_previous_step("user", ru) if ru.numel() else empty       # owner side of the lookup
+            gi = self.rows_as_of_previous_step("item", ri) if ri.numel() else empty
             bu, bi = xu.return_rows(gu), xi.return_rows(gi)          # bucket order
             if B == 0:
                 eu, ei = empty, empty
@@ -748,21 +724,12 @@ def make_sharded_bpr(base_cls):
             if max(xu.n_recv, xi.n_recv) > self._idx_cap:
                 self._idx_cap = int(1.25 * max(xu.n_recv, xi.n_recv)) + 64
                 self.user_index, self.item_index = ops.RowIndex(self._idx_cap, self.id_dtype, self.device), ops.RowIndex(self._idx_cap, self.id_dtype, self.device)
-            a = ops.adam_alpha(self.lr, self.t)
-            dense = self.optimizer == "adam_dense" and not self.deferred     # per-step sweep of the untouched rows
             for name, idx, ex, og, served in (("user", self.user_index, xu, ou, gu), ("item", self.item_index, xi, oi, gi)):
-                tab, m, v = getattr(self, "_" + name), getattr(self, name + "_m"), getattr(self, name + "_v")
-                mark = getattr(self, name + "_mark", None)
                 if ex.n_recv:
-                    idx.build(ex.recv_local, tab.shape[0])
-                    if self.deferred:
-                        # (the rows this rank served for these positions = its rows replayed to step t-1)
-                        ops.adam_rows_sorted_deferred(tab, m, v, getattr(self, name + "_last"), idx, og, D, self.step_state, *hp,
-                                                      replayed=served if served.shape[0] == ex.n_recv else None)
-                    else:
-                        ops.adam_rows_sorted(tab, m, v, idx, og, D, a, mark=mark if dense else None)
-                if dense:
-                    ops.adam_dense_sweep(tab, m, v, a, mark=mark)
+                    idx.build(ex.recv_local, getattr(self, "_" + name).shape[0])
+                    # (the rows this rank served for these positions = its rows replayed to step t-1)
+                    self._adam_rows(name, idx, og, D, replayed=served if served.shape[0] == ex.n_recv else None)
+                self._adam_sweep(name)
             self.n_seen += B
 
         def _gather_global(self, name, ids):

@@ -61,6 +61,7 @@ class TwoTowerEngine:
         self.slabs = f(self.ns * (E * S + S))
         self.dz_ws = f(ops.dense_backward_ws_floats(B, E, S))
         self.user_index, self.item_index = ops.RowIndex(B, id_dtype, dev), ops.RowIndex(B, id_dtype, dev)
+        self._side_index = ops.SideIndexes(dev)
         self.err = ops.new_err_flag(dev)
         self.t, self.n_seen = 0, 0
 
@@ -97,21 +98,12 @@ class TwoTowerEngine:
     def _start_indexes(self, users, items):
         """the two dedup indexes depend only on the ids: each on a side stream of its own beside the lookup / towers / softmax, joined in
         _apply_tables.  (The row-sharded subclass builds its indexes over the ids it RECEIVES and overrides this with a no-op.)"""
-        main = torch.cuda.current_stream(self.device)
-        if getattr(self, "_side", None) is None:
-            self._side = (torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device))
-            self._ev = (torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event())
-        self._ev[0].record(main)                   # the previous step's readers of the indexes are behind this point
-        for k, (idx, ids, rows) in enumerate(((self.user_index, users, self.user_emb.shape[0]), (self.item_index, items, self.item_emb.shape[0]))):
-            self._side[k].wait_event(self._ev[0])
-            with torch.cuda.stream(self._side[k]):
-                idx.build(ids, rows)
-                self._ev[1 + k].record(self._side[k])
+        self._side_index.start(torch.cuda.current_stream(self.device),
+                               ((self.user_index, users, self.user_emb.shape[0]), (self.item_index, items, self.item_emb.shape[0])))
 
     def _apply_tables(self, users, items, B):
         """S1 + O2/O1 on the two embedding tables from the per-pair row gradients deu / dei."""
-        main = torch.cuda.current_stream(self.device)
-        main.wait_event(self._ev[1]); main.wait_event(self._ev[2])
+        self._side_index.join(torch.cuda.current_stream(self.device))
         self._opt_rows(self.user_emb, self.user_acc, getattr(self, "user_v", None), self.user_index, self.deu[:B])
         self._opt_rows(self.item_emb, self.item_acc, getattr(self, "item_v", None), self.item_index, self.dei[:B])
 

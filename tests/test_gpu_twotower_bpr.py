@@ -287,8 +287,10 @@ def test_bpr_fused_gather_sort_step_equals_the_side_stream_step(dev, graph):
     torch.cuda.synchronize()
     a.check_ids(); b.check_ids()
     assert a.t == b.t == 6 and int(a.step_state[0].item()) == int(b.step_state[0].item()) == 6
-    for k in ("_user", "_item", "user_m", "user_v", "item_m", "item_v", "user_last", "item_last"):
+    for k in ("_user", "_item", "user_m", "user_v", "item_m", "item_v"):
         assert torch.equal(getattr(a, k), getattr(b, k)), k
+    for k in ("user", "item"):
+        assert torch.equal(a.last[k], b.last[k]), k
     assert abs(a.pop_loss() - b.pop_loss()) < 1e-9
 
 
