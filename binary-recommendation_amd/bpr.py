@@ -206,6 +206,29 @@ class BPREngine(RowAdam):
         it = self.item if item_ids is None else ops.gather_rows([self.item], [item_ids])[0]
         return ops.score_matrix(u, it)
 
+    def recommend(self, users, k, items=None, exclude=None, dump_scores=False):
+        """The k best items of every user of `users` by the dot score predict_scores returns, without the U x I matrix: one fused
+        launch scores, masks and selects (ops.dot_catalog_topk, csrc/recommend_dot.hip).  items: the candidate ids (None: the item
+        table in place); exclude: (off, idx) CSR over `users` of candidate POSITIONS never to return (topk_metrics.seen_csr).
+        -> (scores (U, k) float32, index (U, k) int32 positions into `items`) on the device, best first, ties to the lower position;
+        slots past the remaining candidates are (-inf, -1).  Ids outside the tables set self.err (check_ids raises)."""
+        self.flush()                         # deferred-Adam rows lag until then
+        users, items = self._recommend_ids(users, items)
+        q = ops.gather_rows([self._user], [users], err_flag=self.err)[0]
+        c = self._item if items is None else ops.gather_rows([self._item], [items], err_flag=self.err)[0]
+        return ops.dot_catalog_topk(q, c, k, exclude=exclude, dump_scores=dump_scores)
+
+    def _recommend_ids(self, users, items):
+        users = torch.as_tensor(users, device=self.device)
+        if users.dtype not in (torch.int32, torch.int64):
+            users = users.to(self.id_dtype)
+        if items is not None:
+            items = torch.as_tensor(items, device=self.device)
+            if items.dtype != users.dtype:
+                items = items.to(users.dtype)
+            items = items.contiguous()
+        return users.contiguous(), items
+
     def check_ids(self):
         ops.raise_if_flag(self.err)
 

@@ -18,15 +18,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "topk_list.h"
 
 namespace br {
 namespace {
 
-constexpr int kRecWaves = 4;              // users (waves) per workgroup
-constexpr int kRecSlots = 4;              // list entries per lane: k <= 256
-constexpr int kRecMaxK = 64 * kRecSlots;
 constexpr int64_t kRecTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
-constexpr int32_t kNoPos = 0x7FFFFFFF;    // empty list entry (score -inf): never beats anything, written out as -1
 
 // padded width of the second layer (the per-lane accumulator count): one instantiation per width
 int tower_width(int n2) {
@@ -62,89 +59,6 @@ void catalog_plan(int64_t n_users, int64_t n_items, int64_t* splits, int64_t* ch
   *chunks_per_split = cps;
   *splits = ceil_div(n_chunks, cps);
 }
-
-__device__ __forceinline__ bool beats(float s, int32_t p, float ts, int32_t tp) { return s > ts || (s == ts && p < tp); }
-
-__device__ __forceinline__ uint64_t wave_or64(uint64_t m) {
-  uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo |= (uint32_t)__shfl_xor((int)lo, off, 64);
-    hi |= (uint32_t)__shfl_xor((int)hi, off, 64);
-  }
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// A running top-k list held by one wave: entry e at slot e >> 6 of lane e & 63, sorted by (score desc, position asc).
-struct WaveList {
-  float s[kRecSlots];
-  int32_t p[kRecSlots];
-  float ts;      // the k-th entry (wave-uniform): a candidate must beat it
-  int32_t tp;
-
-  __device__ void init() {
-#pragma unroll
-    for (int r = 0; r < kRecSlots; ++r) { s[r] = -INFINITY; p[r] = kNoPos; }
-    ts = -INFINITY; tp = kNoPos;
-  }
-
-  // insert (cs, cp) (wave-uniform; the caller has checked that it beats the k-th entry)
-  __device__ void insert(float cs, int32_t cp, int k, int lane) {
-    int pos = 0;
-#pragma unroll
-    for (int r = 0; r < kRecSlots; ++r) {
-      const int e = r * 64 + lane;
-      pos += __popcll(__ballot(e < k && beats(s[r], p[r], cs, cp)));
-    }
-    float ps[kRecSlots];
-    int32_t pp[kRecSlots];
-#pragma unroll
-    for (int r = 0; r < kRecSlots; ++r) {          // entry e - 1: lane - 1 of the same slot, or lane 63 of the slot before
-      const float up_s = __shfl_up(s[r], 1, 64);
-      const int32_t up_p = __shfl_up(p[r], 1, 64);
-      const float wr_s = r ? __shfl(s[r - 1], 63, 64) : -INFINITY;
-      const int32_t wr_p = r ? __shfl(p[r - 1], 63, 64) : kNoPos;
-      ps[r] = lane ? up_s : wr_s;
-      pp[r] = lane ? up_p : wr_p;
-    }
-#pragma unroll
-    for (int r = 0; r < kRecSlots; ++r) {
-      const int e = r * 64 + lane;
-      if (e == pos) { s[r] = cs; p[r] = cp; }
-      else if (e > pos) { s[r] = ps[r]; p[r] = pp[r]; }
-    }
-    const int last = k - 1, slot = last >> 6;
-    float ls = s[0];
-    int32_t lp = p[0];
-#pragma unroll
-    for (int r = 1; r < kRecSlots; ++r) if (r == slot) { ls = s[r]; lp = p[r]; }   // (no runtime register indexing)
-    ts = __shfl(ls, last & 63, 64);
-    tp = __shfl(lp, last & 63, 64);
-  }
-
-  // offer one candidate per lane (ok = lane has one); lanes are taken in ascending order
-  __device__ void offer(float cs, int32_t cp, bool ok, int k, int lane) {
-    uint64_t bal = __ballot(ok && beats(cs, cp, ts, tp));
-    while (bal) {
-      const int l = __ffsll((unsigned long long)bal) - 1;
-      bal &= bal - 1;
-      const float vs = __shfl(cs, l, 64);
-      const int32_t vp = __shfl(cp, l, 64);
-      if (beats(vs, vp, ts, tp)) insert(vs, vp, k, lane);
-    }
-  }
-
-  __device__ void store(float* out_s, int32_t* out_p, int k, int lane, bool final_form) const {
-#pragma unroll
-    for (int r = 0; r < kRecSlots; ++r) {
-      const int e = r * 64 + lane;
-      if (e < k) {
-        out_s[e] = s[r];
-        out_p[e] = (final_form && p[r] == kNoPos) ? -1 : p[r];
-      }
-    }
-  }
-};
 
 template <typename IdT>
 __global__ __launch_bounds__(256) void catalog_project_kernel(const float* __restrict__ table, int64_t ld, int64_t rows,
@@ -315,26 +229,6 @@ __global__ __launch_bounds__(256) void catalog_topk_kernel(const float* __restri
   list.store(part_s + o, part_p + o, k, lane, false);
 }
 
-// one wave per user: the n_splits lists of k entries -> the final top-k
-__global__ __launch_bounds__(256) void catalog_merge_kernel(const float* __restrict__ part_s, const int32_t* __restrict__ part_p,
-                                                             int64_t n_users, int64_t n_splits, int k, float* __restrict__ out_s,
-                                                             int32_t* __restrict__ out_p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = (int64_t)blockIdx.x * kRecWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (u >= n_users) return;
-  const int64_t n = n_splits * k;
-  const float* s = part_s + u * n;
-  const int32_t* p = part_p + u * n;
-  WaveList list;
-  list.init();
-  for (int64_t base = 0; base < n; base += 64) {
-    const int64_t q = base + lane;
-    const bool ok = q < n;
-    list.offer(ok ? s[q] : -INFINITY, ok ? p[q] : kNoPos, ok, k, lane);
-  }
-  list.store(out_s + u * k, out_p + u * k, k, lane, true);
-}
-
 // brTopKRows with the exclusion CSR: one score row per workgroup, k passes, excluded columns skipped, (-inf, -1) past the end
 __global__ __launch_bounds__(256) void topk_rows_exclude_kernel(const float* __restrict__ scores, int64_t n_items, int k,
                                                                  const int64_t* __restrict__ ex_off, const int32_t* __restrict__ ex_idx,
@@ -394,8 +288,6 @@ void launch_catalog_topk(dim3 grid, hipStream_t st, const float* pu, int64_t ld_
   else
     catalog_topk_kernel<W, BR_ACT_LINEAR><<<grid, 256, 0, st>>>(pu, ld_u, pit, ld_i, U, I, dim, n1, n3, tower, L, ex_off, ex_idx, k, cps, S, ps, pp, dl, dp);
 }
-
-int64_t part_bytes(int64_t U, int64_t S, int k) { return (U * S * k * (int64_t)sizeof(float) + 255) / 256 * 256; }
 
 bool tower_shape_ok(int n1, int n2, int n3) { return n1 >= 1 && n1 <= 128 && n2 >= 1 && n2 <= 128 && n3 >= 1 && n3 <= 32; }
 

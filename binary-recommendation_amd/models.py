@@ -414,8 +414,12 @@ class BPRModel(RModel):
         has = np.array([len(t) > 0 for _u, t in gt])
         return float(np.mean(auc[has]))
 
-    def mean_average_precision_k(self, ground_truth, items, k=100) -> float:
-        """mean_average_precision_k (src/models/bpr.py:257-289): AP of the top-k of the bpr_predict scores per user / min(len(actual), k)."""
+    def mean_average_precision_k(self, ground_truth, items, k=100, method="matrix") -> float:
+        """mean_average_precision_k (src/models/bpr.py:257-289): AP of the top-k of the bpr_predict scores per user / min(len(actual), k).
+        method="matrix": score_matrix + brTopKRows (the default); "fused": the same lists from BPREngine.recommend without the
+        users x items matrix (k <= 256)."""
+        if method not in ("matrix", "fused"):
+            raise ValueError(f"method must be 'matrix' or 'fused', got {method!r}")
         gt = list(ground_truth)
         col = {it: j for j, it in enumerate(items)}
         rows = [r for r, (_u, t) in enumerate(gt) for _ in t]
@@ -423,7 +427,12 @@ class BPRModel(RModel):
         rows = [r for r, (_u, t) in enumerate(gt) for p in t if p in col]
         off, idx = ops.truth_csr(len(gt), rows, cols, self.model.device)
         k = min(int(k), len(items))
-        _ts, ti = ops.topk_rows(self._scores([u for u, _ in gt], items), k)
+        if method == "fused":
+            e = self.model
+            _ts, ti = e.recommend(_to_dev(np.asarray([u for u, _ in gt]), e.device, e.id_dtype), k,
+                                  items=_to_dev(np.asarray(items), e.device, e.id_dtype))
+        else:
+            _ts, ti = ops.topk_rows(self._scores([u for u, _ in gt], items), k)
         ap, _ = ops.map_at_k(ti, off, idx, want_hits=False)
         # brMapAtK divides by min(truth items it was given, k); the reference by min(len(actual), k) with EVERY listed item, also those
         # outside `items` (bpr.py:286): rescale per user on the host (tiny vectors).  A user without positives: the reference divides by
@@ -432,6 +441,34 @@ class BPRModel(RModel):
         want = np.array([len(t) for _u, t in gt], dtype=np.float64)
         scale = np.where(want > 0, np.minimum(have, k) / np.maximum(np.minimum(want, k), 1.0), 0.0)
         return float((ap.double().cpu().numpy() * scale).mean())
+
+    # ---- recommendation (the reference's BPRModel has none): the fused dot-product catalogue top-k ----
+    def getPredictableUsers(self) -> list:
+        """the customers of the training split: the users whose rows the model has learned"""
+        return self.trainDf.CUSTOMER_ID.unique().tolist()
+
+    def recommendForUsers(self, customerIds, numberOfItem=5, excludeSeen=True):
+        """per customer [(item, score)] as strings, best first (ties: the earlier product of the training split's product list), in
+        one fused launch (BPREngine.recommend).  Candidates: the training split's products; excludeSeen: leave out the products the
+        customer has in the training split.  On a row-sharded engine this is a collective (every rank calls it for its customers)."""
+        from .topk_metrics import seen_csr
+        e = self.model
+        users = [int(u) for u in customerIds]
+        items = [int(i) for i in self.productIds]
+        ex = None
+        if excludeSeen:
+            ex = seen_csr(users, items, self.trainDf.CUSTOMER_ID.tolist(), self.trainDf.PRODUCT_ID.tolist(), e.device)
+        k = max(1, min(int(numberOfItem), 256))
+        ts, ti = e.recommend(torch.tensor(users, dtype=e.id_dtype, device=e.device), k,
+                             items=torch.tensor(items, dtype=e.id_dtype, device=e.device), exclude=ex)
+        e.check_ids()
+        ts, ti = ts.cpu().numpy(), ti.cpu().numpy()
+        return [[(str(items[int(ti[n, j])]), str(ts[n, j])) for j in range(min(k, int(numberOfItem))) if ti[n, j] >= 0]
+                for n in range(len(users))]
+
+    def predictForUser(self, customerId, numberOfItem=5, excludeSeen=False):
+        """[(item, score)] as strings, best first, for one customer: recommendForUsers([customerId]) (excludeSeen off by default)."""
+        return self.recommendForUsers([customerId], numberOfItem, excludeSeen=excludeSeen)[0]
 
     def fit(self, X: dict, y=None, batch_size=64, epochs=1, seed=0):
         """model.fit({'customerId_input','pProduct_input','nProduct_input'}, ones, batch_size, epochs) (BPRModel.py:100-109)."""
@@ -550,8 +587,14 @@ class TwoTowerModel:
 
     predict = call
 
-    def topk(self, usersId, itemsId, k, exclude=None):
-        """exclude: (off, idx) CSR over usersId of candidate positions never returned (topk_metrics.seen_csr); (-inf, -1) pads."""
+    def topk(self, usersId, itemsId, k, exclude=None, method="matrix"):
+        """exclude: (off, idx) CSR over usersId of candidate positions never returned (topk_metrics.seen_csr); (-inf, -1) pads.
+        method="matrix": score_matrix + brTopKRows (the default); "fused": ops.dot_catalog_topk on the tower outputs, same lists
+        without the users x items matrix (tower width <= 128, k <= 256)."""
+        if method not in ("matrix", "fused"):
+            raise ValueError(f"method must be 'matrix' or 'fused', got {method!r}")
         self.setCandidates(itemsId, k)
         q = self.engine.user_tower(self.userTowerIn(usersId, self.device))
+        if method == "fused":
+            return ops.dot_catalog_topk(q, self._cand, k, exclude=exclude)
         return ops.topk_rows(ops.score_matrix(q, self._cand), k, exclude=exclude)

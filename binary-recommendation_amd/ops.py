@@ -669,6 +669,51 @@ def neumf_catalog_topk(pu, pit, tower, dim: int, hidden, act: str, k: int, exclu
     return out
 
 
+# ------------------------------------------------------------------------------ dot-product catalogue top-k (csrc/recommend_dot.hip)
+def _rows_f32(t, name: str):
+    """a 2-D float32 device matrix with unit column stride and row stride >= its width (a table as it is, or a column slice of one)"""
+    if t.dtype != torch.float32 or not t.is_cuda:
+        raise TypeError(f"{name}: expected a float32 device tensor, got {t.dtype} {t.device}")
+    if t.shape[1] > 0 and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        raise TypeError(f"{name}: rows must be unit-stride with row stride >= {t.shape[1]} (got strides {tuple(t.stride())})")
+    return t
+
+
+def dot_catalog_topk(Q, C, k, exclude=None, dump_scores=False):
+    """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim) -> (scores (U, k) float32, index (U, k) int32 positions
+    into C) [, every pair's score (U, I)]: per user the k best Q[u] . C[i], best first, ties to the lower position, exclude positions
+    (ops.truth_csr over the rows of Q) never returned, (-inf, -1) past the remaining candidates; the U x I matrix is not stored."""
+    for t, name in ((Q, "Q"), (C, "C")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"dot_catalog_topk: {name} must be a 2-D tensor")
+    U, dim = Q.shape
+    I = C.shape[0]
+    if C.shape[1] != dim:
+        raise ValueError(f"dot_catalog_topk: Q has dim {dim}, C has {C.shape[1]}")
+    if not 1 <= dim <= 128:
+        raise ValueError(f"dot_catalog_topk: dim = {dim}: 1 <= dim <= 128")
+    if not 1 <= int(k) <= 256:
+        raise ValueError(f"k = {k}: 1 <= k <= 256")
+    _rows_f32(Q, "Q"); _rows_f32(C, "C")
+    if Q.device != C.device:
+        raise ValueError("dot_catalog_topk: Q and C on different devices")
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotCatalogTopKWorkspaceBytes(U, I, int(k)))
+    if ws_bytes < 0:
+        raise ValueError(f"dot_catalog_topk: bad sizes U={U} I={I} k={k}")
+    dev = Q.device
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    os_ = torch.empty(U, k, dtype=torch.float32, device=dev)
+    oi = torch.empty(U, k, dtype=torch.int32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    off, idx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
+    ld_q = Q.stride(0) if U > 1 else dim
+    ld_c = C.stride(0) if I > 1 else dim
+    check(lib.brDotCatalogTopK(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(),
+                               _p(dump), ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogTopK")
+    return (os_, oi, dump) if dump_scores else (os_, oi)
+
+
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts
 def truth_csr(n_users: int, user_rows, item_cols, device):
     """Ground truth of `n_users` rows as the CSR the eval kernels take: (offsets int64 (n_users + 1), column indices int32 ascending

@@ -752,6 +752,17 @@ def make_sharded_bpr(base_cls):
             it = self._gather_global("item", item_ids)
             return ops.score_matrix(u, it)
 
+        def recommend(self, users, k, items=None, exclude=None, dump_scores=False):
+            """BPREngine.recommend on row-sharded tables: the user rows (and the candidate rows, every item when items is None) come
+            through the id -> owner exchange of predict_scores, then the fused top-k runs locally.  A collective: every rank calls it
+            and gets the lists of ITS users."""
+            users, items = self._recommend_ids(users, items)
+            u = self._gather_global("user", users.to(self.id_dtype))
+            if items is None:
+                items = torch.arange(self.num_items_global, device=self.device)
+            it = self._gather_global("item", items.to(self.id_dtype))
+            return ops.dot_catalog_topk(u, it, k, exclude=exclude, dump_scores=dump_scores)
+
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 
         def save_sharded(self, path):

@@ -70,19 +70,37 @@ def seen_csr(usersId, itemsId, seen_users, seen_items, device=None):
 
 
 def topKRatings(k, model, usersId, itemsId, mtype=None, *, method="pairs", exclude=None):
-    """trainers/topKmetrics.py:17-43.  `model` is a NeuMF engine / Keras-like wrapper (mtype "NFC"), or
-    any object with `topk(users, items, k) -> (scores, index)` (TwoTower BruteForce).  method / exclude: see topk_scores_neumf
-    (exclude also reaches a model's topk); excluded items never appear, so a list can be shorter than k."""
+    """trainers/topKmetrics.py:17-43.  `model` is a NeuMF engine / Keras-like wrapper (mtype "NFC"), a BPR engine or BPRModel
+    (through recommend: the fused dot-product top-k), or any object with `topk(users, items, k) -> (scores, index)` (TwoTower
+    BruteForce).  method / exclude: see topk_scores_neumf (both also reach a model's topk; method "pairs" is not passed on, so
+    "matrix" is its default); excluded items never appear, so a list can be shorter than k."""
     engine = getattr(model, "engine", model)
+    dot = _dot_engine(model)
     if mtype == "NFC" or hasattr(engine, "predict"):
         ts, ti = topk_scores_neumf(engine, usersId, itemsId, k, method=method, exclude=exclude)
-    elif exclude is not None:
-        ts, ti = model.topk(usersId, itemsId, k, exclude=exclude)
+    elif dot is not None:
+        dev = dot.device
+        ts, ti = dot.recommend(torch.as_tensor(np.asarray(usersId), device=dev).to(dot.id_dtype), k,
+                               items=torch.as_tensor(np.asarray(itemsId), device=dev).to(dot.id_dtype), exclude=exclude)
+        dot.check_ids()
     else:
-        ts, ti = model.topk(usersId, itemsId, k)
+        kw = {} if method == "pairs" else {"method": method}
+        if exclude is not None:
+            kw["exclude"] = exclude
+        ts, ti = model.topk(usersId, itemsId, k, **kw)
     ts, ti = ts.cpu().numpy(), ti.cpu().numpy()
     items = list(itemsId)
     return [(u, [(float(ts[n, j]), items[int(ti[n, j])]) for j in range(ts.shape[1]) if ti[n, j] >= 0]) for n, u in enumerate(usersId)]
+
+
+def _dot_engine(model):
+    """the engine of a dot-product model that recommends but has no pairwise predict and no topk (a BPR engine, or BPRModel's)"""
+    if hasattr(model, "topk"):
+        return None
+    for e in (model, getattr(model, "model", None)):
+        if e is not None and hasattr(e, "recommend") and not hasattr(e, "predict"):
+            return e
+    return None
 
 
 def topKMetrics(predictions, positives, usersId, itemsId):

@@ -453,6 +453,22 @@ int brNeumfCatalogTopK(const float* pu, int64_t ld_u, const float* pit, int64_t 
                        float* out_scores, int32_t* out_index, float* dump_logits, float* dump_probs, void* ws, int64_t ws_bytes,
                        brStream stream);
 
+/* ---- Catalogue top-k for dot-product models (BPR, TwoTower): csrc/recommend_dot.hip ------------------------------------------------
+ * Stands in for score_matrix + brTopKRows over the whole U x I matrix (bpr.py predict_scores, mean_average_precision_k, TwoTower
+ * topk) without storing it.
+ * brDotCatalogTopK: Q [n_users][ld_q] (row-major user rows), C [n_items][ld_c] (row-major item rows: a BPR table as it is); per user the
+ *   k best item positions by score(u, i) = sum_j Q[u][j] C[i][j] in fp32 (features in natural order, one fmaf chain from 0: a pair's
+ *   score depends on its two rows only) -> out_scores / out_index (n_users x k, int32 positions into C), descending, ties keep the
+ *   LOWER position (brTopKRows).  excl_off / excl_idx (optional, the CSR of brTopKRowsExclude): positions never returned; where fewer
+ *   than k remain the trailing slots are (-inf, -1).  dump_scores (optional, n_users x n_items): every pair's score (tests).
+ *   Limits: 1 <= dim <= 128, 1 <= k <= 256, n_items < 2^31, ld_q, ld_c >= dim (16-B aligned item rows take the float4 path, any other
+ *   stride a scalar one with the same scores); anything else is BR_ERR_ARG before any launch.
+ *   ws: brDotCatalogTopKWorkspaceBytes(n_users, n_items, k) bytes (the per-split lists); -1 for sizes outside the limits. */
+int64_t brDotCatalogTopKWorkspaceBytes(int64_t n_users, int64_t n_items, int k);
+int brDotCatalogTopK(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                     const int64_t* excl_off, const int32_t* excl_idx, int k, float* out_scores, int32_t* out_index,
+                     float* dump_scores, void* ws, int64_t ws_bytes, brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the
