@@ -218,6 +218,17 @@ class BPREngine(RowAdam):
         c = self._item if items is None else ops.gather_rows([self._item], [items], err_flag=self.err)[0]
         return ops.dot_catalog_topk(q, c, k, exclude=exclude, dump_scores=dump_scores)
 
+    def full_auc(self, users, truth, items=None, dump_scores=False):
+        """Per-user full AUC (src/models/bpr.py:230-254) of the dot scores predict_scores returns, without the U x I matrix: the fused
+        launches of ops.dot_catalog_auc (csrc/auc_dot.hip).  truth: (off, idx) CSR over `users` of candidate POSITIONS, ascending
+        (ops.truth_csr); items: the candidate ids (None: the item table in place).  -> float32 (U,) on the device, NaN for a user
+        without positives or without negatives.  Ids outside the tables set self.err (check_ids raises)."""
+        self.flush()                         # deferred-Adam rows lag until then
+        users, items = self._recommend_ids(users, items)
+        q = ops.gather_rows([self._user], [users], err_flag=self.err)[0]
+        c = self._item if items is None else ops.gather_rows([self._item], [items], err_flag=self.err)[0]
+        return ops.dot_catalog_auc(q, c, truth[0], truth[1], dump_scores=dump_scores)
+
     def _recommend_ids(self, users, items):
         users = torch.as_tensor(users, device=self.device)
         if users.dtype not in (torch.int32, torch.int64):

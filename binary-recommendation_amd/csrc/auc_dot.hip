@@ -1,0 +1,432 @@
+// Full-catalogue AUC for dot-product models (include/binrec.h "Catalogue AUC"): per user the Mann-Whitney statistic of brFullAuc
+// (eval.hip) over score(u, i) = sum_j Q[u][j] C[i][j] in fp32, without the U x I score matrix:
+//
+//   AUC(u) = W / (P N),  2W = sum over positives p and negatives i of 2 [s_i < s_p] + [s_i == s_p]
+//
+// Three launches:
+//   - auc_pos_kernel: one wave per user scores the user's truth entries on the same v_mfma_f32_16x16x4_f32, with the same feature
+//     order and zero padding, as the catalogue pass (so a positive's score is bit for bit the one the catalogue pass sees), then
+//     sorts them ascending by counting rank (O(P^2) compares per user), NaN scores dropped; the count P' of the rest goes beside;
+//   - dot_auc_kernel: the tile loop of dot_topk_kernel (recommend_dot.hip): 4 waves, 32 users per wave with their A fragments in
+//     registers, 64-item steps streamed through LDS with the next step in flight.  Each lane takes its 32 scores per step: a
+//     positive (the truth CSR walked with a cursor and a 64-bit window mask, as the exclusion there) or a NaN score adds 0, a
+//     score below the user's smallest positive 2P', above the largest 0, and one inside [min, max] 2 #{positives > s} +
+//     #{positives == s} by a branchless binary search of the sorted list (the 16 searches of a lane's row tile step in lockstep, so
+//     their loads are issued together).  The sorted lists of a wave's users sit in LDS when they fit (kAucLdsCap), in global memory
+//     (L2) otherwise.  Per user and item split one 64-bit partial 2W;
+//   - auc_finalize_kernel: 2W summed over the splits in integers, then (float)((double)W / ((double)P (double)N)), brFullAuc's
+//     rounding: the result equals brFullAuc on the same scores bit for bit (exact while P N < 2^53), whatever the plan.
+#include <math.h>
+
+#include "common.h"
+
+namespace br {
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int64_t kAucTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
+constexpr int kAucRT = 2, kAucCT = 4;     // 32 users per wave, 64 items per step
+constexpr int kAucUW = 16 * kAucRT, kAucNT = 16 * kAucCT;
+constexpr int kAucLdsCap = 2048;          // sorted positives of a wave's 32 users kept in LDS up to this many (8 KB per wave)
+
+void auc_plan(int64_t n_users, int64_t n_items, int64_t* splits, int64_t* steps_per_split) {
+  const int64_t n_steps = ceil_div(n_items, kAucNT), wgs = ceil_div(n_users > 0 ? n_users : 1, 4 * kAucUW);
+  int64_t s = ceil_div(kAucTargetWgs, wgs);
+  if (s > n_steps) s = n_steps;
+  if (s > 65535) s = 65535;
+  if (s < 1) s = 1;
+  const int64_t sps = ceil_div(n_steps, s);
+  *steps_per_split = sps;
+  *splits = ceil_div(n_steps, sps);
+}
+
+int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// workspace: partials uint64 [n_users][splits], P' int32 [n_users], then the raw and the sorted positive scores, float [n_truth + 1]
+// each (the tail is split in two halves; its size bounds the truth entries a call can take)
+int64_t auc_fixed_bytes(int64_t n_users, int64_t n_items) {
+  int64_t S, sps;
+  auc_plan(n_users, n_items, &S, &sps);
+  return align256(n_users * S * 8) + align256(n_users * 4);
+}
+
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// one wave per user: score its truth entries, sort them ascending (NaN dropped) into sorted[off[u] ...], P' into pcnt[u] (-1: the
+// user's entries lie past the workspace's capacity `cap`)
+template <int KB>
+__global__ __launch_bounds__(256) void auc_pos_kernel(const float* __restrict__ Q, int64_t ld_q, int64_t n_users, const float* __restrict__ C,
+                                                       int64_t ld_c, int64_t n_items, int dim, const int64_t* __restrict__ off,
+                                                       const int32_t* __restrict__ idx, float* raw, float* __restrict__ sorted,
+                                                       int32_t* __restrict__ pcnt, int64_t cap) {
+  __shared__ float chunk[4][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+  if (u >= n_users) return;
+  const int64_t o0 = off[u], o1 = off[u + 1], P = o1 - o0;
+  if (P <= 0 || o0 < 0 || o1 > cap) {
+    if (lane == 0) pcnt[u] = P <= 0 ? 0 : -1;
+    return;
+  }
+  // A: the user's row in all 16 rows (lane l: feature 4 kb + (l >> 4)), as the catalogue pass holds its users
+  float qa[KB];
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+    const int f = 4 * kb + (lane >> 4);
+    qa[kb] = f < dim ? Q[u * ld_q + f] : 0.f;
+  }
+  for (int64_t c0 = 0; c0 < P; c0 += 16) {
+    const int64_t j = c0 + (lane & 15);
+    const int64_t p = j < P ? (int64_t)idx[o0 + j] : -1;
+    const bool ok = p >= 0 && p < n_items;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      const int f = 4 * kb + (lane >> 4);
+      const float b = ok && f < dim ? C[p * ld_c + f] : 0.f;      // B[k][j] = C[positive j][feature 4 kb + k]
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[kb], b, acc, 0, 0, 0);
+    }
+    // D: lane l < 16, register 0 = row 0, column l = score(u, positive c0 + l); an entry outside [0, n_items) scores NaN (no credit)
+    if (lane < 16 && j < P) raw[o0 + j] = ok ? acc[0] : __builtin_nanf("");
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");           // this wave's raw stores before its loads below
+  __builtin_amdgcn_wave_barrier();
+
+  // counting rank: rank(i) = #{j: s_j < s_i} + #{j < i: s_j == s_i}; NaN compares false, so NaN entries take no rank
+  float* const ch = chunk[wave];
+  int64_t nn = 0;
+  for (int64_t i0 = 0; i0 < P; i0 += 64) {
+    const int64_t i = i0 + lane;
+    const float si = i < P ? raw[o0 + i] : __builtin_nanf("");
+    int64_t rank = 0;
+    for (int64_t j0 = 0; j0 < P; j0 += 64) {
+      wave_lds_order();
+      ch[lane] = j0 + lane < P ? raw[o0 + j0 + lane] : __builtin_nanf("");
+      wave_lds_order();
+      const int m = P - j0 < 64 ? (int)(P - j0) : 64;
+      uint32_t r = 0;
+      for (int t = 0; t < m; ++t) {
+        const float v = ch[t];
+        r += (v < si) | ((v == si) & (j0 + t < i));
+      }
+      rank += r;
+    }
+    if (si == si) sorted[o0 + rank] = si;
+    nn += __popcll(__ballot(si == si));
+  }
+  if (lane == 0) pcnt[u] = (int32_t)nn;
+}
+
+template <int KB>
+__global__ __launch_bounds__(256) void dot_auc_kernel(const float* __restrict__ Q, int64_t ld_q, int64_t n_users, const float* __restrict__ C,
+                                                       int64_t ld_c, int64_t n_items, int dim, int vec, const int64_t* __restrict__ off,
+                                                       const int32_t* __restrict__ idx, const float* __restrict__ sorted,
+                                                       const int32_t* __restrict__ pcnt, int64_t cap, int64_t steps_per_split,
+                                                       int64_t n_splits, uint64_t* __restrict__ part, float* __restrict__ dump) {
+  constexpr int RT = kAucRT, CT = kAucCT, UW = kAucUW, NT = kAucNT;
+  constexpr int LD = 4 * KB + 4;           // item tile row stride (floats): KB even -> the B-fragment reads hit 64 distinct banks
+  constexpr int CHUNKS = NT * KB;          // float4 chunks per item tile
+  constexpr int CPT = (CHUNKS + 255) / 256;
+  static_assert(NT <= 64 && KB % 2 == 0, "tile shape");
+  __shared__ __attribute__((aligned(16))) float tile[NT * LD];
+  __shared__ float pos_s[4 * kAucLdsCap];
+  __shared__ uint64_t xm_s[4 * UW];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t u0 = ((int64_t)blockIdx.x * 4 + wave) * UW;         // first user of this wave
+  const bool active = u0 < n_users;                                   // (inactive waves still take part in the barriers)
+  const int64_t split = blockIdx.y;
+  const int64_t p0 = split * steps_per_split * NT;
+  const int64_t p1 = p0 + steps_per_split * NT < n_items ? p0 + steps_per_split * NT : n_items;
+  float* const PS = pos_s + wave * kAucLdsCap;
+  uint64_t* const XM = xm_s + wave * UW;
+
+  // user rows as A fragments: lane l holds Q[u0 + 16 rt + (l & 15)][4 kb + (l >> 4)]
+  float qa[RT][KB];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    const int64_t u = u0 + 16 * rt + (lane & 15);
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      const int f = 4 * kb + (lane >> 4);
+      qa[rt][kb] = (u < n_users && f < dim) ? Q[u * ld_q + f] : 0.f;
+    }
+  }
+
+  // the sorted positives of the wave's users: in LDS when they fit (and lie inside the workspace), else read from `sorted`
+  const int64_t u_end = u0 + UW < n_users ? u0 + UW : n_users;
+  const int64_t w0 = active ? off[u0] : 0, w1 = active ? off[u_end] : 0;
+  const bool in_lds = active && w0 >= 0 && w1 >= w0 && w1 <= cap && w1 - w0 <= kAucLdsCap;
+  if (in_lds)
+    for (int64_t e = lane; e < w1 - w0; e += 64) PS[e] = sorted[w0 + e];
+  // the lane's users (rt, r): user u0 + 16 rt + 4 (lane >> 4) + r: P', list start, smallest and largest positive
+  int np[RT][4], lb[RT][4];                                           // (lb: relative to w0 or to `sorted`, < cap < 2^31)
+  float mn[RT][4], mx[RT][4];
+  uint64_t w2[RT][4];
+  int top = 0;                                                        // largest P' of the lane's users
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t u = u0 + 16 * rt + 4 * (lane >> 4) + r;
+      const int n = u < n_users ? pcnt[u] : 0;
+      np[rt][r] = n > 0 ? n : 0;
+      lb[rt][r] = n > 0 ? (int)(off[u] - (in_lds ? w0 : 0)) : 0;      // (0 for an empty list: every load stays in bounds)
+      mn[rt][r] = n > 0 ? sorted[off[u]] : INFINITY;
+      mx[rt][r] = n > 0 ? sorted[off[u] + n - 1] : -INFINITY;
+      w2[rt][r] = 0;
+      top = np[rt][r] > top ? np[rt][r] : top;
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int t = __shfl_xor(top, o, 64);
+    top = t > top ? t : top;
+  }
+  int step0 = 0;                                                      // highest power of two <= top (wave-uniform)
+  if (top > 0) step0 = 1 << (31 - __builtin_clz((unsigned)top));
+
+  // truth cursor of user u0 + lane: the first entry of its list at or after p0, and that entry's position
+  int64_t ex_cur = 0, ex_end = 0, ex_nxt = INT64_MAX;
+  if (lane < UW && u0 + lane < n_users) {
+    int64_t lo = off[u0 + lane], hi = off[u0 + lane + 1];
+    ex_end = hi;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)idx[mid] < p0) lo = mid + 1; else hi = mid;
+    }
+    ex_cur = lo;
+    if (ex_cur < ex_end) ex_nxt = idx[ex_cur];
+  }
+
+  float4 pre[CPT];
+  auto load_tile = [&](int64_t start) {
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+      const int chunk = c * 256 + tid;
+      const int it = chunk / KB, f = 4 * (chunk % KB);
+      const int64_t p = start + it;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (chunk < CHUNKS && p < p1 && f < dim) {
+        const float* row = C + p * ld_c + f;
+        if (vec) {
+          v = *reinterpret_cast<const float4*>(row);
+        } else {
+          v.x = row[0];
+          if (f + 1 < dim) v.y = row[1];
+          if (f + 2 < dim) v.z = row[2];
+          if (f + 3 < dim) v.w = row[3];
+        }
+      }
+      pre[c] = v;
+    }
+  };
+  load_tile(p0);
+
+  for (int64_t base = p0; base < p1; base += NT) {
+    __syncthreads();                                                  // the previous step's tile reads are done
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+      const int chunk = c * 256 + tid;
+      if (chunk < CHUNKS) *reinterpret_cast<float4*>(tile + (chunk / KB) * LD + 4 * (chunk % KB)) = pre[c];
+    }
+    __syncthreads();
+    if (base + NT < p1) load_tile(base + NT);                         // in flight while this step is scored
+    if (!active) continue;
+
+    // this window's positive mask of user u0 + lane (lanes < UW), handed to the lanes that hold the user's scores through LDS
+    uint64_t xm = 0;
+    while (ex_nxt < base + NT) {
+      if (ex_nxt >= base) xm |= 1ull << (ex_nxt - base);
+      ++ex_cur;
+      ex_nxt = ex_cur < ex_end ? (int64_t)idx[ex_cur] : INT64_MAX;
+    }
+    const bool any_ex = __ballot(xm != 0) != 0;
+    if (any_ex) {
+      if (lane < UW) XM[lane] = xm;
+      wave_lds_order();
+    }
+
+    f32x4 acc[RT][CT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const float b = tile[(16 * ct + (lane & 15)) * LD + 4 * kb + (lane >> 4)];   // B[k][j] = C[item j][feature 4 kb + k]
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[rt][kb], b, acc[rt][ct], 0, 0, 0);
+      }
+    }
+
+    // D: lane l, register r = score(user u0 + 16 rt + 4 (l >> 4) + r, item base + 16 ct + (l & 15)), user (rt, r) of the lane.
+    // A score counts unless its item is one of the user's positives or lies past the split; fast paths first, then the scores
+    // inside [min, max] of their user (never NaN, never a user without positives) search the sorted list, one row tile at a time
+    const int pl = lane & 15;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      uint64_t m[4] = {0, 0, 0, 0};
+      if (any_ex) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[r] = XM[16 * rt + 4 * (lane >> 4) + r];
+      }
+      auto counts = [&](int ct, int r) { return base + 16 * ct + pl < p1 && !((m[r] >> (16 * ct + pl)) & 1); };
+      auto inside = [&](int ct, int r) {
+        const float s = acc[rt][ct][r];
+        return counts(ct, r) && s >= mn[rt][r] && s <= mx[rt][r];
+      };
+      bool any_in = false;
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float s = acc[rt][ct][r];
+          const int64_t p = base + 16 * ct + pl;
+          const int row = 16 * rt + 4 * (lane >> 4) + r;
+          if (dump && p < p1 && u0 + row < n_users) dump[(u0 + row) * n_items + p] = s;
+          if (counts(ct, r) && s < mn[rt][r]) w2[rt][r] += 2 * (uint64_t)np[rt][r];
+          any_in |= inside(ct, r);
+        }
+      if (__ballot(any_in) == 0) continue;
+
+      // c = #{entries < s} (le: <= s) by binary lifting over the user's np entries: the 16 searches step in lockstep
+      auto search = [&](const float* A, int (&c)[CT][4], bool le) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) c[ct][r] = 0;
+        for (int step = step0; step > 0; step >>= 1) {
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int j = c[ct][r] + step;
+              const bool in = j <= np[rt][r];
+              const float v = A[lb[rt][r] + (in ? j - 1 : 0)];
+              const float s = acc[rt][ct][r];
+              if (in && (le ? v <= s : v < s)) c[ct][r] = j;
+            }
+        }
+      };
+      auto entry = [&](const float* A, int ct, int r, int l) __attribute__((always_inline)) {
+        return A[lb[rt][r] + (l < np[rt][r] ? l : 0)];
+      };
+      int lo[CT][4], hi[CT][4];
+      bool any_tie = false;
+      if (in_lds) search(PS, lo, false); else search(sorted, lo, false);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = in_lds ? entry(PS, ct, r, lo[ct][r]) : entry(sorted, ct, r, lo[ct][r]);
+          any_tie |= inside(ct, r) && lo[ct][r] < np[rt][r] && v == acc[rt][ct][r];
+          hi[ct][r] = lo[ct][r];
+        }
+      if (__ballot(any_tie)) {
+        if (in_lds) search(PS, hi, true); else search(sorted, hi, true);
+      }
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (inside(ct, r)) {                                        // 2 #{> s} + #{== s} of np < 2^31 entries: fits 32 bits
+            const uint32_t n = (uint32_t)np[rt][r], l = (uint32_t)lo[ct][r], h = (uint32_t)hi[ct][r];
+            w2[rt][r] += 2u * (n - h) + (h - l);
+          }
+    }
+  }
+
+  if (!active) return;
+  // the 16 lanes of a lane group hold the same users: sum them, one partial per (user, split)
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      uint64_t v = w2[rt][r];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      const int64_t u = u0 + 16 * rt + 4 * (lane >> 4) + r;
+      if ((lane & 15) == 0 && u < n_users) part[u * n_splits + split] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void auc_finalize_kernel(const uint64_t* __restrict__ part, int64_t n_splits, const int64_t* __restrict__ off,
+                                                            const int32_t* __restrict__ pcnt, int64_t n_users, int64_t n_items,
+                                                            float* __restrict__ auc) {
+  const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= n_users) return;
+  const int64_t P = off[u + 1] - off[u], N = n_items - P;
+  if (P <= 0 || N <= 0 || pcnt[u] < 0) {
+    auc[u] = __builtin_nanf("");
+    return;
+  }
+  uint64_t w2 = 0;
+  for (int64_t s = 0; s < n_splits; ++s) w2 += part[u * n_splits + s];
+  auc[u] = (float)((double)w2 * 0.5 / ((double)P * (double)N));
+}
+
+template <int KB>
+void launch_auc(int64_t S, int64_t sps, hipStream_t st, const float* Q, int64_t ld_q, int64_t U, const float* C, int64_t ld_c, int64_t I,
+                int dim, int vec, const int64_t* off, const int32_t* idx, float* raw, float* sorted, int32_t* pcnt, int64_t cap,
+                uint64_t* part, float* dump) {
+  auc_pos_kernel<KB><<<(unsigned)ceil_div(U, 4), 256, 0, st>>>(Q, ld_q, U, C, ld_c, I, dim, off, idx, raw, sorted, pcnt, cap);
+  const dim3 grid((unsigned)ceil_div(U, 4 * kAucUW), (unsigned)S);
+  dot_auc_kernel<KB><<<grid, 256, 0, st>>>(Q, ld_q, U, C, ld_c, I, dim, vec, off, idx, sorted, pcnt, cap, sps, S, part, dump);
+}
+
+}  // namespace
+}  // namespace br
+
+using namespace br;
+
+extern "C" int64_t brDotCatalogAucWorkspaceBytes(int64_t n_users, int64_t n_items, int64_t n_truth) {
+  if (n_users < 0 || n_items < 1 || n_items >= ((int64_t)1 << 31) || n_truth < 0) return -1;
+  return auc_fixed_bytes(n_users, n_items) + 2 * align256(4 * (n_truth + 1));
+}
+
+extern "C" int brDotCatalogAuc(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                               const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, void* ws,
+                               int64_t ws_bytes, brStream stream) {
+  BR_CHECK_ARG(Q && C && truth_off && truth_idx && out_auc && ws, "brDotCatalogAuc: null pointer");
+  BR_CHECK_ARG(dim >= 1 && dim <= 128, "brDotCatalogAuc: dim = %d outside [1, 128]", dim);
+  BR_CHECK_ARG(n_users >= 0 && n_items >= 1 && n_items < ((int64_t)1 << 31), "brDotCatalogAuc: bad sizes (1 <= n_items < 2^31)");
+  BR_CHECK_ARG(ld_q >= dim && ld_c >= dim, "brDotCatalogAuc: ld_q, ld_c >= dim (got %lld, %lld, dim %d)", (long long)ld_q,
+               (long long)ld_c, dim);
+  const int64_t fixed = auc_fixed_bytes(n_users, n_items), least = brDotCatalogAucWorkspaceBytes(n_users, n_items, 0);
+  if (ws_bytes < least) {
+    br::set_error("brDotCatalogAuc: workspace %lld bytes < %lld", (long long)ws_bytes, (long long)least);
+    return BR_ERR_WORKSPACE;
+  }
+  if (n_users == 0) return BR_OK;
+  int64_t S, sps;
+  auc_plan(n_users, n_items, &S, &sps);
+  const int64_t half = (ws_bytes - fixed) / 2 / 256 * 256;         // >= align256(4): one float of padding at least
+  uint64_t* part = (uint64_t*)ws;
+  int32_t* pcnt = (int32_t*)((char*)ws + align256(n_users * S * 8));
+  float* raw = (float*)((char*)ws + fixed);
+  float* sorted = (float*)((char*)ws + fixed + half);
+  int64_t cap = half / 4 - 1;                                        // truth entries [0, cap) fit; a user past them gets NaN
+  if (cap > INT32_MAX) cap = INT32_MAX;
+  const int vec = dim % 4 == 0 && ld_c % 4 == 0 && ((uintptr_t)C & 15) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int kb = (dim + 3) / 4;
+#define BR_AUC_ARGS S, sps, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, truth_off, truth_idx, raw, sorted, pcnt, cap, part, dump_scores
+  if (kb <= 4) launch_auc<4>(BR_AUC_ARGS);
+  else if (kb <= 8) launch_auc<8>(BR_AUC_ARGS);
+  else if (kb <= 16) launch_auc<16>(BR_AUC_ARGS);
+  else if (kb <= 24) launch_auc<24>(BR_AUC_ARGS);
+  else launch_auc<32>(BR_AUC_ARGS);
+#undef BR_AUC_ARGS
+  BR_CHECK_LAUNCH("brDotCatalogAuc");
+  auc_finalize_kernel<<<(unsigned)ceil_div(n_users, 256), 256, 0, st>>>(part, S, truth_off, pcnt, n_users, n_items, out_auc);
+  BR_CHECK_LAUNCH("brDotCatalogAuc finalize");
+  return BR_OK;
+}

@@ -399,9 +399,13 @@ class BPRModel(RModel):
         it = _to_dev(np.asarray(items), e.device, e.id_dtype)
         return e.predict_scores(u, it)                                   # bpr_predict (bpr.py:122-133) for all users at once
 
-    def full_auc(self, ground_truth, items) -> float:
+    def full_auc(self, ground_truth, items, method="matrix") -> float:
         """full_auc (src/models/bpr.py:230-254): mean over the users that have positives of roc_auc_score(ground truth over all
-        `items`, bpr_predict scores).  ground_truth: iterable of (user_id, [true item ids])."""
+        `items`, bpr_predict scores).  ground_truth: iterable of (user_id, [true item ids]).
+        method="matrix": score_matrix + brFullAuc (the default); "fused": BPREngine.full_auc, the same per-user values without the
+        users x items matrix."""
+        if method not in ("matrix", "fused"):
+            raise ValueError(f"method must be 'matrix' or 'fused', got {method!r}")
         gt = list(ground_truth)
         col = {it: j for j, it in enumerate(items)}
         missing = [p for _u, t in gt for p in t if p not in col]
@@ -410,7 +414,14 @@ class BPRModel(RModel):
         rows = [r for r, (_u, t) in enumerate(gt) for _ in t]
         cols = [col[p] for _u, t in gt for p in t]
         off, idx = ops.truth_csr(len(gt), rows, cols, self.model.device)
-        auc = ops.full_auc(self._scores([u for u, _ in gt], items), off, idx).cpu().numpy()
+        if method == "fused":
+            e = self.model
+            auc = e.full_auc(_to_dev(np.asarray([u for u, _ in gt]), e.device, e.id_dtype), (off, idx),
+                             items=_to_dev(np.asarray(items), e.device, e.id_dtype))
+            e.check_ids()
+            auc = auc.cpu().numpy()
+        else:
+            auc = ops.full_auc(self._scores([u for u, _ in gt], items), off, idx).cpu().numpy()
         has = np.array([len(t) > 0 for _u, t in gt])
         return float(np.mean(auc[has]))
 

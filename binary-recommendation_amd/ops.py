@@ -714,6 +714,40 @@ def dot_catalog_topk(Q, C, k, exclude=None, dump_scores=False):
     return (os_, oi, dump) if dump_scores else (os_, oi)
 
 
+# ------------------------------------------------------------------------------ dot-product catalogue AUC (csrc/auc_dot.hip)
+def dot_catalog_auc(Q, C, truth_off, truth_idx, dump_scores=False):
+    """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim), truth (ops.truth_csr over the rows of Q: ascending
+    positions into C) -> per-user AUC float32 (U,) [, every pair's score (U, I)]: full_auc of the scores Q[u] . C[i], equal bit for
+    bit to full_auc(score_matrix(Q, C), truth_off, truth_idx) on the same scores, NaN where undefined; the U x I matrix is not stored."""
+    for t, name in ((Q, "Q"), (C, "C")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"dot_catalog_auc: {name} must be a 2-D tensor")
+    U, dim = Q.shape
+    I = C.shape[0]
+    if C.shape[1] != dim:
+        raise ValueError(f"dot_catalog_auc: Q has dim {dim}, C has {C.shape[1]}")
+    if not 1 <= dim <= 128:
+        raise ValueError(f"dot_catalog_auc: dim = {dim}: 1 <= dim <= 128")
+    _rows_f32(Q, "Q"); _rows_f32(C, "C")
+    if Q.device != C.device:
+        raise ValueError("dot_catalog_auc: Q and C on different devices")
+    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
+    off, idx = _csr((truth_off, truth_idx), U, "truth")
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotCatalogAucWorkspaceBytes(U, I, n_truth))
+    if ws_bytes < 0:
+        raise ValueError(f"dot_catalog_auc: bad sizes U={U} I={I}")
+    dev = Q.device
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.float32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    ld_q = Q.stride(0) if U > 1 else dim
+    ld_c = C.stride(0) if I > 1 else dim
+    check(lib.brDotCatalogAuc(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
+                              ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogAuc")
+    return (out, dump) if dump_scores else out
+
+
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts
 def truth_csr(n_users: int, user_rows, item_cols, device):
     """Ground truth of `n_users` rows as the CSR the eval kernels take: (offsets int64 (n_users + 1), column indices int32 ascending

@@ -763,6 +763,16 @@ def make_sharded_bpr(base_cls):
             it = self._gather_global("item", items.to(self.id_dtype))
             return ops.dot_catalog_topk(u, it, k, exclude=exclude, dump_scores=dump_scores)
 
+        def full_auc(self, users, truth, items=None, dump_scores=False):
+            """BPREngine.full_auc on row-sharded tables: the rows come through the id -> owner exchange of recommend, then the fused AUC
+            runs locally.  A collective: every rank calls it and gets the AUCs of ITS users."""
+            users, items = self._recommend_ids(users, items)
+            u = self._gather_global("user", users.to(self.id_dtype))
+            if items is None:
+                items = torch.arange(self.num_items_global, device=self.device)
+            it = self._gather_global("item", items.to(self.id_dtype))
+            return ops.dot_catalog_auc(u, it, truth[0], truth[1], dump_scores=dump_scores)
+
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 
         def save_sharded(self, path):

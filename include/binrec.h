@@ -469,6 +469,23 @@ int brDotCatalogTopK(const float* Q, int64_t ld_q, int64_t n_users, const float*
                      const int64_t* excl_off, const int32_t* excl_idx, int k, float* out_scores, int32_t* out_index,
                      float* dump_scores, void* ws, int64_t ws_bytes, brStream stream);
 
+/* ---- Catalogue AUC for dot-product models (BPR, TwoTower): csrc/auc_dot.hip ---------------------------------------------------------
+ * Stands in for score_matrix + brFullAuc (full_auc, src/models/bpr.py:230-254) without storing the U x I score matrix.
+ * brDotCatalogAuc: Q [n_users][ld_q], C [n_items][ld_c] and the scores of brDotCatalogTopK (features in natural order, one fmaf chain
+ *   from 0); truth_off (n_users + 1) / truth_idx: per user the ascending, unique positions into C of its positives (ops.truth_csr,
+ *   the CSR of brFullAuc).  out_auc[u] = W / (P N) with P = the user's truth entries, N = n_items - P and W = sum over positives p
+ *   and the other items i of [s_i < s_p] + [s_i == s_p] / 2, summed exactly and divided once in double: bit for bit brFullAuc on
+ *   the same scores (while P N < 2^53).  NaN for P == 0 or N == 0.  A NaN score gets no credit on either side.  dump_scores
+ *   (optional, n_users x n_items): every pair's score (tests).
+ *   Limits: those of brDotCatalogTopK (1 <= dim <= 128, 1 <= n_items < 2^31, ld_q, ld_c >= dim); BR_ERR_ARG / BR_ERR_WORKSPACE
+ *   before any launch.  ws: brDotCatalogAucWorkspaceBytes(n_users, n_items, truth_off[n_users]) bytes (per-split partials and the
+ *   sorted positive scores); -1 for sizes outside the limits.  The truth entries the workspace cannot hold (and any past 2^31 - 1)
+ *   are never written: their users get NaN.  The user's positives are sorted by counting rank, O(P^2) compares per user. */
+int64_t brDotCatalogAucWorkspaceBytes(int64_t n_users, int64_t n_items, int64_t n_truth);
+int brDotCatalogAuc(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                    const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, void* ws, int64_t ws_bytes,
+                    brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the

@@ -1,0 +1,325 @@
+"""-m gpu: the fused dot-product catalogue AUC (csrc/auc_dot.hip, ops.dot_catalog_auc, BPREngine.full_auc and the sharded engine's,
+BPRModel.full_auc(method="fused")) against brFullAuc on the same scores (bit for bit), the float64 oracle, ties, non-finite scores,
+strides, plan independence, scale and memory."""
+import os
+import socket
+import sys
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _m(name):
+    return import_module("binary-recommendation_amd." + name)
+
+
+def _truth(sizes, I, dev, seed=0):
+    """ops.truth_csr with sizes[u] distinct random positions per user"""
+    rng = np.random.default_rng(seed)
+    rows = np.repeat(np.arange(len(sizes)), sizes)
+    cols = np.concatenate([rng.choice(I, int(p), replace=False) for p in sizes] + [np.zeros(0, np.int64)])
+    return _m("ops").truth_csr(len(sizes), rows, cols, dev)
+
+
+def _equal(a, b):
+    """bit for bit, NaN in the same places"""
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(a[~torch.isnan(a)], b[~torch.isnan(b)])
+
+
+def _auc64(S, off, idx):
+    """float64 Mann-Whitney AUC per user (ties one half) of the score rows S (torch float64, any device): oracle.roc_auc's rule"""
+    off, idx = off.cpu().numpy(), idx.cpu().numpy()
+    out = []
+    for u in range(S.shape[0]):
+        t = torch.as_tensor(idx[off[u]:off[u + 1]].astype(np.int64), device=S.device)
+        mask = torch.zeros(S.shape[1], dtype=torch.bool, device=S.device)
+        mask[t] = True
+        pos, neg = S[u][mask], S[u][~mask]
+        if len(pos) == 0 or len(neg) == 0:
+            out.append(float("nan")); continue
+        neg = torch.sort(neg).values
+        below = torch.searchsorted(neg, pos, right=False).sum().item()
+        le = torch.searchsorted(neg, pos, right=True).sum().item()
+        out.append((below + 0.5 * (le - below)) / (len(pos) * len(neg)))
+    return np.array(out)
+
+
+@pytest.mark.parametrize("dim", [1, 16, 33, 64, 128])
+def test_bit_exact_against_full_auc_of_the_dump(dev, dim):
+    """the fused AUC equals brFullAuc of the dumped scores bit for bit; the positives' scores of the prepass are the dump's (were
+    any of them different, a positive would be counted against a different value and the equality would break)"""
+    ops = _m("ops")
+    U, I = 300, 5000
+    rng = np.random.default_rng(dim)
+    g = torch.Generator(device="cpu").manual_seed(dim)
+    Q = torch.randn(U, dim, generator=g).to(dev)
+    C = torch.randn(I, dim, generator=g).to(dev)
+    mixed = rng.choice([0, 1, 2, 7, 200, 2500, I - 1, I], U)
+    small = rng.choice([0, 1, 2, 7], U)                                # every wave's lists fit in LDS
+    for sizes in (mixed, small):
+        off, idx = _truth(sizes, I, dev, seed=dim)
+        auc, dump = ops.dot_catalog_auc(Q, C, off, idx, dump_scores=True)
+        ref = ops.full_auc(dump, off, idx)
+        assert _equal(auc, ref)
+        assert torch.isnan(auc[torch.from_numpy((sizes == 0) | (sizes == I)).to(dev)]).all()
+        assert not torch.isnan(auc[torch.from_numpy((sizes > 0) & (sizes < I)).to(dev)]).any()
+        assert _equal(auc, ops.dot_catalog_auc(Q, C, off, idx))        # the dump changes nothing
+    S = Q.double() @ C.double().T
+    np.testing.assert_allclose(auc.double().cpu().numpy(), _auc64(S, off, idx), atol=1e-5)
+
+
+def test_ties(dev):
+    """integer rows: exact scores with many ties, positive against negative included, and duplicate item rows"""
+    ops = _m("ops")
+    O = import_module("oracle.binrec_oracle")
+    U, I, dim = 200, 3000, 8
+    g = torch.Generator(device="cpu").manual_seed(3)
+    Q = torch.randint(-2, 3, (U, dim), generator=g).float()
+    C = torch.randint(-2, 3, (I, dim), generator=g).float()
+    C[1000:2000] = C[:1000]                                            # duplicate rows
+    rng = np.random.default_rng(3)
+    sizes = rng.choice([0, 1, 3, 50, 700, I], U)
+    off, idx = _truth(sizes, I, dev, seed=3)
+    Qd, Cd = Q.to(dev), C.to(dev)
+    auc = ops.dot_catalog_auc(Qd, Cd, off, idx)
+    assert _equal(auc, ops.full_auc(ops.score_matrix(Qd, Cd), off, idx))
+    S = (Q.double() @ C.double().T).numpy()
+    o, x = off.cpu().numpy(), idx.cpu().numpy()
+    items = list(range(I))
+    for u in range(U):
+        t = x[o[u]:o[u + 1]]
+        grnd = np.zeros(I, np.int32); grnd[t] = 1
+        want = O.roc_auc(grnd, S[u])
+        got = float(auc[u])
+        assert (np.isnan(want) and np.isnan(got)) or np.float32(want) == np.float32(got), (u, want, got)
+    gt = [(u, [int(p) for p in x[o[u]:o[u + 1]]]) for u in range(U)]
+    mean, per = O.full_auc(S, gt, items)
+    has = sizes > 0
+    assert per == pytest.approx([float(a) for a in auc.cpu().numpy()[has]], abs=1e-7, nan_ok=True)
+
+
+def test_non_finite_scores(dev):
+    ops = _m("ops")
+    U, I, dim = 40, 700, 16
+    g = torch.Generator(device="cpu").manual_seed(4)
+    Q = torch.rand(U, dim, generator=g) + 0.1                          # positive rows: inf features give +-inf scores
+    C = torch.randn(I, dim, generator=g)
+    Q[5] = float("nan")
+    C[10, 3] = float("inf"); C[11, 0] = float("-inf"); C[12:20, 7] = float("inf")
+    C[30, 1] = float("inf"); C[30, 2] = float("-inf")                  # inf - inf: NaN for every user
+    sizes = np.full(U, 30); sizes[7] = 0; sizes[8] = I
+    rows = np.repeat(np.arange(U), sizes)
+    rng = np.random.default_rng(4)
+    cols = np.concatenate([np.r_[[10, 11, 12, 30], rng.choice(np.arange(40, I), int(p) - 4, replace=False)] if 4 < p < I
+                           else np.arange(int(p)) for p in sizes])
+    off, idx = ops.truth_csr(U, rows, cols, dev)
+    auc, dump = ops.dot_catalog_auc(Q.to(dev), C.to(dev), off, idx, dump_scores=True)
+    assert torch.isnan(dump[5]).all() and torch.isinf(dump[torch.arange(U) != 5][:, 10]).all() and torch.isnan(dump[:, 30]).all()
+    assert _equal(auc, ops.full_auc(dump, off, idx))
+    assert float(auc[5]) == 0.0                                        # NaN user: no pair counts
+
+
+def test_strides_and_alignment(dev):
+    """a column slice of a wider table (16-B aligned rows and not: the scalar-load path) gives the contiguous result"""
+    ops = _m("ops")
+    g = torch.Generator(device="cpu").manual_seed(1)
+    rng = np.random.default_rng(1)
+    for dim, ld, o in ((64, 72, 0), (64, 72, 1), (64, 67, 0), (33, 40, 0), (10, 11, 1)):
+        Qw = torch.randn(300, ld, generator=g).to(dev)
+        Cw = torch.randn(1500, ld, generator=g).to(dev)
+        Q, C = Qw[:, o:dim + o], Cw[:, o:dim + o]
+        assert Q.stride(0) == ld and C.stride(0) == ld
+        off, idx = _truth(rng.integers(0, 60, 300), 1500, dev, seed=dim + ld)
+        a = ops.dot_catalog_auc(Q, C, off, idx, dump_scores=True)
+        b = ops.dot_catalog_auc(Q.contiguous(), C.contiguous(), off, idx, dump_scores=True)
+        assert _equal(a[0], b[0]) and torch.equal(a[1], b[1]), (dim, ld, o)
+        assert _equal(a[0], ops.full_auc(a[1], off, idx))
+
+
+def test_plan_independence(dev):
+    """a user's AUC is the same alone, among 65 536 users, and with the users in another order"""
+    ops = _m("ops")
+    U, I = 65536, 20000
+    g = torch.Generator(device=dev).manual_seed(5)
+    Q = torch.empty(U, 64, device=dev).uniform_(-0.05, 0.05, generator=g)
+    C = torch.empty(I, 64, device=dev).uniform_(-0.05, 0.05, generator=g)
+    rng = np.random.default_rng(5)
+    sizes = rng.integers(0, 40, U)
+    off, idx = _truth(sizes, I, dev, seed=5)
+    full = ops.dot_catalog_auc(Q, C, off, idx)
+    o, x = off.cpu().numpy(), idx.cpu().numpy()
+    for u in (0, 1, 4097, U - 1):
+        t = torch.from_numpy(x[o[u]:o[u + 1]]).to(dev)
+        one = ops.dot_catalog_auc(Q[u:u + 1], C, torch.tensor([0, len(t)], dtype=torch.int64, device=dev), t)
+        assert _equal(one, full[u:u + 1]), u
+    perm = rng.permutation(U)
+    offp, idxp = ops.truth_csr(U, np.repeat(np.arange(U), sizes[perm]),
+                               np.concatenate([x[o[u]:o[u + 1]] for u in perm]), dev)
+    shuffled = ops.dot_catalog_auc(Q[torch.from_numpy(perm).to(dev)].contiguous(), C, offp, idxp)
+    assert _equal(shuffled, full[torch.from_numpy(perm).to(dev)])
+
+
+def test_scale_against_float64(dev):
+    ops = _m("ops")
+    U, I, dim, P = 65536, 100000, 64, 20
+    g = torch.Generator(device=dev).manual_seed(6)
+    Q = torch.empty(U, dim, device=dev).uniform_(-0.05, 0.05, generator=g)
+    C = torch.empty(I, dim, device=dev).uniform_(-0.05, 0.05, generator=g)
+    off, idx = _truth(np.full(U, P), I, dev, seed=6)
+    auc = ops.dot_catalog_auc(Q, C, off, idx)
+    assert not torch.isnan(auc).any()
+    sample = np.random.default_rng(6).choice(U, 256, replace=False)
+    o, x = off.cpu().numpy(), idx.cpu().numpy()
+    so = np.r_[0, np.cumsum([o[u + 1] - o[u] for u in sample])]
+    sx = np.concatenate([x[o[u]:o[u + 1]] for u in sample])
+    S = Q[torch.from_numpy(sample).to(dev)].double() @ C.double().T
+    want = _auc64(S, torch.from_numpy(so), torch.from_numpy(sx))
+    np.testing.assert_allclose(auc[torch.from_numpy(sample).to(dev)].double().cpu().numpy(), want, rtol=0, atol=1e-6)
+
+
+def test_bpr_full_auc_memory(dev):
+    bpr = _m("bpr")
+    U, I, dim = 65536, 100000, 64
+    eng = bpr.BPREngine(U, I, dim, dev, max_batch=1024)
+    users = torch.arange(U, dtype=torch.int32, device=dev)
+    truth = _truth(np.full(U, 20), I, dev, seed=7)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    auc = eng.full_auc(users, truth)
+    torch.cuda.synchronize()
+    eng.check_ids()
+    rise = torch.cuda.max_memory_allocated(dev) - before
+    assert rise < U * I * 4 / 8, rise
+    assert auc.shape == (U,) and not torch.isnan(auc).any()
+
+
+def _trained(dev, impl, U=300, I=500, dim=32):
+    bpr = _m("bpr")
+    eng = bpr.BPREngine(U, I, dim, dev, max_batch=256, dense_impl=impl, init_seed=5, replay="exact")
+    rng = np.random.default_rng(3)
+    td = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev)
+    for _ in range(3):
+        eng.train_step(td(rng.integers(0, U, 256)), td(rng.integers(0, I, 256)), td(rng.integers(0, I, 256)))
+    return eng
+
+
+def test_bpr_engine_full_auc(dev):
+    ops = _m("ops")
+    eng = _trained(dev, "deferred")
+    users = torch.arange(0, 300, 3, dtype=torch.int32, device=dev)
+    truth = _truth(np.random.default_rng(8).integers(0, 30, 100), 500, dev, seed=8)
+    a = eng.full_auc(users, truth)                                     # no explicit flush: full_auc flushes
+    want = ops.dot_catalog_auc(eng.user[users.long()].contiguous(), eng.item, *truth)
+    assert _equal(a, want)
+    items = torch.arange(500, dtype=torch.int32, device=dev)
+    assert _equal(a, eng.full_auc(users.long(), truth, items=items.long()))
+    sub = torch.tensor([499, 3, 250, 7], dtype=torch.int64, device=dev)
+    st = ops.truth_csr(100, np.arange(100), np.arange(100) % 4, dev)
+    s, dump = eng.full_auc(users, st, items=sub, dump_scores=True)
+    assert _equal(s, ops.full_auc(dump, *st))
+    eng.check_ids()
+    eng.full_auc(torch.tensor([0, 300], dtype=torch.int32, device=dev), _truth([1, 1], 500, dev))
+    with pytest.raises(IndexError):
+        eng.check_ids()
+    eng.full_auc(users[:2], _truth([1, 1], 2, dev), items=torch.tensor([1, -1], dtype=torch.int32, device=dev))
+    with pytest.raises(IndexError):
+        eng.check_ids()
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _sharded_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import torch.distributed as dist
+    try:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        par = import_module("binary-recommendation_amd.parallel")
+        bpr = import_module("binary-recommendation_amd.bpr")
+        ops = import_module("binary-recommendation_amd.ops")
+        dev = torch.device("cuda:0")
+        ctx = par.DistCtx()
+        U, I, F = 211, 389, 32
+        rng = np.random.default_rng(21)
+        ut = rng.uniform(-.05, .05, (U, F)).astype(np.float32); it = rng.uniform(-.05, .05, (I, F)).astype(np.float32)
+        Eng = par.make_sharded_bpr(bpr.BPREngine)
+        eng = Eng(U, I, F, dev, 64, ctx, full_tables={"user": torch.from_numpy(ut), "item": torch.from_numpy(it)})
+        single = bpr.BPREngine(U, I, F, dev, 64)
+        single.user.copy_(torch.from_numpy(ut)); single.item.copy_(torch.from_numpy(it))
+        mine = torch.from_numpy(rng.permutation(U)[rank::world][:50].astype(np.int32)).to(dev)   # each rank its own users
+        sizes = np.random.default_rng(rank).integers(0, 40, 50)
+        truth = ops.truth_csr(50, np.repeat(np.arange(50), sizes),
+                              np.concatenate([np.random.default_rng(n).choice(I, p, replace=False) for n, p in enumerate(sizes)]), dev)
+        a, b = eng.full_auc(mine, truth), single.full_auc(mine, truth)
+        assert torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(a[~torch.isnan(a)], b[~torch.isnan(b)])
+        items = torch.arange(100, 300, dtype=torch.int32, device=dev)
+        st = ops.truth_csr(50, np.arange(50), np.arange(50) * 3, dev)
+        a, b = eng.full_auc(mine, st, items=items), single.full_auc(mine, st, items=items)
+        assert torch.equal(a, b)
+        eng.check_ids()
+        q.put((rank, "ok"))
+    except Exception:  # noqa: BLE001
+        import traceback
+        q.put((rank, "FAIL: " + traceback.format_exc()[-1800:]))
+    finally:
+        try:
+            dist.destroy_process_group()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def test_sharded_bpr_full_auc_two_ranks(dev):
+    import torch.multiprocessing as mp
+    world, port = 2, _free_port()
+    ctxm = mp.get_context("spawn")
+    q = ctxm.Queue()
+    procs = [ctxm.Process(target=_sharded_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=300) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+    for r in res:
+        assert r[1] == "ok", f"rank {r[0]}: {r[1]}"
+
+
+def test_bpr_model_surface(dev, tmp_path, monkeypatch):
+    import pandas as pd
+    models = _m("models")
+    monkeypatch.chdir(tmp_path)
+    rng = np.random.default_rng(0)
+    U, I, n = 120, 80, 4000
+    u = rng.integers(0, U, n); i = (u * 7 + rng.integers(0, 5, n)) % I
+    pd.DataFrame({"CUSTOMER_ID": u, "PRODUCT_ID": i, "MATERIAL": i, "QUANTITY": 1}).to_csv(tmp_path / "sdata.csv", index=False)
+    m = models.BPRModel(device="cuda:0", max_batch=4096)
+    m.epochs = 2
+    m.train(str(tmp_path / "sdata.csv"), 50000, {})
+    items = [int(x) for x in m.productIds]
+    cust = [int(c) for c in m.getPredictableUsers()[:30]]
+    gt = [(c, [int(x) for x in m.testDf[m.testDf.CUSTOMER_ID == c].PRODUCT_ID.tolist() if int(x) in set(items)]) for c in cust]
+    gt.append((cust[0], []))                                           # a user without positives: left out of the mean
+    got = m.full_auc(gt, items, method="fused")
+    assert got == pytest.approx(m.full_auc(gt, items, method="matrix"), abs=1e-6)
+    assert got == pytest.approx(m.full_auc(gt, items), abs=1e-6)      # the default is the matrix path
+    e = m.model
+    Qu = e.user[torch.tensor([c for c, _ in gt], device=e.device)].double()
+    S = (Qu @ e.item[torch.tensor(items, device=e.device)].double().T).cpu().numpy()
+    O = import_module("oracle.binrec_oracle")
+    assert got == pytest.approx(O.full_auc(S, gt, items)[0], abs=1e-6)
+    with pytest.raises(ValueError):
+        m.full_auc([(cust[0], [10 ** 9])], items, method="fused")      # a true item outside `items`
+    with pytest.raises(ValueError):
+        m.full_auc(gt, items, method="pairs")
