@@ -211,23 +211,28 @@ class BPREngine(RowAdam):
         launch scores, masks and selects (ops.dot_catalog_topk, csrc/recommend_dot.hip).  items: the candidate ids (None: the item
         table in place); exclude: (off, idx) CSR over `users` of candidate POSITIONS never to return (topk_metrics.seen_csr).
         -> (scores (U, k) float32, index (U, k) int32 positions into `items`) on the device, best first, ties to the lower position;
-        slots past the remaining candidates are (-inf, -1).  Ids outside the tables set self.err (check_ids raises)."""
-        self.flush()                         # deferred-Adam rows lag until then
-        users, items = self._recommend_ids(users, items)
-        q = ops.gather_rows([self._user], [users], err_flag=self.err)[0]
-        c = self._item if items is None else ops.gather_rows([self._item], [items], err_flag=self.err)[0]
+        slots past the remaining candidates are (-inf, -1).  Ids outside the tables set self.err (check_ids raises).  On the row-sharded
+        engine (parallel.py) this is a collective: every rank calls it and gets the lists of ITS users."""
+        q, c = self._catalog_rows(users, items)
         return ops.dot_catalog_topk(q, c, k, exclude=exclude, dump_scores=dump_scores)
 
     def full_auc(self, users, truth, items=None, dump_scores=False):
         """Per-user full AUC (src/models/bpr.py:230-254) of the dot scores predict_scores returns, without the U x I matrix: the fused
         launches of ops.dot_catalog_auc (csrc/auc_dot.hip).  truth: (off, idx) CSR over `users` of candidate POSITIONS, ascending
         (ops.truth_csr); items: the candidate ids (None: the item table in place).  -> float32 (U,) on the device, NaN for a user
-        without positives or without negatives.  Ids outside the tables set self.err (check_ids raises)."""
+        without positives or without negatives.  Ids outside the tables set self.err (check_ids raises).  On the row-sharded engine
+        (parallel.py) this is a collective: every rank calls it and gets the AUCs of ITS users."""
+        q, c = self._catalog_rows(users, items)
+        return ops.dot_catalog_auc(q, c, truth[0], truth[1], dump_scores=dump_scores)
+
+    def _catalog_rows(self, users, items):
+        """-> (the rows of `users`, the rows of `items` or the item table in place) that recommend / full_auc score (row-sharded
+        engines override this: parallel.py)"""
         self.flush()                         # deferred-Adam rows lag until then
         users, items = self._recommend_ids(users, items)
         q = ops.gather_rows([self._user], [users], err_flag=self.err)[0]
         c = self._item if items is None else ops.gather_rows([self._item], [items], err_flag=self.err)[0]
-        return ops.dot_catalog_auc(q, c, truth[0], truth[1], dump_scores=dump_scores)
+        return q, c
 
     def _recommend_ids(self, users, items):
         users = torch.as_tensor(users, device=self.device)

@@ -7,7 +7,7 @@
 //   - auc_pos_kernel: one wave per user scores the user's truth entries on the same v_mfma_f32_16x16x4_f32, with the same feature
 //     order and zero padding, as the catalogue pass (so a positive's score is bit for bit the one the catalogue pass sees), then
 //     sorts them ascending by counting rank (O(P^2) compares per user), NaN scores dropped; the count P' of the rest goes beside;
-//   - dot_auc_kernel: the tile loop of dot_topk_kernel (recommend_dot.hip): 4 waves, 32 users per wave with their A fragments in
+//   - dot_auc_kernel: a copy of the tile loop of dot_topk_kernel (recommend_dot.hip; kept the same by hand, dot_tile.h): 4 waves, 32 users per wave with their A fragments in
 //     registers, 64-item steps streamed through LDS with the next step in flight.  Each lane takes its 32 scores per step: a
 //     positive (the truth CSR walked with a cursor and a 64-bit window mask, as the exclusion there) or a NaN score adds 0, a
 //     score below the user's smallest positive 2P', above the largest 0, and one inside [min, max] 2 #{positives > s} +
@@ -19,26 +19,17 @@
 #include <math.h>
 
 #include "common.h"
+#include "dot_tile.h"
 
 namespace br {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int64_t kAucTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
 constexpr int kAucRT = 2, kAucCT = 4;     // 32 users per wave, 64 items per step
 constexpr int kAucUW = 16 * kAucRT, kAucNT = 16 * kAucCT;
 constexpr int kAucLdsCap = 2048;          // sorted positives of a wave's 32 users kept in LDS up to this many (8 KB per wave)
 
 void auc_plan(int64_t n_users, int64_t n_items, int64_t* splits, int64_t* steps_per_split) {
-  const int64_t n_steps = ceil_div(n_items, kAucNT), wgs = ceil_div(n_users > 0 ? n_users : 1, 4 * kAucUW);
-  int64_t s = ceil_div(kAucTargetWgs, wgs);
-  if (s > n_steps) s = n_steps;
-  if (s > 65535) s = 65535;
-  if (s < 1) s = 1;
-  const int64_t sps = ceil_div(n_steps, s);
-  *steps_per_split = sps;
-  *splits = ceil_div(n_steps, sps);
+  split_plan(ceil_div(n_items, kAucNT), n_users, 4 * kAucUW, splits, steps_per_split);
 }
 
 int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
@@ -49,11 +40,6 @@ int64_t auc_fixed_bytes(int64_t n_users, int64_t n_items) {
   int64_t S, sps;
   auc_plan(n_users, n_items, &S, &sps);
   return align256(n_users * S * 8) + align256(n_users * 4);
-}
-
-__device__ __forceinline__ void wave_lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 // one wave per user: score its truth entries, sort them ascending (NaN dropped) into sorted[off[u] ...], P' into pcnt[u] (-1: the
@@ -396,10 +382,7 @@ extern "C" int brDotCatalogAuc(const float* Q, int64_t ld_q, int64_t n_users, co
                                const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, void* ws,
                                int64_t ws_bytes, brStream stream) {
   BR_CHECK_ARG(Q && C && truth_off && truth_idx && out_auc && ws, "brDotCatalogAuc: null pointer");
-  BR_CHECK_ARG(dim >= 1 && dim <= 128, "brDotCatalogAuc: dim = %d outside [1, 128]", dim);
-  BR_CHECK_ARG(n_users >= 0 && n_items >= 1 && n_items < ((int64_t)1 << 31), "brDotCatalogAuc: bad sizes (1 <= n_items < 2^31)");
-  BR_CHECK_ARG(ld_q >= dim && ld_c >= dim, "brDotCatalogAuc: ld_q, ld_c >= dim (got %lld, %lld, dim %d)", (long long)ld_q,
-               (long long)ld_c, dim);
+  if (const int rc = dot_check_args("brDotCatalogAuc", ld_q, n_users, ld_c, n_items, dim)) return rc;
   const int64_t fixed = auc_fixed_bytes(n_users, n_items), least = brDotCatalogAucWorkspaceBytes(n_users, n_items, 0);
   if (ws_bytes < least) {
     br::set_error("brDotCatalogAuc: workspace %lld bytes < %lld", (long long)ws_bytes, (long long)least);
@@ -415,16 +398,12 @@ extern "C" int brDotCatalogAuc(const float* Q, int64_t ld_q, int64_t n_users, co
   float* sorted = (float*)((char*)ws + fixed + half);
   int64_t cap = half / 4 - 1;                                        // truth entries [0, cap) fit; a user past them gets NaN
   if (cap > INT32_MAX) cap = INT32_MAX;
-  const int vec = dim % 4 == 0 && ld_c % 4 == 0 && ((uintptr_t)C & 15) == 0;
+  const int vec = rows_vec4(C, ld_c, dim);
   hipStream_t st = (hipStream_t)stream;
-  const int kb = (dim + 3) / 4;
-#define BR_AUC_ARGS S, sps, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, truth_off, truth_idx, raw, sorted, pcnt, cap, part, dump_scores
-  if (kb <= 4) launch_auc<4>(BR_AUC_ARGS);
-  else if (kb <= 8) launch_auc<8>(BR_AUC_ARGS);
-  else if (kb <= 16) launch_auc<16>(BR_AUC_ARGS);
-  else if (kb <= 24) launch_auc<24>(BR_AUC_ARGS);
-  else launch_auc<32>(BR_AUC_ARGS);
-#undef BR_AUC_ARGS
+  dispatch_kb(dim, [&](auto kb) {
+    launch_auc<decltype(kb)::value>(S, sps, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, truth_off, truth_idx, raw, sorted, pcnt, cap, part,
+                                    dump_scores);
+  });
   BR_CHECK_LAUNCH("brDotCatalogAuc");
   auc_finalize_kernel<<<(unsigned)ceil_div(n_users, 256), 256, 0, st>>>(part, S, truth_off, pcnt, n_users, n_items, out_auc);
   BR_CHECK_LAUNCH("brDotCatalogAuc finalize");

@@ -1,0 +1,54 @@
+// What the dot-product catalogue kernels (recommend_dot.hip: top-k, auc_dot.hip: AUC) share outside their tile loops: the split
+// plan (recommend.hip's too), wave_lds_order and what the two entry points check and choose alike.  The tile loop itself is still
+// written out in both kernels and kept the same by hand: see DESIGN.md 4e "One copy of the tile loop".
+#pragma once
+#include <type_traits>
+
+#include "common.h"
+
+namespace br {
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int64_t kSplitTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
+
+// `units` steps of the item axis, users_per_wg users per workgroup -> the number of splits (grid.y, <= 65535) and the steps each takes
+void split_plan(int64_t units, int64_t n_users, int64_t users_per_wg, int64_t* splits, int64_t* units_per_split) {
+  int64_t s = ceil_div(kSplitTargetWgs, ceil_div(n_users > 0 ? n_users : 1, users_per_wg));
+  if (s > units) s = units;
+  if (s > 65535) s = 65535;
+  if (s < 1) s = 1;
+  const int64_t ups = ceil_div(units, s);
+  *units_per_split = ups;
+  *splits = ceil_div(units, ups);
+}
+
+// compiler barrier between one lane's LDS stores and another lane's loads of the same words (a wave's LDS accesses execute in order)
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// float4 item loads: every row of C 16-B aligned and whole chunks only
+int rows_vec4(const float* C, int64_t ld_c, int dim) { return dim % 4 == 0 && ld_c % 4 == 0 && ((uintptr_t)C & 15) == 0; }
+
+// f(std::integral_constant<int, KB>) for the instantiated feature width 4 KB >= dim
+template <typename F>
+void dispatch_kb(int dim, F&& f) {
+  const int kb = (dim + 3) / 4;
+  if (kb <= 4) f(std::integral_constant<int, 4>{}); else if (kb <= 8) f(std::integral_constant<int, 8>{});
+  else if (kb <= 16) f(std::integral_constant<int, 16>{}); else if (kb <= 24) f(std::integral_constant<int, 24>{});
+  else f(std::integral_constant<int, 32>{});
+}
+
+// the checks both entry points make on (Q, C); `name`: the entry point, for the message
+int dot_check_args(const char* name, int64_t ld_q, int64_t n_users, int64_t ld_c, int64_t n_items, int dim) {
+  BR_CHECK_ARG(dim >= 1 && dim <= 128, "%s: dim = %d outside [1, 128]", name, dim);
+  BR_CHECK_ARG(n_users >= 0 && n_items >= 1 && n_items < ((int64_t)1 << 31), "%s: bad sizes (1 <= n_items < 2^31)", name);
+  BR_CHECK_ARG(ld_q >= dim && ld_c >= dim, "%s: ld_q, ld_c >= dim (got %lld, %lld, dim %d)", name, (long long)ld_q, (long long)ld_c, dim);
+  return BR_OK;
+}
+
+}  // namespace
+}  // namespace br

@@ -18,12 +18,11 @@
 #include <math.h>
 
 #include "common.h"
+#include "dot_tile.h"
 #include "topk_list.h"
 
 namespace br {
 namespace {
-
-constexpr int64_t kRecTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
 
 // padded width of the second layer (the per-lane accumulator count): one instantiation per width
 int tower_width(int n2) {
@@ -50,14 +49,7 @@ TowerLayout tower_layout(int n1, int n2, int n3) {
 }
 
 void catalog_plan(int64_t n_users, int64_t n_items, int64_t* splits, int64_t* chunks_per_split) {
-  const int64_t n_chunks = ceil_div(n_items, 64), wgs = ceil_div(n_users > 0 ? n_users : 1, kRecWaves);
-  int64_t s = ceil_div(kRecTargetWgs, wgs);
-  if (s > n_chunks) s = n_chunks;
-  if (s > 65535) s = 65535;
-  if (s < 1) s = 1;
-  const int64_t cps = ceil_div(n_chunks, s);
-  *chunks_per_split = cps;
-  *splits = ceil_div(n_chunks, cps);
+  split_plan(ceil_div(n_items, 64), n_users, kRecWaves, splits, chunks_per_split);   // (dot_tile.h: the one plan of the catalogue kernels)
 }
 
 template <typename IdT>

@@ -18,14 +18,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "dot_tile.h"
 #include "topk_list.h"
 
 namespace br {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int64_t kDotTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
 constexpr int kDotQueue = 128;            // candidate queue entries per wave (flushed before it can overflow)
 
 // list capacity, row tiles per wave and column tiles per step by k: the per-user lists of a workgroup live in LDS
@@ -42,14 +40,7 @@ DotCfg dot_cfg(int k) {
 
 void dot_plan(int64_t n_users, int64_t n_items, int k, int64_t* splits, int64_t* steps_per_split) {
   const DotCfg c = dot_cfg(k);
-  const int64_t n_steps = ceil_div(n_items, 16 * c.ct), wgs = ceil_div(n_users > 0 ? n_users : 1, 64 * c.rt);
-  int64_t s = ceil_div(kDotTargetWgs, wgs);
-  if (s > n_steps) s = n_steps;
-  if (s > 65535) s = 65535;
-  if (s < 1) s = 1;
-  const int64_t sps = ceil_div(n_steps, s);
-  *steps_per_split = sps;
-  *splits = ceil_div(n_steps, sps);
+  split_plan(ceil_div(n_items, 16 * c.ct), n_users, 64 * c.rt, splits, steps_per_split);
 }
 
 // Insert (cs, cp) (wave-uniform) into the k-entry list S/P in LDS (entry e at S[e]; lane holds entries lane + 64 r) unless it does
@@ -93,12 +84,6 @@ __device__ void list_insert(float* S, int32_t* P, int k, int lane, float cs, int
   for (int r = 1; r < SLOTS; ++r) if (r == slot) { ls = s[r]; lp = p[r]; }   // (no runtime register indexing)
   ts = __shfl(ls, last & 63, 64);
   tp = __shfl(lp, last & 63, 64);
-}
-
-// compiler barrier between one lane's LDS stores and another lane's loads of the same words (a wave's LDS accesses execute in order)
-__device__ __forceinline__ void wave_lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 template <int KB, int KMAX, int RT, int CT>
@@ -326,10 +311,7 @@ extern "C" int brDotCatalogTopK(const float* Q, int64_t ld_q, int64_t n_users, c
                                 float* dump_scores, void* ws, int64_t ws_bytes, brStream stream) {
   BR_CHECK_ARG(Q && C && out_scores && out_index && ws, "brDotCatalogTopK: null pointer");
   BR_CHECK_ARG(k >= 1 && k <= kRecMaxK, "brDotCatalogTopK: k = %d outside [1, %d]", k, kRecMaxK);
-  BR_CHECK_ARG(dim >= 1 && dim <= 128, "brDotCatalogTopK: dim = %d outside [1, 128]", dim);
-  BR_CHECK_ARG(n_users >= 0 && n_items >= 1 && n_items < ((int64_t)1 << 31), "brDotCatalogTopK: bad sizes (1 <= n_items < 2^31)");
-  BR_CHECK_ARG(ld_q >= dim && ld_c >= dim, "brDotCatalogTopK: ld_q, ld_c >= dim (got %lld, %lld, dim %d)", (long long)ld_q,
-               (long long)ld_c, dim);
+  if (const int rc = dot_check_args("brDotCatalogTopK", ld_q, n_users, ld_c, n_items, dim)) return rc;
   BR_CHECK_ARG((excl_off == nullptr) == (excl_idx == nullptr), "brDotCatalogTopK: exclusion needs both excl_off and excl_idx");
   int64_t S, sps;
   dot_plan(n_users, n_items, k, &S, &sps);
@@ -343,14 +325,12 @@ extern "C" int brDotCatalogTopK(const float* Q, int64_t ld_q, int64_t n_users, c
   int32_t* pp = (int32_t*)((char*)ws + pb);
   const DotCfg c = dot_cfg(k);
   const dim3 grid((unsigned)ceil_div(n_users, 64 * c.rt), (unsigned)S);
-  const int vec = dim % 4 == 0 && ld_c % 4 == 0 && ((uintptr_t)C & 15) == 0;
+  const int vec = rows_vec4(C, ld_c, dim);
   hipStream_t st = (hipStream_t)stream;
-  const int kb = (dim + 3) / 4;
-  if (kb <= 4) launch_dot_topk<4>(c.kmax, grid, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, excl_off, excl_idx, k, sps, S, ps, pp, dump_scores);
-  else if (kb <= 8) launch_dot_topk<8>(c.kmax, grid, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, excl_off, excl_idx, k, sps, S, ps, pp, dump_scores);
-  else if (kb <= 16) launch_dot_topk<16>(c.kmax, grid, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, excl_off, excl_idx, k, sps, S, ps, pp, dump_scores);
-  else if (kb <= 24) launch_dot_topk<24>(c.kmax, grid, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, excl_off, excl_idx, k, sps, S, ps, pp, dump_scores);
-  else launch_dot_topk<32>(c.kmax, grid, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, excl_off, excl_idx, k, sps, S, ps, pp, dump_scores);
+  dispatch_kb(dim, [&](auto kb) {
+    launch_dot_topk<decltype(kb)::value>(c.kmax, grid, st, Q, ld_q, n_users, C, ld_c, n_items, dim, vec, excl_off, excl_idx, k, sps, S, ps, pp,
+                                         dump_scores);
+  });
   BR_CHECK_LAUNCH("brDotCatalogTopK");
   catalog_merge_kernel<<<(unsigned)ceil_div(n_users, kRecWaves), 256, 0, st>>>(ps, pp, n_users, S, k, out_scores, out_index);
   BR_CHECK_LAUNCH("brDotCatalogTopK merge");

@@ -679,36 +679,39 @@ def _rows_f32(t, name: str):
     return t
 
 
+def _dot_catalog_args(who: str, Q, C, k=None):
+    """the checks dot_catalog_topk / dot_catalog_auc (`who`) make on Q, C (and k) -> (U, I, dim, ld_q, ld_c, device)"""
+    for t, name in ((Q, "Q"), (C, "C")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{who}: {name} must be a 2-D tensor")
+    U, dim = Q.shape
+    I = C.shape[0]
+    if C.shape[1] != dim:
+        raise ValueError(f"{who}: Q has dim {dim}, C has {C.shape[1]}")
+    if not 1 <= dim <= 128:
+        raise ValueError(f"{who}: dim = {dim}: 1 <= dim <= 128")
+    if k is not None and not 1 <= int(k) <= 256:
+        raise ValueError(f"k = {k}: 1 <= k <= 256")
+    _rows_f32(Q, "Q"); _rows_f32(C, "C")
+    if Q.device != C.device:
+        raise ValueError(f"{who}: Q and C on different devices")
+    return U, I, dim, (Q.stride(0) if U > 1 else dim), (C.stride(0) if I > 1 else dim), Q.device
+
+
 def dot_catalog_topk(Q, C, k, exclude=None, dump_scores=False):
     """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim) -> (scores (U, k) float32, index (U, k) int32 positions
     into C) [, every pair's score (U, I)]: per user the k best Q[u] . C[i], best first, ties to the lower position, exclude positions
     (ops.truth_csr over the rows of Q) never returned, (-inf, -1) past the remaining candidates; the U x I matrix is not stored."""
-    for t, name in ((Q, "Q"), (C, "C")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise ValueError(f"dot_catalog_topk: {name} must be a 2-D tensor")
-    U, dim = Q.shape
-    I = C.shape[0]
-    if C.shape[1] != dim:
-        raise ValueError(f"dot_catalog_topk: Q has dim {dim}, C has {C.shape[1]}")
-    if not 1 <= dim <= 128:
-        raise ValueError(f"dot_catalog_topk: dim = {dim}: 1 <= dim <= 128")
-    if not 1 <= int(k) <= 256:
-        raise ValueError(f"k = {k}: 1 <= k <= 256")
-    _rows_f32(Q, "Q"); _rows_f32(C, "C")
-    if Q.device != C.device:
-        raise ValueError("dot_catalog_topk: Q and C on different devices")
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_topk", Q, C, k)
     lib = _lib.load()
     ws_bytes = int(lib.brDotCatalogTopKWorkspaceBytes(U, I, int(k)))
     if ws_bytes < 0:
         raise ValueError(f"dot_catalog_topk: bad sizes U={U} I={I} k={k}")
-    dev = Q.device
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
     os_ = torch.empty(U, k, dtype=torch.float32, device=dev)
     oi = torch.empty(U, k, dtype=torch.int32, device=dev)
     dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
     off, idx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
-    ld_q = Q.stride(0) if U > 1 else dim
-    ld_c = C.stride(0) if I > 1 else dim
     check(lib.brDotCatalogTopK(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(),
                                _p(dump), ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogTopK")
     return (os_, oi, dump) if dump_scores else (os_, oi)
@@ -719,30 +722,16 @@ def dot_catalog_auc(Q, C, truth_off, truth_idx, dump_scores=False):
     """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim), truth (ops.truth_csr over the rows of Q: ascending
     positions into C) -> per-user AUC float32 (U,) [, every pair's score (U, I)]: full_auc of the scores Q[u] . C[i], equal bit for
     bit to full_auc(score_matrix(Q, C), truth_off, truth_idx) on the same scores, NaN where undefined; the U x I matrix is not stored."""
-    for t, name in ((Q, "Q"), (C, "C")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise ValueError(f"dot_catalog_auc: {name} must be a 2-D tensor")
-    U, dim = Q.shape
-    I = C.shape[0]
-    if C.shape[1] != dim:
-        raise ValueError(f"dot_catalog_auc: Q has dim {dim}, C has {C.shape[1]}")
-    if not 1 <= dim <= 128:
-        raise ValueError(f"dot_catalog_auc: dim = {dim}: 1 <= dim <= 128")
-    _rows_f32(Q, "Q"); _rows_f32(C, "C")
-    if Q.device != C.device:
-        raise ValueError("dot_catalog_auc: Q and C on different devices")
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_auc", Q, C)
     n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
     off, idx = _csr((truth_off, truth_idx), U, "truth")
     lib = _lib.load()
     ws_bytes = int(lib.brDotCatalogAucWorkspaceBytes(U, I, n_truth))
     if ws_bytes < 0:
         raise ValueError(f"dot_catalog_auc: bad sizes U={U} I={I}")
-    dev = Q.device
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(U, dtype=torch.float32, device=dev)
     dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
-    ld_q = Q.stride(0) if U > 1 else dim
-    ld_c = C.stride(0) if I > 1 else dim
     check(lib.brDotCatalogAuc(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
                               ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogAuc")
     return (out, dump) if dump_scores else out

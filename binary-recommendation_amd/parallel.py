@@ -752,26 +752,17 @@ def make_sharded_bpr(base_cls):
             it = self._gather_global("item", item_ids)
             return ops.score_matrix(u, it)
 
-        def recommend(self, users, k, items=None, exclude=None, dump_scores=False):
-            """BPREngine.recommend on row-sharded tables: the user rows (and the candidate rows, every item when items is None) come
-            through the id -> owner exchange of predict_scores, then the fused top-k runs locally.  A collective: every rank calls it
-            and gets the lists of ITS users."""
+        def _catalog_rows(self, users, items):
+            """The rows BPREngine.recommend / full_auc score, on row-sharded tables: the user rows (and the candidate rows, every item
+            when items is None) come through the id -> owner exchange of predict_scores, then the fused launch runs locally.  So both
+            are collectives here: every rank calls them and gets the lists / AUCs of ITS users.  (No flush() of its own: _gather_global
+            reads the tables through the flushing properties when this rank serves rows.)"""
             users, items = self._recommend_ids(users, items)
             u = self._gather_global("user", users.to(self.id_dtype))
             if items is None:
                 items = torch.arange(self.num_items_global, device=self.device)
             it = self._gather_global("item", items.to(self.id_dtype))
-            return ops.dot_catalog_topk(u, it, k, exclude=exclude, dump_scores=dump_scores)
-
-        def full_auc(self, users, truth, items=None, dump_scores=False):
-            """BPREngine.full_auc on row-sharded tables: the rows come through the id -> owner exchange of recommend, then the fused AUC
-            runs locally.  A collective: every rank calls it and gets the AUCs of ITS users."""
-            users, items = self._recommend_ids(users, items)
-            u = self._gather_global("user", users.to(self.id_dtype))
-            if items is None:
-                items = torch.arange(self.num_items_global, device=self.device)
-            it = self._gather_global("item", items.to(self.id_dtype))
-            return ops.dot_catalog_auc(u, it, truth[0], truth[1], dump_scores=dump_scores)
+            return u, it
 
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 
