@@ -92,7 +92,7 @@ struct AdamPairCall {
 struct FinalArgs;
 int adam_rows_pair_keep(const AdamPairCall& c, const KeepArgs* keep, brStream stream, const FinalArgs* fin = nullptr, bool* fin_done = nullptr);
 
-// sparse_opt.hip: the deferred NeuMF lookup and both dedup indexes of the step on ONE stream (the chunk sorts ride in the lookup's grid)
+// row_index.hip: the deferred NeuMF lookup and both dedup indexes of the step on ONE stream (the chunk sorts ride in the lookup's grid)
 struct LookupArgs;
 struct IndexPairArgs {
   void* sorted_ids_a; int32_t* sorted_pos_a; void* ws_a; int64_t ws_a_bytes;

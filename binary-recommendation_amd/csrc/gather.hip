@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void gather_rows_deferred_wave_kernel(
 
 // two deferred tables of one geometry served by ONE launch (blockIdx.y): a row-sharded owner's user and item shard - each gather alone
 // is a chain of dependent round trips per row and leaves HBM half idle
-// (GatherDefJob / GatherDefJobs / gather_deferred_wave_row: lookup_wave.h - the fused gather + chunk-sort launch of sparse_opt.hip shares them)
+// (GatherDefJob / GatherDefJobs / gather_deferred_wave_row: lookup_wave.h - the fused gather + chunk-sort launch of row_index.hip shares them)
 template <typename IdT, int VEC>
 __global__ __launch_bounds__(256) void gather_rows_deferred_wave_pair_kernel(GatherDefJobs jobs, const StepStateDev* __restrict__ ss, AdamHp h,
                                                                               int64_t ld_out, int* err) {
@@ -438,19 +438,15 @@ extern "C" int brGatherRows(int n_tables, const float* const* tables, const int6
       a.outs[t] = outs[t0 + t];
       a.rows[t] = table_rows[t0 + t];
     }
-#define LAUNCH_G(IdT, NT) \
-  BR_DISPATCH_VEC(g.vec, (gather_rows_kernel<IdT, VEC, NT><<<grid, 256, 0, s>>>(a, dim, g.chunks, g.lpr_log2, batch, err_flag)))
-#define LAUNCH_G_ID(NT)                                   \
-  do {                                                    \
-    if (id_type == BR_IDS_I32) LAUNCH_G(int32_t, NT);     \
-    else LAUNCH_G(int64_t, NT);                           \
-  } while (0)
+#define LAUNCH_G(NT) \
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (gather_rows_kernel<IdT, VEC, NT><<<grid, 256, 0, s>>>(a, dim, g.chunks, g.lpr_log2, batch, err_flag))))
     switch (nt) {
-      case 1: LAUNCH_G_ID(1); break;
-      case 2: LAUNCH_G_ID(2); break;
-      case 3: LAUNCH_G_ID(3); break;
-      default: LAUNCH_G_ID(4); break;
+      case 1: LAUNCH_G(1); break;
+      case 2: LAUNCH_G(2); break;
+      case 3: LAUNCH_G(3); break;
+      default: LAUNCH_G(4); break;
     }
+#undef LAUNCH_G
     BR_CHECK_LAUNCH("brGatherRows");
   }
   return BR_OK;
@@ -496,20 +492,12 @@ extern "C" int brNeumfEmbedForwardStash(const float* user_mlp, const float* item
   BR_CHECK_ARG(ld_user >= dim && ld_item >= dim, "brNeumfEmbedForward: row strides < dim");
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brNeumfEmbedForward: bad id_type");
   if (batch == 0) return BR_OK;
-  const bool st4 = !stash_user || (ld_stash % 4 == 0 && ((reinterpret_cast<uintptr_t>(stash_user) | reinterpret_cast<uintptr_t>(stash_item)) & 15) == 0);
-  const bool st2 = !stash_user || (ld_stash % 2 == 0 && ((reinterpret_cast<uintptr_t>(stash_user) | reinterpret_cast<uintptr_t>(stash_item)) & 7) == 0);
-  const RowGeom g = row_geom_ld(dim, (ld_user % 4 == 0 && ld_item % 4 == 0 && st4) ? 4 : (ld_user % 2 == 0 && ld_item % 2 == 0 && st2) ? 2 : 1);
+  const RowGeom g = row_geom_ld(dim, vec_width({ld_user, ld_item, stash_user ? ld_stash : 0}, {stash_user, stash_item}));      // (the stashes: both or neither)
   const unsigned grid = grid_for_rows(batch, g.lpr_log2);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32) {
-    BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(
-                               user_mlp, item_mlp, user_mf, item_mf, ld_user, ld_item, user_rows, item_rows, (const int32_t*)users,
-                               (const int32_t*)items, dim, g.chunks, g.lpr_log2, batch, item_first, x0, dot, err_flag, stash_user, stash_item, ld_stash)));
-  } else {
-    BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(
-                               user_mlp, item_mlp, user_mf, item_mf, ld_user, ld_item, user_rows, item_rows, (const int64_t*)users,
-                               (const int64_t*)items, dim, g.chunks, g.lpr_log2, batch, item_first, x0, dot, err_flag, stash_user, stash_item, ld_stash)));
-  }
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_kernel<IdT, VEC><<<grid, 256, 0, s>>>(
+                                                     user_mlp, item_mlp, user_mf, item_mf, ld_user, ld_item, user_rows, item_rows, (const IdT*)users, (const IdT*)items, dim,
+                                                     g.chunks, g.lpr_log2, batch, item_first, x0, dot, err_flag, stash_user, stash_item, ld_stash))));
   BR_CHECK_LAUNCH("brNeumfEmbedForward");
   return BR_OK;
 }
@@ -525,34 +513,24 @@ extern "C" int brNeumfEmbedForwardDeferred(const float* user_tab, const float* u
   BR_CHECK_ARG(dim >= 1 && batch >= 0 && user_rows > 0 && item_rows > 0 && ld_stash >= dim, "brNeumfEmbedForwardDeferred: bad sizes");
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brNeumfEmbedForwardDeferred: bad id_type");
   if (batch == 0) return BR_OK;
-  const RowGeom g = row_geom_ld(dim, ld_stash % 4 == 0 ? 4 : ld_stash % 2 == 0 ? 2 : 1);
+  const RowGeom g = row_geom_ld(dim, vec_width({ld_stash}));
   const unsigned grid = grid_for_rows(batch, g.lpr_log2);
   const AdamHp h = make_hp(0.0, beta1, beta2, eps);
   const StepStateDev* ss = (const StepStateDev*)step_state;
   hipStream_t s = (hipStream_t)stream;
-  static const bool wave_rows = [] { const char* e = getenv("BR_WAVE_ROWS"); return !(e && e[0] == '0'); }();
-  const int wvec = dim / 32;
-  if (wave_rows && dim % 32 == 0 && (wvec == 2 || wvec == 4) && ld_stash % wvec == 0 &&
+  const int wvec = wave_pair_vec(dim);      // (units of 32 floats: a lane owns the same columns of the user row and the item row)
+  if (wave_rows_enabled() && wvec && ld_stash % wvec == 0 &&
       ((reinterpret_cast<uintptr_t>(stash_user) | reinterpret_cast<uintptr_t>(stash_item) | reinterpret_cast<uintptr_t>(x0)) & (4 * wvec - 1)) == 0) {
     const unsigned wgrid = (unsigned)ceil_div(batch, 4);
     const LookupArgs la{user_tab, user_m, user_v, user_last, item_tab, item_m, item_v, item_last, user_rows, item_rows, users, items, batch, item_first, ss, h,
                         x0, dot, stash_user, stash_item, ld_stash, err_flag};
-    if (id_type == BR_IDS_I32) { if (wvec == 2) neumf_embed_fwd_deferred_wave_kernel<int32_t, 2><<<wgrid, 256, 0, s>>>(la); else neumf_embed_fwd_deferred_wave_kernel<int32_t, 4><<<wgrid, 256, 0, s>>>(la); }
-    else { if (wvec == 2) neumf_embed_fwd_deferred_wave_kernel<int64_t, 2><<<wgrid, 256, 0, s>>>(la); else neumf_embed_fwd_deferred_wave_kernel<int64_t, 4><<<wgrid, 256, 0, s>>>(la); }
+    BR_DISPATCH_ID(id_type, { if (wvec == 2) neumf_embed_fwd_deferred_wave_kernel<IdT, 2><<<wgrid, 256, 0, s>>>(la); else neumf_embed_fwd_deferred_wave_kernel<IdT, 4><<<wgrid, 256, 0, s>>>(la); });
     BR_CHECK_LAUNCH("brNeumfEmbedForwardDeferred(wave)");
     return BR_OK;
   }
-  if (id_type == BR_IDS_I32) {
-    BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_deferred_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(
-                               user_tab, user_m, user_v, user_last, item_tab, item_m, item_v, item_last, user_rows, item_rows,
-                               (const int32_t*)users, (const int32_t*)items, dim, g.chunks, g.lpr_log2, batch, item_first, ss, h, x0, dot,
-                               stash_user, stash_item, ld_stash, err_flag)));
-  } else {
-    BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_deferred_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(
-                               user_tab, user_m, user_v, user_last, item_tab, item_m, item_v, item_last, user_rows, item_rows,
-                               (const int64_t*)users, (const int64_t*)items, dim, g.chunks, g.lpr_log2, batch, item_first, ss, h, x0, dot,
-                               stash_user, stash_item, ld_stash, err_flag)));
-  }
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_deferred_kernel<IdT, VEC><<<grid, 256, 0, s>>>(
+                                                     user_tab, user_m, user_v, user_last, item_tab, item_m, item_v, item_last, user_rows, item_rows, (const IdT*)users,
+                                                     (const IdT*)items, dim, g.chunks, g.lpr_log2, batch, item_first, ss, h, x0, dot, stash_user, stash_item, ld_stash, err_flag))));
   BR_CHECK_LAUNCH("brNeumfEmbedForwardDeferred");
   return BR_OK;
 }
@@ -569,25 +547,16 @@ extern "C" int brGatherRowsDeferred(const float* table, const float* m, const fl
   const AdamHp h = make_hp(0.0, beta1, beta2, eps);
   const StepStateDev* ss = (const StepStateDev*)step_state;
   hipStream_t s = (hipStream_t)stream;
-  static const bool wave_rows = [] { const char* e = getenv("BR_WAVE_ROWS"); return !(e && e[0] == '0'); }();
-  const int wvec = dim / 64;
-  if (wave_rows && dim % 64 == 0 && (wvec == 1 || wvec == 2 || wvec == 4) && ld_out % wvec == 0 && (reinterpret_cast<uintptr_t>(out) & (4 * wvec - 1)) == 0) {
+  const int wvec = wave_row_vec(dim);
+  if (wave_rows_enabled() && wvec && ld_out % wvec == 0 && (reinterpret_cast<uintptr_t>(out) & (4 * wvec - 1)) == 0) {
     const unsigned wgrid = (unsigned)ceil_div(n, 4);
-    if (id_type == BR_IDS_I32)
-      BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_kernel<int32_t, VEC><<<wgrid, 256, 0, s>>>(table, m, v, last, table_rows, (const int32_t*)ids, n, ss, h,
-                                                                                                   out, ld_out, err_flag)));
-    else
-      BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_kernel<int64_t, VEC><<<wgrid, 256, 0, s>>>(table, m, v, last, table_rows, (const int64_t*)ids, n, ss, h,
-                                                                                                   out, ld_out, err_flag)));
+    BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_kernel<IdT, VEC><<<wgrid, 256, 0, s>>>(table, m, v, last, table_rows, (const IdT*)ids, n, ss, h, out,
+                                                                                                                 ld_out, err_flag))));
     BR_CHECK_LAUNCH("brGatherRowsDeferred(wave)");
     return BR_OK;
   }
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (gather_rows_deferred_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(table, m, v, last, table_rows, dim, g.chunks, g.lpr_log2,
-                                                                                           (const int32_t*)ids, n, ss, h, out, ld_out, err_flag)));
-  else
-    BR_DISPATCH_VEC(g.vec, (gather_rows_deferred_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(table, m, v, last, table_rows, dim, g.chunks, g.lpr_log2,
-                                                                                           (const int64_t*)ids, n, ss, h, out, ld_out, err_flag)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (gather_rows_deferred_kernel<IdT, VEC><<<grid, 256, 0, s>>>(table, m, v, last, table_rows, dim, g.chunks, g.lpr_log2, (const IdT*)ids, n,
+                                                                                                          ss, h, out, ld_out, err_flag))));
   BR_CHECK_LAUNCH("brGatherRowsDeferred");
   return BR_OK;
 }
@@ -601,9 +570,8 @@ extern "C" int brGatherRowsDeferredPair(const float* table_a, const float* m_a, 
                    n >= 0 && n_b >= 0 && ld_out >= dim, "brGatherRowsDeferredPair: bad args");
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brGatherRowsDeferredPair: bad id_type");
   if (n == 0 && n_b == 0) return BR_OK;
-  const int wvec = dim / 64;
-  const bool wave_ok = dim % 64 == 0 && (wvec == 1 || wvec == 2 || wvec == 4) && ld_out % wvec == 0 &&
-                       ((reinterpret_cast<uintptr_t>(out_a) | reinterpret_cast<uintptr_t>(out_b)) & (4 * wvec - 1)) == 0;
+  const int wvec = wave_row_vec(dim);
+  const bool wave_ok = wvec && ld_out % wvec == 0 && ((reinterpret_cast<uintptr_t>(out_a) | reinterpret_cast<uintptr_t>(out_b)) & (4 * wvec - 1)) == 0;
   if (!wave_ok) {      // other row widths: the two single-table launches
     const int rc = brGatherRowsDeferred(table_a, m_a, v_a, last_a, rows_a, dim, ids_a, id_type, n, step_state, beta1, beta2, eps, out_a, ld_out, err_flag, stream);
     if (rc != BR_OK) return rc;
@@ -616,10 +584,7 @@ extern "C" int brGatherRowsDeferredPair(const float* table_a, const float* m_a, 
   const StepStateDev* ss = (const StepStateDev*)step_state;
   const dim3 grid((unsigned)ceil_div(n > n_b ? n : n_b, 4), 2);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_pair_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(J, ss, h, ld_out, err_flag)));
-  else
-    BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_pair_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(J, ss, h, ld_out, err_flag)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_pair_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, ss, h, ld_out, err_flag))));
   BR_CHECK_LAUNCH("brGatherRowsDeferredPair");
   return BR_OK;
 }
@@ -633,8 +598,8 @@ extern "C" int brGatherRowsDeferredPairSeg(const float* table_a, const float* m_
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brGatherRowsDeferredPairSeg: bad id_type");
   BR_CHECK_ARG(seg_len >= 1 && seg_stride >= seg_len && seg_off_a >= 0 && seg_off_b >= 0, "brGatherRowsDeferredPairSeg: bad segment geometry");
   if (n == 0) return BR_OK;
-  const int wvec = dim / 64;
-  BR_CHECK_ARG(dim % 64 == 0 && (wvec == 1 || wvec == 2 || wvec == 4) && ld_out % wvec == 0 && (reinterpret_cast<uintptr_t>(out) & (4 * wvec - 1)) == 0,
+  const int wvec = wave_row_vec(dim);
+  BR_CHECK_ARG(wvec && ld_out % wvec == 0 && (reinterpret_cast<uintptr_t>(out) & (4 * wvec - 1)) == 0,
                "brGatherRowsDeferredPairSeg: rows of 64 / 128 / 256 floats (one wave per row)");
   GatherDefJobs J;
   J.j[0] = GatherDefJob{table_a, m_a, v_a, last_a, rows_a, ids, out, n, seg_off_a};
@@ -644,10 +609,7 @@ extern "C" int brGatherRowsDeferredPairSeg(const float* table_a, const float* m_
   const StepStateDev* ss = (const StepStateDev*)step_state;
   const dim3 grid((unsigned)ceil_div(n, 4), 2);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_pair_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(J, ss, h, ld_out, err_flag)));
-  else
-    BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_pair_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(J, ss, h, ld_out, err_flag)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(wvec, (gather_rows_deferred_wave_pair_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, ss, h, ld_out, err_flag))));
   BR_CHECK_LAUNCH("brGatherRowsDeferredPairSeg");
   return BR_OK;
 }
@@ -659,16 +621,13 @@ extern "C" int brGatherRowsPairSeg(const float* table_a, int64_t rows_a, const f
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brGatherRowsPairSeg: bad id_type");
   BR_CHECK_ARG(seg_len >= 1 && seg_stride >= seg_len && seg_off_a >= 0 && seg_off_b >= 0, "brGatherRowsPairSeg: bad segment geometry");
   if (n == 0) return BR_OK;
-  const RowGeom g = row_geom_ld(dim, (ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 4 : (ld_out % 2 == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0) ? 2 : 1);
+  const RowGeom g = row_geom_ld(dim, vec_width({ld_out}, {out}));
   GatherSegJobs J;
   J.j[0] = GatherSegJob{table_a, rows_a, ids, out, seg_off_a};
   J.j[1] = GatherSegJob{table_b, rows_b, ids, out, seg_off_b};
   const dim3 grid(grid_for_rows(n, g.lpr_log2), 2);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (gather_rows_seg_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(J, dim, g.chunks, g.lpr_log2, n, seg_len, seg_stride, ld_out, err_flag)));
-  else
-    BR_DISPATCH_VEC(g.vec, (gather_rows_seg_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(J, dim, g.chunks, g.lpr_log2, n, seg_len, seg_stride, ld_out, err_flag)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (gather_rows_seg_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, dim, g.chunks, g.lpr_log2, n, seg_len, seg_stride, ld_out, err_flag))));
   BR_CHECK_LAUNCH("brGatherRowsPairSeg");
   return BR_OK;
 }
@@ -676,7 +635,7 @@ extern "C" int brGatherRowsPairSeg(const float* table_a, int64_t rows_a, const f
 extern "C" int brMfGradInplace(float* stash_user, float* stash_item, int64_t ld, const float* ddot, int64_t batch, int dim, brStream stream) {
   BR_CHECK_ARG(stash_user && stash_item && ddot && dim >= 1 && ld >= dim && batch >= 0, "brMfGradInplace: bad args");
   if (batch == 0) return BR_OK;
-  const RowGeom g = row_geom_ld(dim, ld % 4 == 0 ? 4 : ld % 2 == 0 ? 2 : 1);
+  const RowGeom g = row_geom_ld(dim, vec_width({ld}));
   const unsigned grid = (unsigned)ceil_div(batch * g.chunks, 256);
   BR_DISPATCH_VEC(g.vec, (mf_grad_inplace_kernel<VEC><<<grid, 256, 0, (hipStream_t)stream>>>(stash_user, stash_item, ld, ddot, batch, g.chunks)));
   BR_CHECK_LAUNCH("brMfGradInplace");
@@ -694,19 +653,12 @@ extern "C" int brNeumfEmbedBackward(const float* user_mf, const float* item_mf, 
   BR_CHECK_ARG(ld_user >= dim && ld_item >= dim && ldg >= dim, "brNeumfEmbedBackward: row strides < dim");
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brNeumfEmbedBackward: bad id_type");
   if (batch == 0) return BR_OK;
-  const int64_t ldmin = (ld_user % 4 == 0 && ld_item % 4 == 0 && ldg % 4 == 0) ? 4 : (ld_user % 2 == 0 && ld_item % 2 == 0 && ldg % 2 == 0) ? 2 : 1;
-  const RowGeom g = row_geom_ld(dim, ldmin);
+  const RowGeom g = row_geom_ld(dim, vec_width({ld_user, ld_item, ldg}));
   const unsigned grid = grid_for_rows(batch, g.lpr_log2);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32) {
-    BR_DISPATCH_VEC(g.vec, (neumf_embed_bwd_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(
-                               user_mf, item_mf, ld_user, ld_item, user_rows, item_rows, (const int32_t*)users, (const int32_t*)items,
-                               dim, g.chunks, g.lpr_log2, batch, item_first, dx0, ddot, g_user_mlp, g_item_mlp, g_user_mf, g_item_mf, ldg, out_rows_by_id)));
-  } else {
-    BR_DISPATCH_VEC(g.vec, (neumf_embed_bwd_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(
-                               user_mf, item_mf, ld_user, ld_item, user_rows, item_rows, (const int64_t*)users, (const int64_t*)items,
-                               dim, g.chunks, g.lpr_log2, batch, item_first, dx0, ddot, g_user_mlp, g_item_mlp, g_user_mf, g_item_mf, ldg, out_rows_by_id)));
-  }
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (neumf_embed_bwd_kernel<IdT, VEC><<<grid, 256, 0, s>>>(
+                                                     user_mf, item_mf, ld_user, ld_item, user_rows, item_rows, (const IdT*)users, (const IdT*)items, dim, g.chunks, g.lpr_log2,
+                                                     batch, item_first, dx0, ddot, g_user_mlp, g_item_mlp, g_user_mf, g_item_mf, ldg, out_rows_by_id))));
   BR_CHECK_LAUNCH("brNeumfEmbedBackward");
   return BR_OK;
 }
@@ -722,17 +674,9 @@ extern "C" int brBprForwardBackward(const float* user_table, const float* item_t
   const RowGeom g = row_geom(dim);
   const unsigned grid = grid_for_rows(batch, g.lpr_log2);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32) {
-    BR_DISPATCH_VEC(g.vec, (bpr_fwd_bwd_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(
-                               user_table, item_table, user_rows, item_rows, (const int32_t*)users, (const int32_t*)pos,
-                               (const int32_t*)neg, dim, g.chunks, g.lpr_log2, batch, inv_batch, per_triplet, loss_sum,
-                               g_user, g_item, err_flag)));
-  } else {
-    BR_DISPATCH_VEC(g.vec, (bpr_fwd_bwd_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(
-                               user_table, item_table, user_rows, item_rows, (const int64_t*)users, (const int64_t*)pos,
-                               (const int64_t*)neg, dim, g.chunks, g.lpr_log2, batch, inv_batch, per_triplet, loss_sum,
-                               g_user, g_item, err_flag)));
-  }
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (bpr_fwd_bwd_kernel<IdT, VEC><<<grid, 256, 0, s>>>(user_table, item_table, user_rows, item_rows, (const IdT*)users, (const IdT*)pos,
+                                                                                                 (const IdT*)neg, dim, g.chunks, g.lpr_log2, batch, inv_batch, per_triplet, loss_sum,
+                                                                                                 g_user, g_item, err_flag))));
   BR_CHECK_LAUNCH("brBprForwardBackward");
   return BR_OK;
 }

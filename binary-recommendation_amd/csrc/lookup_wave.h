@@ -1,5 +1,5 @@
 // One pair of the deferred NeuMF lookup by one wave (gather.hip neumf_embed_fwd_deferred_wave_kernel; also the body of the lookup
-// workgroups of the fused lookup + chunk-sort launch in sparse_opt.hip).
+// workgroups of the fused lookup + chunk-sort launch in row_index.hip).
 #pragma once
 #include "common.h"
 #include "rows.h"

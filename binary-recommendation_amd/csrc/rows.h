@@ -4,6 +4,9 @@
 #pragma once
 #include "common.h"
 
+#include <initializer_list>
+#include <stdlib.h>
+
 namespace br {
 
 template <int VEC> struct VecT;
@@ -95,5 +98,34 @@ __device__ __forceinline__ float rowgroup_sum(float v, int lpr) {
     else if ((vec) == 2) { constexpr int VEC = 2; __VA_ARGS__; }         \
     else { constexpr int VEC = 1; __VA_ARGS__; }                         \
   } while (0)
+
+// binds IdT to the storage type of an id stream (id_type checked by the caller), as BR_DISPATCH_VEC binds VEC:
+//   BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (kernel<IdT, VEC><<<grid, 256, 0, s>>>((const IdT*)ids, ..))));
+#define BR_DISPATCH_ID(id_type, ...)                                     \
+  do {                                                                   \
+    if ((id_type) == BR_IDS_I32) { using IdT = int32_t; __VA_ARGS__; }   \
+    else { using IdT = int64_t; __VA_ARGS__; }                           \
+  } while (0)
+
+// widest vector (4, 2 or 1 floats) that divides every one of `strides` (row strides, split points: floats) and whose byte width every
+// one of `ptrs` is aligned to.  A site lists exactly what its kernel addresses by vector; a null pointer and a stride of 0 pass.
+static inline int vec_width(std::initializer_list<int64_t> strides, std::initializer_list<const void*> ptrs = {}) {
+  int64_t st = 0;
+  uintptr_t al = 0;
+  for (const int64_t x : strides) st |= x;
+  for (const void* p : ptrs) al |= reinterpret_cast<uintptr_t>(p);
+  return ((st & 3) == 0 && (al & 15) == 0) ? 4 : ((st & 1) == 0 && (al & 7) == 0) ? 2 : 1;
+}
+
+// BR_WAVE_ROWS=0: keep the row-group kernels (A/B runs)
+inline bool wave_rows_enabled() {
+  static const bool on = [] { const char* e = getenv("BR_WAVE_ROWS"); return !(e && e[0] == '0'); }();
+  return on;
+}
+// one wave per row: floats per lane (1 / 2 / 4) for rows of 64 / 128 / 256 floats, 0 for every other width
+static inline int wave_row_vec(int dim) { return dim == 64 ? 1 : dim == 128 ? 2 : dim == 256 ? 4 : 0; }
+// one wave per (user, item) pair of the NeuMF lookup: a lane owns 32-float units, so embed_dim 64 / 128 (fused rows of 128 / 256
+// floats) give 2 / 4 floats per lane and every other width 0
+static inline int wave_pair_vec(int embed_dim) { return embed_dim == 64 ? 2 : embed_dim == 128 ? 4 : 0; }
 
 }  // namespace br

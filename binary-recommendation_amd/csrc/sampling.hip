@@ -15,6 +15,7 @@
 // Feistel network over ceil(log2 M) bits with cycle walking (a keyed bijection of [0, M): O(1) per element, no sort, no state).
 // [pandas-sem] the reference is unseeded and uses pandas' sample(): only the distributions are restated, like the initialisers.
 #include "common.h"
+#include "rows.h"
 #include "philox.h"
 
 #include <hipcub/hipcub.hpp>
@@ -132,10 +133,7 @@ extern "C" int brBootstrapDataset(const void* users, const void* items, int id_t
   BR_CHECK_ARG(n >= 1 && n_neg >= 0 && n + n_neg < ((int64_t)1 << 31) && users && items && out_users && out_items && out_labels, "brBootstrapDataset: bad args");
   const unsigned grid = (unsigned)ceil_div(n + n_neg, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    bootstrap_kernel<int32_t><<<grid, 256, 0, s>>>((const int32_t*)users, (const int32_t*)items, (uint32_t)n, (uint32_t)n_neg, seed, (int32_t*)out_users, (int32_t*)out_items, out_labels);
-  else
-    bootstrap_kernel<int64_t><<<grid, 256, 0, s>>>((const int64_t*)users, (const int64_t*)items, (uint32_t)n, (uint32_t)n_neg, seed, (int64_t*)out_users, (int64_t*)out_items, out_labels);
+  BR_DISPATCH_ID(id_type, (bootstrap_kernel<IdT><<<grid, 256, 0, s>>>((const IdT*)users, (const IdT*)items, (uint32_t)n, (uint32_t)n_neg, seed, (IdT*)out_users, (IdT*)out_items, out_labels)));
   BR_CHECK_LAUNCH("brBootstrapDataset");
   return BR_OK;
 }
@@ -148,12 +146,8 @@ extern "C" int brBprSampleTriplets(const void* users, const void* items, int id_
                pos_off && pos_items && out_users && out_pos && out_neg, "brBprSampleTriplets: bad args");
   const unsigned grid = (unsigned)ceil_div(n * neg_per_pos, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    bpr_triplets_kernel<int32_t><<<grid, 256, 0, s>>>((const int32_t*)users, (const int32_t*)items, (uint32_t)n, neg_per_pos, pos_off, (const int32_t*)pos_items,
-                                                      (const int32_t*)cand_items, (uint32_t)n_cand, seed, max_tries, (int32_t*)out_users, (int32_t*)out_pos, (int32_t*)out_neg);
-  else
-    bpr_triplets_kernel<int64_t><<<grid, 256, 0, s>>>((const int64_t*)users, (const int64_t*)items, (uint32_t)n, neg_per_pos, pos_off, (const int64_t*)pos_items,
-                                                      (const int64_t*)cand_items, (uint32_t)n_cand, seed, max_tries, (int64_t*)out_users, (int64_t*)out_pos, (int64_t*)out_neg);
+  BR_DISPATCH_ID(id_type, (bpr_triplets_kernel<IdT><<<grid, 256, 0, s>>>((const IdT*)users, (const IdT*)items, (uint32_t)n, neg_per_pos, pos_off, (const IdT*)pos_items, (const IdT*)cand_items,
+                                                                       (uint32_t)n_cand, seed, max_tries, (IdT*)out_users, (IdT*)out_pos, (IdT*)out_neg)));
   BR_CHECK_LAUNCH("brBprSampleTriplets");
   return BR_OK;
 }
@@ -164,10 +158,7 @@ extern "C" int brNcfNegativeCandidates(const void* users, const void* items, int
   BR_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31) && n_cand >= 1 && num_items >= 1 && users && items && pos_off && pos_items && keys, "brNcfNegativeCandidates: bad args");
   const unsigned grid = (unsigned)ceil_div(n_cand, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    ncf_candidates_kernel<int32_t><<<grid, 256, 0, s>>>((const int32_t*)users, (const int32_t*)items, (uint32_t)n, (uint64_t)n_cand, pos_off, (const int32_t*)pos_items, num_items, seed, keys);
-  else
-    ncf_candidates_kernel<int64_t><<<grid, 256, 0, s>>>((const int64_t*)users, (const int64_t*)items, (uint32_t)n, (uint64_t)n_cand, pos_off, (const int64_t*)pos_items, num_items, seed, keys);
+  BR_DISPATCH_ID(id_type, (ncf_candidates_kernel<IdT><<<grid, 256, 0, s>>>((const IdT*)users, (const IdT*)items, (uint32_t)n, (uint64_t)n_cand, pos_off, (const IdT*)pos_items, num_items, seed, keys)));
   BR_CHECK_LAUNCH("brNcfNegativeCandidates");
   return BR_OK;
 }
@@ -202,10 +193,7 @@ extern "C" int brGatherPermutedPairs(const uint64_t* keys, int64_t n_keys, int64
   if (n_out == 0) return BR_OK;
   const unsigned grid = (unsigned)ceil_div(n_out, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    gather_permuted_pairs_kernel<int32_t><<<grid, 256, 0, s>>>(keys, (uint32_t)n_keys, (uint32_t)n_out, num_items, seed, (int32_t*)out_users, (int32_t*)out_items);
-  else
-    gather_permuted_pairs_kernel<int64_t><<<grid, 256, 0, s>>>(keys, (uint32_t)n_keys, (uint32_t)n_out, num_items, seed, (int64_t*)out_users, (int64_t*)out_items);
+  BR_DISPATCH_ID(id_type, (gather_permuted_pairs_kernel<IdT><<<grid, 256, 0, s>>>(keys, (uint32_t)n_keys, (uint32_t)n_out, num_items, seed, (IdT*)out_users, (IdT*)out_items)));
   BR_CHECK_LAUNCH("brGatherPermutedPairs");
   return BR_OK;
 }

@@ -4,7 +4,7 @@
 // step sends each owner the ids it must serve.  A batch names the same id many times (Zipf: one id on thousands of positions) - the
 // owner needs it once, and so does the wire:
 //   key[b]  = owner(id_b) * R + id_b div W        (R = rows per owner, rounded up: keys of one owner are contiguous)
-//   (key, position) pairs are sorted (the dedup index machinery of sparse_opt.hip: stable, so equal keys keep batch order),
+//   (key, position) pairs are sorted (the dedup index machinery of row_index.hip: stable, so equal keys keep batch order),
 //   the k-th DISTINCT key of owner d gets send slot (d * 2 + stream) * cap + k of the step's ONE all-to-all buffer
 //   [owner][stream: user | item][cap], every position of the batch learns its id's slot, and the sorted index stays behind for the
 //   backward: the row gradients of an id's positions are summed (ordered, two-level) into that slot before they travel
@@ -15,6 +15,7 @@
 // no row of any table sees a wrong gradient) and BR_ERRFLAG_CAPACITY is raised for the host's next check.  Out-of-range ids likewise
 // (BR_ERRFLAG_RANGE).
 #include "common.h"
+#include "rows.h"
 
 namespace br {
 
@@ -186,8 +187,7 @@ extern "C" int brShardDedupPlanPair(const void* ids_a, const void* ids_b, int id
   J.j[1] = DedupJob{ids_b, keys_b, sorted_keys_b, sorted_pos_b, urank_b, first_b, slot_b, total_rows_b, Rb, 1};
   if (n > 0) {
     const dim3 g((unsigned)ceil_div(n, 256), 2);
-    if (id_type == BR_IDS_I32) dedup_key_kernel<int32_t><<<g, 256, 0, s>>>(J, n, world, err_flag);
-    else dedup_key_kernel<int64_t><<<g, 256, 0, s>>>(J, n, world, err_flag);
+    BR_DISPATCH_ID(id_type, (dedup_key_kernel<IdT><<<g, 256, 0, s>>>(J, n, world, err_flag)));
     BR_CHECK_LAUNCH("brShardDedupPlanPair(keys)");
     const int rc = brRowIndexBuildPair(keys_a, (int64_t)world * Ra + 1, sorted_keys_a, sorted_pos_a, ws_a, ws_bytes, keys_b, (int64_t)world * Rb + 1, sorted_keys_b,
                                        sorted_pos_b, ws_b, ws_bytes, id_type, n, stream);
@@ -200,23 +200,184 @@ extern "C" int brShardDedupPlanPair(const void* ids_a, const void* ids_b, int id
     int32_t* block_cnt = (int32_t*)ws_a;
     BR_CHECK_ARG(ws_bytes >= (int64_t)sizeof(int32_t) * 2 * n_blocks, "brShardDedupPlanPair: workspace too small for the scan");
     const dim3 gs((unsigned)n_blocks, 2);
-    if (id_type == BR_IDS_I32) { dedup_count_kernel<int32_t><<<gs, kScanThreads, 0, s>>>(J, n, block_cnt, n_blocks); dedup_rank_kernel<int32_t><<<gs, kScanThreads, 0, s>>>(J, n, block_cnt, n_blocks); }
-    else { dedup_count_kernel<int64_t><<<gs, kScanThreads, 0, s>>>(J, n, block_cnt, n_blocks); dedup_rank_kernel<int64_t><<<gs, kScanThreads, 0, s>>>(J, n, block_cnt, n_blocks); }
+    BR_DISPATCH_ID(id_type, { dedup_count_kernel<IdT><<<gs, kScanThreads, 0, s>>>(J, n, block_cnt, n_blocks); dedup_rank_kernel<IdT><<<gs, kScanThreads, 0, s>>>(J, n, block_cnt, n_blocks); });
     BR_CHECK_LAUNCH("brShardDedupPlanPair(scan)");
   }
   const dim3 gf((unsigned)ceil_div(world + 1, 256), 2);
-  if (id_type == BR_IDS_I32) dedup_first_kernel<int32_t><<<gf, 256, 0, s>>>(J, n, world);
-  else dedup_first_kernel<int64_t><<<gf, 256, 0, s>>>(J, n, world);
+  BR_DISPATCH_ID(id_type, (dedup_first_kernel<IdT><<<gf, 256, 0, s>>>(J, n, world)));
   BR_CHECK_LAUNCH("brShardDedupPlanPair(first)");
   const int64_t m = n > (int64_t)world * cap ? n : (int64_t)world * cap;
   const dim3 g2((unsigned)ceil_div(m, 256), 2);
-  if (id_type == BR_IDS_I32) dedup_slot_kernel<int32_t><<<g2, 256, 0, s>>>(J, n, world, cap, (int32_t*)send_ids, err_flag);
-  else dedup_slot_kernel<int64_t><<<g2, 256, 0, s>>>(J, n, world, cap, (int64_t*)send_ids, err_flag);
+  BR_DISPATCH_ID(id_type, (dedup_slot_kernel<IdT><<<g2, 256, 0, s>>>(J, n, world, cap, (IdT*)send_ids, err_flag)));
   BR_CHECK_LAUNCH("brShardDedupPlanPair(slots)");
   if (grad_slots) {
     const dim3 gz((unsigned)ceil_div((int64_t)world * cap * (zero_dim >> 2), 256), 2);
     dedup_zero_pads_kernel<<<gz, 256, 0, s>>>(J, world, cap, grad_slots, zero_dim);
     BR_CHECK_LAUNCH("brShardDedupPlanPair(pads)");
   }
+  return BR_OK;
+}
+
+// ---- row-sharded exchange planning without dedup (parallel.py ShardExchange.plan): owner(id) = id mod W ---------------
+// One id stream: dest = id mod W -> stable sort of (dest, position) with the index machinery of row_index.hip -> order[j] = batch
+// position of bucket slot j, inv[b] = bucket slot of position b, send_local[j] = id div W in bucket order, counts[d] =
+// rows for owner d.  4 launches for a PAIR of equally long streams instead of ~10 torch ops per stream.
+template <typename IdT>
+__global__ __launch_bounds__(256) void shard_dest_kernel(const IdT* __restrict__ a, const IdT* __restrict__ b, IdT* __restrict__ da,
+                                                          IdT* __restrict__ db, int64_t n, int world) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const IdT* src = blockIdx.y ? b : a;
+  IdT* dst = blockIdx.y ? db : da;
+  const int64_t id = (int64_t)src[i];
+  const int64_t m = id % world;
+  dst[i] = (IdT)(m < 0 ? m + world : m);
+}
+
+struct ShardFinishJob { const void* ids; const void* sorted_dest; const int32_t* order; int32_t* inv; void* send_local; int64_t* counts; };
+struct ShardFinishJobs { ShardFinishJob j[2]; };
+
+template <typename IdT>
+__global__ __launch_bounds__(256) void shard_finish_kernel(ShardFinishJobs jobs, int64_t n, int world) {
+  const ShardFinishJob& jb = jobs.j[blockIdx.y];
+  const IdT* ids = (const IdT*)jb.ids;
+  const IdT* sd = (const IdT*)jb.sorted_dest;
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) {
+    const int32_t b = jb.order[j];
+    jb.inv[b] = (int32_t)j;
+    const int64_t id = (int64_t)ids[b];
+    const int64_t m = id % world;
+    ((IdT*)jb.send_local)[j] = (IdT)((id - (m < 0 ? m + world : m)) / world);      // floor division for every sign
+  }
+  if (j < world) {                                   // rows for owner j: [lower_bound(j), lower_bound(j + 1)) of the sorted dests
+    auto lb = [&](int64_t d) {
+      int64_t lo = 0, hi = n;
+      while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)sd[mid] < d) lo = mid + 1; else hi = mid; }
+      return lo;
+    };
+    jb.counts[j] = lb(j + 1) - lb(j);
+  }
+}
+
+// ---- fixed-capacity form of the exchange plan: every peer gets exactly `cap` slots per stream, so the all-to-alls have equal, static
+// splits and no row count ever crosses to the host.  Slot t = d * cap + k holds the k-th row for owner d (bucket order), pad slots
+// hold the owner's spare row (local index = its row count: the tables of a padded engine carry one extra row whose gradient is always 0).
+struct ShardPadJob {
+  const void* sorted_dest; const int32_t* order; const void* send_local; const int64_t* counts;
+  void* send_pad; int32_t* slot; int32_t* bpos; int64_t total_rows;
+  float* zero_rows; int zero_dim;      // optional [world*cap][zero_dim] buffer whose PAD rows are cleared (gradient send slots)
+};
+struct ShardPadJobs { ShardPadJob j[2]; };
+
+template <typename IdT>
+__global__ __launch_bounds__(256) void shard_pad_kernel(ShardPadJobs jobs, int64_t n, int world, int64_t cap, int* __restrict__ overflow) {
+  const ShardPadJob& jb = jobs.j[blockIdx.y];
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < n) {                                        // bucket position t -> its slot
+    const int64_t d = (int64_t)((const IdT*)jb.sorted_dest)[t];
+    int64_t off = 0;
+    for (int64_t q = 0; q < d; ++q) off += jb.counts[q];
+    int64_t k = t - off;
+    if (k >= cap) { atomicOr(overflow, BR_ERRFLAG_CAPACITY); k = cap - 1; }     // reported by the host's next flag check
+    const int64_t sl = d * cap + k;
+    const int32_t b = jb.order[t];
+    jb.slot[b] = (int32_t)sl;
+    if (t - off < cap) { ((IdT*)jb.send_pad)[sl] = ((const IdT*)jb.send_local)[t]; jb.bpos[sl] = b; }
+  }
+  if (t < (int64_t)world * cap) {                     // pad slots
+    const int64_t d = t / cap, k = t - d * cap;
+    if (k >= jb.counts[d]) {
+      const int64_t spare = jb.total_rows > d ? (jb.total_rows - d + world - 1) / world : 0;   // rows owner d holds = index of its spare row
+      ((IdT*)jb.send_pad)[t] = (IdT)spare;
+      jb.bpos[t] = -1;
+      if (jb.zero_rows)
+        for (int c = 0; c < jb.zero_dim; c += 4) *reinterpret_cast<float4*>(jb.zero_rows + t * jb.zero_dim + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
+extern "C" int brShardPadPair(const void* sorted_dest_a, const void* sorted_dest_b, const int32_t* order_a, const int32_t* order_b,
+                              const void* send_local_a, const void* send_local_b, const int64_t* counts_a, const int64_t* counts_b, int id_type,
+                              int64_t n, int world, int64_t cap, int64_t total_rows_a, int64_t total_rows_b, void* send_pad_a, void* send_pad_b,
+                              int32_t* slot_a, int32_t* slot_b, int32_t* bpos_a, int32_t* bpos_b, float* zero_a, float* zero_b, int zero_dim, int* err_flag,
+                              brStream stream) {
+  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brShardPadPair: bad id_type");
+  BR_CHECK_ARG(!zero_a || (zero_dim >= 4 && zero_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(zero_a) & 15) == 0 && (reinterpret_cast<uintptr_t>(zero_b) & 15) == 0),
+               "brShardPadPair: zero rows need a dim that is a multiple of 4 and 16-byte alignment");
+  BR_CHECK_ARG(world >= 1 && world <= 256 && n >= 0 && cap >= 1 && err_flag, "brShardPadPair: bad world / n / cap / flag");
+  BR_CHECK_ARG(sorted_dest_a && order_a && send_local_a && counts_a && send_pad_a && slot_a && bpos_a, "brShardPadPair: null pointer (stream a)");
+  const int n_jobs = sorted_dest_b ? 2 : 1;
+  BR_CHECK_ARG(!sorted_dest_b || (order_b && send_local_b && counts_b && send_pad_b && slot_b && bpos_b), "brShardPadPair: null pointer (stream b)");
+  ShardPadJobs J;
+  J.j[0] = ShardPadJob{sorted_dest_a, order_a, send_local_a, counts_a, send_pad_a, slot_a, bpos_a, total_rows_a, zero_a, zero_dim};
+  J.j[1] = sorted_dest_b ? ShardPadJob{sorted_dest_b, order_b, send_local_b, counts_b, send_pad_b, slot_b, bpos_b, total_rows_b, zero_b, zero_dim} : J.j[0];
+  const int64_t m = n > (int64_t)world * cap ? n : (int64_t)world * cap;
+  const dim3 g((unsigned)ceil_div(m, 256), (unsigned)n_jobs);
+  BR_DISPATCH_ID(id_type, (shard_pad_kernel<IdT><<<g, 256, 0, (hipStream_t)stream>>>(J, n, world, cap, err_flag)));
+  BR_CHECK_LAUNCH("brShardPadPair");
+  return BR_OK;
+}
+
+// dst[t] = bpos[t] >= 0 ? src[bpos[t]] : 0 for one or two (src, bpos, dst) sets of equal shape: per-pair rows -> padded send slots
+struct PadRowsJob { const float* src; int64_t ld; const int32_t* bpos; float* dst; };
+struct PadRowsJobs { PadRowsJob j[2]; };
+__global__ __launch_bounds__(256) void rows_to_slots_kernel(PadRowsJobs jobs, int64_t n_slots, int dim) {
+  const PadRowsJob& jb = jobs.j[blockIdx.y];
+  const int q4 = dim >> 2;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_slots * q4) return;
+  const int64_t t = i / q4;
+  const int c = (int)(i - t * q4) << 2;
+  const int32_t b = jb.bpos[t];
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (b >= 0) v = *reinterpret_cast<const float4*>(jb.src + (int64_t)b * jb.ld + c);
+  *reinterpret_cast<float4*>(jb.dst + t * dim + c) = v;
+}
+
+extern "C" int brRowsToSlotsPair(const float* src_a, const float* src_b, int64_t ld, const int32_t* bpos_a, const int32_t* bpos_b, float* dst_a,
+                                 float* dst_b, int64_t n_slots, int dim, brStream stream) {
+  BR_CHECK_ARG(src_a && bpos_a && dst_a && n_slots >= 0 && dim >= 4 && dim % 4 == 0 && ld >= dim && ld % 4 == 0, "brRowsToSlotsPair: bad args (dim, ld multiples of 4)");
+  BR_CHECK_ARG(((reinterpret_cast<uintptr_t>(src_a) | reinterpret_cast<uintptr_t>(dst_a) | reinterpret_cast<uintptr_t>(src_b) | reinterpret_cast<uintptr_t>(dst_b)) & 15) == 0,
+               "brRowsToSlotsPair: rows must be 16-byte aligned");
+  BR_CHECK_ARG(!src_b || (bpos_b && dst_b), "brRowsToSlotsPair: null pointer (set b)");
+  if (n_slots == 0) return BR_OK;
+  PadRowsJobs J;
+  J.j[0] = PadRowsJob{src_a, ld, bpos_a, dst_a};
+  J.j[1] = src_b ? PadRowsJob{src_b, ld, bpos_b, dst_b} : J.j[0];
+  const dim3 g((unsigned)ceil_div(n_slots * (dim >> 2), 256), src_b ? 2u : 1u);
+  rows_to_slots_kernel<<<g, 256, 0, (hipStream_t)stream>>>(J, n_slots, dim);
+  BR_CHECK_LAUNCH("brRowsToSlotsPair");
+  return BR_OK;
+}
+
+extern "C" int brShardPlanPair(const void* ids_a, const void* ids_b, int id_type, int64_t n, int world, void* dest_a, void* dest_b,
+                               void* sorted_dest_a, void* sorted_dest_b, int32_t* order_a, int32_t* order_b, void* ws_a, void* ws_b,
+                               int64_t ws_bytes, int32_t* inv_a, int32_t* inv_b, void* send_local_a, void* send_local_b,
+                               int64_t* counts_a, int64_t* counts_b, brStream stream) {
+  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brShardPlanPair: bad id_type");
+  BR_CHECK_ARG(world >= 1 && world <= 256 && n >= 0, "brShardPlanPair: bad world / n");
+  const int n_jobs = ids_b ? 2 : 1;
+  BR_CHECK_ARG(ids_a && dest_a && sorted_dest_a && order_a && ws_a && inv_a && send_local_a && counts_a, "brShardPlanPair: null pointer (stream a)");
+  BR_CHECK_ARG(!ids_b || (dest_b && sorted_dest_b && order_b && ws_b && inv_b && send_local_b && counts_b), "brShardPlanPair: null pointer (stream b)");
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    (void)hipMemsetAsync(counts_a, 0, sizeof(int64_t) * world, s);
+    if (ids_b) (void)hipMemsetAsync(counts_b, 0, sizeof(int64_t) * world, s);
+    return BR_OK;
+  }
+  const dim3 g((unsigned)ceil_div(n, 256), (unsigned)n_jobs);
+  BR_DISPATCH_ID(id_type, (shard_dest_kernel<IdT><<<g, 256, 0, s>>>((const IdT*)ids_a, (const IdT*)ids_b, (IdT*)dest_a, (IdT*)dest_b, n, world)));
+  BR_CHECK_LAUNCH("brShardPlanPair(dest)");
+  int rc;
+  if (ids_b) rc = brRowIndexBuildPair(dest_a, world, sorted_dest_a, order_a, ws_a, ws_bytes, dest_b, world, sorted_dest_b, order_b, ws_b, ws_bytes, id_type, n, stream);
+  else rc = brRowIndexBuild(dest_a, id_type, n, world, sorted_dest_a, order_a, ws_a, ws_bytes, stream);
+  if (rc != BR_OK) return rc;
+  ShardFinishJobs J;
+  J.j[0] = ShardFinishJob{ids_a, sorted_dest_a, order_a, inv_a, send_local_a, counts_a};
+  J.j[1] = ids_b ? ShardFinishJob{ids_b, sorted_dest_b, order_b, inv_b, send_local_b, counts_b} : J.j[0];
+  const dim3 g2((unsigned)ceil_div(n > world ? n : world, 256), (unsigned)n_jobs);
+  BR_DISPATCH_ID(id_type, (shard_finish_kernel<IdT><<<g2, 256, 0, s>>>(J, n, world)));
+  BR_CHECK_LAUNCH("brShardPlanPair(finish)");
   return BR_OK;
 }

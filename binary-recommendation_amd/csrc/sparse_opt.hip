@@ -1,45 +1,24 @@
-// S1 duplicate-id handling + O1 TF-form Adam + O2 Keras Adagrad.
+// S1 duplicate-id sums + O1 TF-form Adam + O2 Keras Adagrad on embedding rows.
 //
-// Design: no float atomics on the training path.  ids are radix-sorted once per id stream
-// together with their batch position (stable => equal ids stay in ascending position); every
-// table that shares the stream reuses the index.  The optimizer kernels walk each segment in
-// that order, so the duplicate sum is exactly a sequential unsorted_segment_sum ([TF-sem]
-// _deduplicate_indexed_slices): bitwise reproducible, and (sum g)^2 feeds Adam's v.
-// The per-pair row gradients are written ONCE with plain stores by the backward kernels and
-// read back here through the inverted index (cdna_hip_programming.md App. B "Scatter / gather").
+// Design: no float atomics on the training path.  ids are radix-sorted once per id stream together with their batch position
+// (row_index.hip; stable => equal ids stay in ascending position); every table that shares the stream reuses the index.  The kernels
+// here walk each segment in that order, so the duplicate sum is exactly a sequential unsorted_segment_sum ([TF-sem]
+// _deduplicate_indexed_slices): bitwise reproducible, and (sum g)^2 feeds Adam's v.  The per-pair row gradients are written ONCE with
+// plain stores by the backward kernels and read back here through the inverted index (cdna_hip_programming.md App. B "Scatter / gather").
+//
+// Two concerns share this unit: the ordered segment sum (seg_walk / seg_acc, the partials, brSegmentSum*, brScatterAddRows) and the row
+// optimizers that run the same walk inside their kernels (Adam rows with the keep-plane and finalize riders, flush, dense sweep, flat
+// Adam, Adagrad).  A unit of their own for the segment-sum launches changes the code the compiler generates for segment_sum_kernel and
+// segment_sum_to_slots_kernel (tools/asm_diff.py), so they stay beside the optimizers' instantiations of the walk.
 #include "common.h"
 #include "rows.h"
 #include "adam_math.h"
 #include "finalize.h"
-#include "lookup_wave.h"
 #include "dense.h"
 
 #include <algorithm>
-#include <vector>
-#include <math.h>
-#include <stddef.h>
-#include <hipcub/hipcub.hpp>
 
 namespace br {
-
-// positions 0..n-1 and the sort keys: ids outside [0, upper) become `upper` so that they sort behind every
-// valid id instead of aliasing one in the low key bits (the optimizer kernels skip ids >= table rows)
-template <typename IdT>
-__global__ void sort_prep_kernel(const IdT* __restrict__ ids, int64_t upper, IdT* __restrict__ keys, int32_t* __restrict__ p, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    p[i] = (int32_t)i;
-    const int64_t id = (int64_t)ids[i];
-    keys[i] = (upper > 0 && (uint64_t)id >= (uint64_t)upper) ? (IdT)upper : (IdT)id;
-  }
-}
-
-__global__ __launch_bounds__(256) void zero_bytes_kernel(uint8_t* __restrict__ p, int64_t n) {
-  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (i0 + q < n) p[i0 + q] = 0;
-}
 
 // one row group per sorted position; only segment heads do work
 template <typename IdT>
@@ -237,6 +216,30 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const IdT* __restrict_
     const V acc = seg_acc<IdT, VEC>(sid, spos, n, i, row, g + c * VEC, ldg, nullptr, part ? part + c * VEC : nullptr, dim);
     vstore<VEC>(out + i * dim + c * VEC, acc);
   }
+}
+
+template <typename IdT>
+__global__ __launch_bounds__(256) void scatter_add_kernel(float* __restrict__ gt, int64_t table_rows, const IdT* __restrict__ ids,
+                                                           int64_t n, const float* __restrict__ rows, int dim, int* err) {
+  // one lane per float: a wave covers 64 contiguous floats (256 B) of one row => the atomic
+  // shape MI355X_MICROARCH.md "Global float atomics" measures at full rate for dim >= 64.
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * dim) return;
+  const int64_t b = e / dim;
+  const int d = (int)(e - b * dim);
+  const int64_t id = load_id(ids, b);
+  if ((uint64_t)id >= (uint64_t)table_rows) {
+    if (err) *err = 1;
+    return;
+  }
+  atomicAdd(gt + id * dim + d, rows[e]);
+}
+
+__global__ __launch_bounds__(256) void zero_bytes_kernel(uint8_t* __restrict__ p, int64_t n) {
+  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (i0 + q < n) p[i0 + q] = 0;
 }
 
 // Row gradients may come from two buffers: columns [0,split) from g0, [split,dim) from g1 (the fused
@@ -601,535 +604,9 @@ __global__ __launch_bounds__(256) void adagrad_flat_kernel(float* __restrict__ t
   if (i < n) adagrad_update1(th[i], acc[i], g[i], lr, eps);
 }
 
-template <typename IdT>
-__global__ __launch_bounds__(256) void scatter_add_kernel(float* __restrict__ gt, int64_t table_rows, const IdT* __restrict__ ids,
-                                                           int64_t n, const float* __restrict__ rows, int dim, int* err) {
-  // one lane per float: a wave covers 64 contiguous floats (256 B) of one row => the atomic
-  // shape MI355X_MICROARCH.md "Global float atomics" measures at full rate for dim >= 64.
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n * dim) return;
-  const int64_t b = e / dim;
-  const int d = (int)(e - b * dim);
-  const int64_t id = load_id(ids, b);
-  if ((uint64_t)id >= (uint64_t)table_rows) {
-    if (err) *err = 1;
-    return;
-  }
-  atomicAdd(gt + id * dim + d, rows[e]);
-}
-
-// top of a training step: step += 1, alpha_t (thread 0), and the step's double scratch zeroed (all threads) -
-// one launch instead of a memset node plus a kernel
-__device__ __forceinline__ void step_state_advance_block(const StepAdvance& a) {
-  for (int64_t i = threadIdx.x; i < a.n_zero; i += blockDim.x) a.zero[i] = 0.0;
-  if (threadIdx.x == 0) {
-    StepStateDev* st = a.st;
-    const uint32_t t = st->step + 1;
-    const double p1 = st->pow_b1 * a.b1, p2 = st->pow_b2 * a.b2;
-    const float al = (float)(a.lr * sqrt(1.0 - p2) / (1.0 - p1));
-    st->step = t;
-    st->pow_b1 = p1;
-    st->pow_b2 = p2;
-    st->alpha_t = al;
-    st->alpha_hist[t & (BR_ALPHA_RING - 1)] = al;
-    if ((t & (BR_ALPHA_RING - 1)) < (uint32_t)BR_RING_MIRROR) st->alpha_hist[BR_ALPHA_RING + (t & (BR_ALPHA_RING - 1))] = al;   // the mirror behind the ring's end
-  }
-}
-__global__ __launch_bounds__(256) void step_state_advance_kernel(StepAdvance a) { step_state_advance_block(a); }
-
-template <typename IdT>
-__global__ __launch_bounds__(256) void stage_batch_kernel(IdT* __restrict__ du, IdT* __restrict__ di, float* __restrict__ dy,
-                                                           const IdT* __restrict__ su, const IdT* __restrict__ si,
-                                                           const float* __restrict__ sy, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const IdT u = su[i], it = si[i];
-  const float y = sy ? sy[i] : 0.f;
-  du[i] = u; di[i] = it;
-  if (dy) dy[i] = y;
-}
-
-static inline int bits_for(int64_t upper) {
-  int bits = 1;
-  while (bits < 63 && ((int64_t)1 << bits) < upper) ++bits;
-  return bits;
-}
-
-template <typename IdT>
-static int64_t sort_temp_bytes(int64_t n) {
-  size_t bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, bytes, (const IdT*)nullptr, (IdT*)nullptr, (const int32_t*)nullptr,
-                                     (int32_t*)nullptr, (int)n, 0, (int)sizeof(IdT) * 8, (hipStream_t)0);
-  return (int64_t)bytes;
-}
-
 }  // namespace br
 
 using namespace br;
-
-static inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-// ---- dedup index for small batches: 2 launches instead of hipcub's ~10 per id stream ------------------------
-// hipcub::DeviceRadixSort on 65 536 pairs is a block sort + 6 merge passes (+ iota): ~10 launches of ~5 us each,
-// and a hipGraph replay runs them on the critical path (rocprofv3 timeline, ROCm 7.2).  For n <= kRankMaxN:
-//   K1 chunk_sort_kernel : every workgroup radix-sorts one chunk of (id, position) pairs in LDS (stable);
-//   K2 chunk_rank_kernel : the final rank of an element = its index in its chunk + for every other chunk the
-//                          number of keys that sort before it (binary search: "<=" in earlier chunks, "<" in
-//                          later ones = stable), then one scatter.
-// Chunk size: 2048 pairs (256 threads) up to 16 384 keys, 8192 pairs (1024 threads) above.  Round 1 used 2048 throughout:
-// at n = 65 536 that is 31 other chunks x 11 probes = 341 dependent L2 probes per key, 25 us alone and 90 us beside the
-// MLP kernels it overlaps (15 % of all GPU time in the rocprofv3 trace).  8 chunks of 8192 need 7 x 13 = 91 probes.
-// Both id streams of a step share the two launches (blockIdx.y).  Out-of-range ids get the key `upper`
-// (>= table rows: the optimizer kernels skip them), so only bits_for(upper + 2) key bits are sorted.
-constexpr int kChunkS = 2048, kThreadsS = 256, kChunkL = 8192, kThreadsL = 1024, kRankMaxChunks = 64;
-constexpr int64_t kChunkSwitchN = 16384;
-constexpr int64_t kRankMaxN = (int64_t)kChunkL * kRankMaxChunks;
-struct IdxJob {
-  const void* ids;
-  void* sorted_ids;
-  int32_t* sorted_pos;
-  uint32_t* ck;       // [n] chunk-sorted keys
-  uint32_t* cp;       // [n] their positions
-  uint32_t upper;     // ids are valid in [0, upper)
-  int end_bit;
-  // segmented id arrays (brRowIndexBuildPairSeg): logical position t sits at element seg_phys(t) of `ids`, and the index carries
-  // that PHYSICAL position (the optimizer reads gradient rows by it); seg_len == 0: contiguous
-  int64_t seg_len = 0, seg_stride = 0, seg_off = 0;
-  int64_t n = 0;      // this stream's keys when the two streams of a launch differ in length (0: the launch's n)
-  int n_chunks = 0;   // its chunk count then
-};
-
-struct IdxJobs { IdxJob j[2]; };
-
-// chunk `chunk` of id stream `which` by the calling workgroup of kSortThreads threads
-template <typename IdT, int kChunk, int kSortThreads>
-__device__ __forceinline__ void chunk_sort_block(const IdxJobs& jobs, int64_t n, int chunk, int which) {
-  constexpr int IPT = kChunk / kSortThreads;
-  using Sort = hipcub::BlockRadixSort<uint32_t, kSortThreads, IPT, uint32_t>;
-  __shared__ typename Sort::TempStorage tmp;
-  const IdxJob& job = jobs.j[which];
-  if (job.n) n = job.n;
-  const IdT* ids = (const IdT*)job.ids;
-  const int64_t base = (int64_t)chunk * kChunk + threadIdx.x * IPT;
-  uint32_t k[IPT], p[IPT];
-#pragma unroll
-  for (int q = 0; q < IPT; ++q) {
-    const int64_t e = base + q;
-    const int64_t pe = seg_phys(e, job.seg_len, job.seg_stride, job.seg_off);
-    const int64_t id = e < n ? (int64_t)ids[pe] : -1;
-    k[q] = e < n ? (((uint64_t)id < (uint64_t)job.upper) ? (uint32_t)id : job.upper) : job.upper + 1u;   // padding sorts last
-    p[q] = (uint32_t)pe;
-  }
-  Sort(tmp).Sort(k, p, 0, job.end_bit);
-#pragma unroll
-  for (int q = 0; q < IPT; ++q)
-    if (base + q < n) { job.ck[base + q] = k[q]; job.cp[base + q] = p[q]; }
-}
-template <typename IdT, int kChunk, int kSortThreads>
-__global__ __launch_bounds__(kSortThreads) void chunk_sort_kernel(IdxJobs jobs, int64_t n) {
-  chunk_sort_block<IdT, kChunk, kSortThreads>(jobs, n, (int)blockIdx.x, (int)blockIdx.y);
-}
-
-// The deferred NeuMF lookup and the chunk sorts of the step's two id streams in ONE launch of 1024-thread workgroups: the first
-// 2 * n_chunks workgroups each sort a chunk (they start first and run ~37 us on 16 CUs), the rest are lookup workgroups of 16 waves =
-// 16 pairs that flow around them.  As a launch of their own on a side stream the sorts needed a fork and a join in the step's
-// hipGraph (~10 us each on the main branch, ROCm 7.2) and stretched the lookup they ran beside; the chunk-rank launch follows on the
-// same stream.  LDS: the sort's image is reserved by every workgroup (two per CU = 32 waves: the lookup's full occupancy anyway).
-template <typename IdT, int VEC, int R>
-__global__ __launch_bounds__(kThreadsL, 8) void lookup_sort_kernel(const LookupArgs a, IdxJobs jobs, int64_t n, int n_chunks) {
-  const int n_sort = 2 * n_chunks;
-  if ((int)blockIdx.x < n_sort) {
-    chunk_sort_block<IdT, kChunkL, kThreadsL>(jobs, n, (int)blockIdx.x % n_chunks, (int)blockIdx.x / n_chunks);
-    return;
-  }
-  const int64_t b = (((int64_t)blockIdx.x - n_sort) * (kThreadsL / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * (R < 1 ? 1 : R);
-  if (b >= a.batch) return;
-  if constexpr (R == 0) {      // embed_dim 64: both rows of the pair side by side (lookup_half_pair); exact replay keeps the form above
-    if (a.ss->fast) lookup_half_pair<IdT>(a, b, (int)(threadIdx.x & 63));
-    else lookup_wave_pair<IdT, VEC>(a, b, (int)(threadIdx.x & 63));
-  } else if constexpr (R == 1) lookup_wave_pair<IdT, VEC>(a, b, (int)(threadIdx.x & 63));
-  else lookup_wave_pairs<IdT, VEC, R>(a, b, (int)(threadIdx.x & 63));
-}
-// form of the fused lookup at embed_dim 64: BR_LOOKUP_PAIRS = 1 (default: one pair per wave, lookup_wave_pair) | 2 (two pairs per wave) |
-// 0 (lookup_half_pair: both rows of the pair side by side, 16 B per lane).  Measured at config 2, same bits in all three: 68-69 us | 70.5 us |
-// 86-88 us - the half-wave form halves the load instructions but replays four elements per lane over max(lag_u, lag_i) steps with a
-// per-lane alpha select: the launch follows its VALU work, not its instruction count.
-static int lookup_pairs_per_wave() {
-  static const int r = [] { const char* e = getenv("BR_LOOKUP_PAIRS"); const int v = e ? atoi(e) : 1; return (v == 0 || v == 2) ? v : 1; }();
-  return r;
-}
-
-// Two deferred gathers of one row width (rows of 64 * VEC floats, one wave per row) and the chunk sorts of their two id streams in ONE
-// launch of 1024-thread workgroups - the BPR step's user gather (B rows) and [pos | neg] item gather (2 B rows): the first workgroups each
-// sort a chunk, the rest gather 16 rows each and flow around them; the chunk-rank launch (+ the step-state advance) follows on the same
-// stream.  As launches of their own on two side streams the sorts and ranks were 42 % of the step's kernel time and cost a fork / join
-// inside the step's hipGraph.
-// rows per wave of the fused gather: 1 KB of row per wave and table (dim 64: four rows)
-template <int VEC> constexpr int kGatherRowsPerWave = VEC == 1 ? 4 : (VEC == 2 ? 2 : 1);
-template <typename IdT, int VEC>
-__global__ __launch_bounds__(kThreadsL) void gather_sort_kernel(const GatherDefJobs gj, const StepStateDev* __restrict__ ss, const AdamHp h, int64_t ld_out, int* err,
-                                                                IdxJobs jobs, int n_sort_a, int n_sort_b, bool gather_group4_enabled) {
-  const int n_sort = n_sort_a + n_sort_b;
-  if ((int)blockIdx.x < n_sort) {
-    const int which = (int)blockIdx.x < n_sort_a ? 0 : 1;
-    chunk_sort_block<IdT, kChunkL, kThreadsL>(jobs, 0, which ? (int)blockIdx.x - n_sort_a : (int)blockIdx.x, which);
-    return;
-  }
-  constexpr int R = kGatherRowsPerWave<VEC>;
-  const int64_t b0 = (((int64_t)blockIdx.x - n_sort) * (kThreadsL / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * R;
-  if (b0 >= gj.j[0].n + gj.j[1].n) return;
-  if constexpr (VEC == 1) {      // 256-B rows: four rows side by side at 16 B per lane under the fast replay (gather_deferred_group4)
-    if (ss->fast && (ld_out & 3) == 0 && gather_group4_enabled) { gather_deferred_group4<IdT>(gj, b0, (int)(threadIdx.x & 63), ss, h, ld_out, err); return; }
-  }
-  gather_deferred_wave_rows<IdT, VEC, R>(gj, b0, (int)(threadIdx.x & 63), ss, h, ld_out, err);
-}
-
-// adv.st != NULL: the grid has one extra column of workgroups, whose y = 0 member advances the step state (nothing in this launch reads it;
-// the lookup in front computed its step as ss->step + 1, everything behind sees the advanced state) - one launch less per step
-template <typename IdT, int kChunk>
-__global__ __launch_bounds__(256) void chunk_rank_kernel(IdxJobs jobs, int64_t n, int n_chunks, const StepAdvance adv) {      // (n: the longer stream's keys)
-  if (adv.st && blockIdx.x == gridDim.x - 1) {
-    if (blockIdx.y == 0) step_state_advance_block(adv);
-    return;
-  }
-  const IdxJob& job = jobs.j[blockIdx.y];
-  if (job.n) { n = job.n; n_chunks = job.n_chunks; }
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const int c = (int)(e / kChunk);
-  const uint32_t key = job.ck[e];
-  uint32_t rank = (uint32_t)(e - (int64_t)c * kChunk);
-  constexpr int G = 8;                                   // chunks searched together (independent probes in flight per step)
-  for (int c0 = 0; c0 < n_chunks; c0 += G) {
-    uint32_t lo[G], len[G];
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const int cc = c0 + u;
-      const int64_t left = n - (int64_t)cc * kChunk;
-      len[u] = (cc < n_chunks && cc != c) ? (uint32_t)(left < kChunk ? left : kChunk) : 0u;
-      lo[u] = 0u;
-    }
-#pragma unroll
-    for (int step = kChunk; step > 0; step >>= 1) {
-      // the G probes of a step are issued first, then the G bounds move - as arithmetic, not predicated moves
-      // (47 -> 38 us for the pair; more chunks per step, more lanes per element or an LDS splitter level were all slower)
-      uint32_t v[G];
-#pragma unroll
-      for (int u = 0; u < G; ++u) {
-        const uint32_t idx = lo[u] + (uint32_t)step;
-        const uint32_t at = idx <= len[u] ? idx - 1u : 0u;                          // clamped probe, branch-free
-        v[u] = job.ck[(int64_t)(c0 + u < n_chunks ? c0 + u : 0) * kChunk + at];
-      }
-#pragma unroll
-      for (int u = 0; u < G; ++u) {
-        const uint32_t idx = lo[u] + (uint32_t)step;
-        const uint32_t lt = (c0 + u < c) ? (v[u] <= key ? 1u : 0u) : (v[u] < key ? 1u : 0u);   // earlier chunk: ties sort before
-        lo[u] += (idx <= len[u] ? lt : 0u) * (uint32_t)step;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u) rank += lo[u];
-  }
-  ((IdT*)job.sorted_ids)[rank] = (IdT)key;
-  job.sorted_pos[rank] = (int32_t)job.cp[e];
-}
-
-static bool rank_path_ok(int64_t n, int64_t upper) { return n <= kRankMaxN && upper > 0 && upper < ((int64_t)1 << 31) - 2; }
-
-static int index_build_rank(IdxJobs& jobs, int n_jobs, int id_type, int64_t n, hipStream_t s) {
-  const bool large = n > kChunkSwitchN;
-  const int n_chunks = (int)ceil_div(n, large ? kChunkL : kChunkS);
-  const dim3 g1((unsigned)n_chunks, (unsigned)n_jobs), g2((unsigned)ceil_div(n, 256), (unsigned)n_jobs);
-  if (id_type == BR_IDS_I32) {
-    if (large) { chunk_sort_kernel<int32_t, kChunkL, kThreadsL><<<g1, kThreadsL, 0, s>>>(jobs, n); probe_split(BR_TAG_INDEX_SORT, s); chunk_rank_kernel<int32_t, kChunkL><<<g2, 256, 0, s>>>(jobs, n, n_chunks, StepAdvance{}); }
-    else { chunk_sort_kernel<int32_t, kChunkS, kThreadsS><<<g1, kThreadsS, 0, s>>>(jobs, n); probe_split(BR_TAG_INDEX_SORT, s); chunk_rank_kernel<int32_t, kChunkS><<<g2, 256, 0, s>>>(jobs, n, n_chunks, StepAdvance{}); }
-  } else {
-    if (large) { chunk_sort_kernel<int64_t, kChunkL, kThreadsL><<<g1, kThreadsL, 0, s>>>(jobs, n); probe_split(BR_TAG_INDEX_SORT, s); chunk_rank_kernel<int64_t, kChunkL><<<g2, 256, 0, s>>>(jobs, n, n_chunks, StepAdvance{}); }
-    else { chunk_sort_kernel<int64_t, kChunkS, kThreadsS><<<g1, kThreadsS, 0, s>>>(jobs, n); probe_split(BR_TAG_INDEX_SORT, s); chunk_rank_kernel<int64_t, kChunkS><<<g2, 256, 0, s>>>(jobs, n, n_chunks, StepAdvance{}); }
-  }
-  BR_CHECK_LAUNCH("brRowIndexBuild");
-  return BR_OK;
-}
-static IdxJob make_job(const void* ids, void* sorted_ids, int32_t* sorted_pos, void* workspace, int64_t n, int64_t upper) {
-  IdxJob j{};
-  j.ids = ids; j.sorted_ids = sorted_ids; j.sorted_pos = sorted_pos;
-  j.ck = (uint32_t*)workspace;
-  j.cp = (uint32_t*)((char*)workspace + align256(n * 4));
-  j.upper = (uint32_t)upper;
-  j.end_bit = bits_for(upper + 2);
-  return j;
-}
-
-extern "C" int64_t brRowIndexWorkspaceBytes(int64_t n, int id_type) {
-  if (n <= 0) return 256;
-  const int64_t iota = align256(n * 4);
-  const int64_t tmp = id_type == BR_IDS_I64 ? sort_temp_bytes<int64_t>(n) : sort_temp_bytes<int32_t>(n);
-  const int64_t rank = 2 * align256(n * 4);       // chunk-sorted keys + positions (small-batch path)
-  const int64_t sort = iota + align256(n * 8) + align256(tmp);
-  return (sort > rank ? sort : rank) + 256;
-}
-
-extern "C" int brRowIndexBuild(const void* ids, int id_type, int64_t n, int64_t id_upper_bound, void* sorted_ids,
-                               int32_t* sorted_pos, void* workspace, int64_t workspace_bytes, brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brRowIndexBuild: bad id_type");
-  BR_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31), "brRowIndexBuild: n out of range");
-  if (n == 0) return BR_OK;
-  BR_CHECK_ARG(ids && sorted_ids && sorted_pos && workspace, "brRowIndexBuild: null pointer");
-  const int64_t need = brRowIndexWorkspaceBytes(n, id_type);
-  if (workspace_bytes < need) {
-    set_error("brRowIndexBuild: workspace %lld < required %lld", (long long)workspace_bytes, (long long)need);
-    return BR_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (rank_path_ok(n, id_upper_bound)) {
-    IdxJobs jobs;
-    jobs.j[0] = jobs.j[1] = make_job(ids, sorted_ids, sorted_pos, workspace, n, id_upper_bound);
-    return index_build_rank(jobs, 1, id_type, n, s);
-  }
-  int32_t* iota = (int32_t*)workspace;
-  void* keys = (char*)workspace + align256(n * 4);
-  void* tmp = (char*)keys + align256(n * 8);
-  size_t tmp_bytes = (size_t)(workspace_bytes - align256(n * 4) - align256(n * 8));
-  const int end_bit_cap = (id_type == BR_IDS_I64 ? 64 : 32);
-  int end_bit = id_upper_bound > 0 ? bits_for(id_upper_bound + 1) : end_bit_cap;
-  if (end_bit > end_bit_cap) end_bit = end_bit_cap;
-  hipError_t e;
-  if (id_type == BR_IDS_I64) {
-    sort_prep_kernel<int64_t><<<(unsigned)ceil_div(n, 256), 256, 0, s>>>((const int64_t*)ids, id_upper_bound, (int64_t*)keys, iota, n);
-    e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, (const int64_t*)keys, (int64_t*)sorted_ids, (const int32_t*)iota,
-                                           sorted_pos, (int)n, 0, end_bit, s);
-  } else {
-    sort_prep_kernel<int32_t><<<(unsigned)ceil_div(n, 256), 256, 0, s>>>((const int32_t*)ids, id_upper_bound, (int32_t*)keys, iota, n);
-    e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, (const int32_t*)keys, (int32_t*)sorted_ids, (const int32_t*)iota,
-                                           sorted_pos, (int)n, 0, end_bit, s);
-  }
-  if (e != hipSuccess) {
-    set_error("brRowIndexBuild: radix sort failed: %s", hipGetErrorString(e));
-    return BR_ERR_HIP;
-  }
-  BR_CHECK_LAUNCH("brRowIndexBuild");
-  return BR_OK;
-}
-
-extern "C" int brRowIndexBuildPair(const void* ids_a, int64_t upper_a, void* sorted_ids_a, int32_t* sorted_pos_a, void* ws_a, int64_t ws_a_bytes,
-                                   const void* ids_b, int64_t upper_b, void* sorted_ids_b, int32_t* sorted_pos_b, void* ws_b, int64_t ws_b_bytes,
-                                   int id_type, int64_t n, brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brRowIndexBuildPair: bad id_type");
-  if (n == 0) return BR_OK;
-  if (rank_path_ok(n, upper_a) && rank_path_ok(n, upper_b)) {
-    BR_CHECK_ARG(ids_a && ids_b && sorted_ids_a && sorted_ids_b && sorted_pos_a && sorted_pos_b && ws_a && ws_b, "brRowIndexBuildPair: null pointer");
-    const int64_t need = brRowIndexWorkspaceBytes(n, id_type);
-    if (ws_a_bytes < need || ws_b_bytes < need) {
-      set_error("brRowIndexBuildPair: workspace < required %lld", (long long)need);
-      return BR_ERR_WORKSPACE;
-    }
-    IdxJobs jobs;
-    jobs.j[0] = make_job(ids_a, sorted_ids_a, sorted_pos_a, ws_a, n, upper_a);
-    jobs.j[1] = make_job(ids_b, sorted_ids_b, sorted_pos_b, ws_b, n, upper_b);
-    return index_build_rank(jobs, 2, id_type, n, (hipStream_t)stream);
-  }
-  const int rc = brRowIndexBuild(ids_a, id_type, n, upper_a, sorted_ids_a, sorted_pos_a, ws_a, ws_a_bytes, stream);
-  return rc != BR_OK ? rc : brRowIndexBuild(ids_b, id_type, n, upper_b, sorted_ids_b, sorted_pos_b, ws_b, ws_b_bytes, stream);
-}
-
-// The same pair of indexes over SEGMENTED id arrays: both streams of a row-sharded step arrive in ONE all-to-all buffer laid out
-// [source rank][stream][cap] (parallel.py PaddedExchange), so stream k's logical position t = src * cap + j sits at element
-// (src * 2 + k) * cap + j.  sorted_pos holds that physical element index: the owner's optimizer reads the received gradient rows (same
-// layout, one buffer for both streams) by it.  Stable in logical = physical order.
-extern "C" int brRowIndexBuildPairSeg(const void* ids_a, int64_t upper_a, void* sorted_ids_a, int32_t* sorted_pos_a, void* ws_a, int64_t ws_a_bytes,
-                                      const void* ids_b, int64_t upper_b, void* sorted_ids_b, int32_t* sorted_pos_b, void* ws_b, int64_t ws_b_bytes,
-                                      int id_type, int64_t n, int64_t seg_len, int64_t seg_stride, int64_t seg_off_a, int64_t seg_off_b, brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brRowIndexBuildPairSeg: bad id_type");
-  BR_CHECK_ARG(seg_len >= 1 && seg_stride >= seg_len && seg_off_a >= 0 && seg_off_b >= 0, "brRowIndexBuildPairSeg: bad segment geometry");
-  if (n == 0) return BR_OK;
-  BR_CHECK_ARG(ids_a && ids_b && sorted_ids_a && sorted_ids_b && sorted_pos_a && sorted_pos_b && ws_a && ws_b, "brRowIndexBuildPairSeg: null pointer");
-  BR_CHECK_ARG(rank_path_ok(n, upper_a) && rank_path_ok(n, upper_b) && seg_phys(n - 1, seg_len, seg_stride, seg_off_a > seg_off_b ? seg_off_a : seg_off_b) < ((int64_t)1 << 31),
-               "brRowIndexBuildPairSeg: n <= %lld positions and id bounds < 2^31 - 2", (long long)kRankMaxN);
-  const int64_t need = brRowIndexWorkspaceBytes(n, id_type);
-  if (ws_a_bytes < need || ws_b_bytes < need) { set_error("brRowIndexBuildPairSeg: workspace < required %lld", (long long)need); return BR_ERR_WORKSPACE; }
-  IdxJobs jobs;
-  jobs.j[0] = make_job(ids_a, sorted_ids_a, sorted_pos_a, ws_a, n, upper_a);
-  jobs.j[1] = make_job(ids_b, sorted_ids_b, sorted_pos_b, ws_b, n, upper_b);
-  jobs.j[0].seg_len = jobs.j[1].seg_len = seg_len; jobs.j[0].seg_stride = jobs.j[1].seg_stride = seg_stride;
-  jobs.j[0].seg_off = seg_off_a; jobs.j[1].seg_off = seg_off_b;
-  return index_build_rank(jobs, 2, id_type, n, (hipStream_t)stream);
-}
-
-// ---- the same index when every segment of the array is ALREADY sorted ascending (the fixed-capacity exchange: a requester sends each
-// owner its distinct local rows in key order, pads = the spare row = the largest id, behind them): the W segments of a stream are W sorted
-// runs, so the index is their merge - rank(e) = position in its own run + the number of smaller keys (earlier runs: smaller or equal) in
-// every other run, one binary search each - and the 35 us chunk sort of brRowIndexBuildPairSeg is not needed.  Output identical to it
-// (stable in logical order).  A run that is not sorted sets BR_ERRFLAG_RANGE in *err_flag (the index is then wrong).
-template <typename IdT>
-__global__ __launch_bounds__(256) void run_rank_kernel(IdxJobs jobs, int64_t n, int64_t run_len, int n_runs, int steps, int* err) {
-  const IdxJob& job = jobs.j[blockIdx.y];
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const IdT* __restrict__ ids = (const IdT*)job.ids;
-  auto key_at = [&](int64_t t) -> uint32_t {
-    const int64_t id = (int64_t)ids[seg_phys(t, job.seg_len, job.seg_stride, job.seg_off)];
-    return ((uint64_t)id < (uint64_t)job.upper) ? (uint32_t)id : job.upper;
-  };
-  const int r = (int)(e / run_len);
-  const int64_t i = e - (int64_t)r * run_len;
-  const uint32_t key = key_at(e);
-  if (i > 0 && key_at(e - 1) > key && err) atomicOr(err, BR_ERRFLAG_RANGE);
-  uint32_t rank = (uint32_t)i;
-  constexpr int G = 8;                                   // runs searched together (independent probes in flight per step)
-  for (int r0 = 0; r0 < n_runs; r0 += G) {
-    uint32_t lo[G], len[G];
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const int rr = r0 + u;
-      const int64_t left = n - (int64_t)rr * run_len;
-      len[u] = (rr < n_runs && rr != r) ? (uint32_t)(left < run_len ? left : run_len) : 0u;
-      lo[u] = 0u;
-    }
-    for (int st = steps - 1; st >= 0; --st) {
-      const uint32_t step = 1u << st;
-      uint32_t v[G];
-#pragma unroll
-      for (int u = 0; u < G; ++u) {
-        const uint32_t idx = lo[u] + step;
-        const uint32_t at = idx <= len[u] ? idx - 1u : 0u;                          // clamped probe, branch-free
-        v[u] = key_at((int64_t)(r0 + u < n_runs ? r0 + u : 0) * run_len + at);
-      }
-#pragma unroll
-      for (int u = 0; u < G; ++u) {
-        const uint32_t idx = lo[u] + step;
-        const uint32_t lt = (r0 + u < r) ? (v[u] <= key ? 1u : 0u) : (v[u] < key ? 1u : 0u);   // earlier run: ties sort before
-        lo[u] += (idx <= len[u] ? lt : 0u) * step;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u) rank += lo[u];
-  }
-  ((IdT*)job.sorted_ids)[rank] = (IdT)key;
-  job.sorted_pos[rank] = (int32_t)seg_phys(e, job.seg_len, job.seg_stride, job.seg_off);
-}
-
-extern "C" int brRowIndexMergePairSeg(const void* ids_a, int64_t upper_a, void* sorted_ids_a, int32_t* sorted_pos_a, const void* ids_b, int64_t upper_b,
-                                      void* sorted_ids_b, int32_t* sorted_pos_b, int id_type, int64_t n, int64_t seg_len, int64_t seg_stride, int64_t seg_off_a,
-                                      int64_t seg_off_b, int* err_flag, brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brRowIndexMergePairSeg: bad id_type");
-  BR_CHECK_ARG(seg_len >= 1 && seg_stride >= seg_len && seg_off_a >= 0 && seg_off_b >= 0, "brRowIndexMergePairSeg: bad segment geometry");
-  if (n == 0) return BR_OK;
-  BR_CHECK_ARG(ids_a && ids_b && sorted_ids_a && sorted_ids_b && sorted_pos_a && sorted_pos_b, "brRowIndexMergePairSeg: null pointer");
-  BR_CHECK_ARG(upper_a > 0 && upper_b > 0 && upper_a < ((int64_t)1 << 31) - 2 && upper_b < ((int64_t)1 << 31) - 2 && n < ((int64_t)1 << 31) &&
-                   seg_phys(n - 1, seg_len, seg_stride, seg_off_a > seg_off_b ? seg_off_a : seg_off_b) < ((int64_t)1 << 31),
-               "brRowIndexMergePairSeg: positions and id bounds < 2^31 - 2");
-  IdxJobs jobs;
-  jobs.j[0].ids = ids_a; jobs.j[0].sorted_ids = sorted_ids_a; jobs.j[0].sorted_pos = sorted_pos_a; jobs.j[0].upper = (uint32_t)upper_a;
-  jobs.j[1].ids = ids_b; jobs.j[1].sorted_ids = sorted_ids_b; jobs.j[1].sorted_pos = sorted_pos_b; jobs.j[1].upper = (uint32_t)upper_b;
-  jobs.j[0].ck = jobs.j[1].ck = nullptr; jobs.j[0].cp = jobs.j[1].cp = nullptr; jobs.j[0].end_bit = jobs.j[1].end_bit = 0;
-  jobs.j[0].seg_len = jobs.j[1].seg_len = seg_len; jobs.j[0].seg_stride = jobs.j[1].seg_stride = seg_stride;
-  jobs.j[0].seg_off = seg_off_a; jobs.j[1].seg_off = seg_off_b;
-  const int n_runs = (int)ceil_div(n, seg_len);
-  int steps = 0;
-  while (((int64_t)1 << steps) <= seg_len) ++steps;       // 2^steps > seg_len: the search covers every length <= seg_len
-  const dim3 grid((unsigned)ceil_div(n, 256), 2);
-  hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32) run_rank_kernel<int32_t><<<grid, 256, 0, s>>>(jobs, n, seg_len, n_runs, steps, err_flag);
-  else run_rank_kernel<int64_t><<<grid, 256, 0, s>>>(jobs, n, seg_len, n_runs, steps, err_flag);
-  BR_CHECK_LAUNCH("brRowIndexMergePairSeg");
-  return BR_OK;
-}
-
-static bool wave_rows_enabled();
-// neumf_step.cpp: lookup + both dedup indexes on one stream (lookup_sort_kernel, then the chunk-rank launch).  supported(): the wave
-// lookup's shapes, the large-chunk sort's range, BR_FUSED_SORT != 0.
-bool br::lookup_with_index_supported(int dim, int64_t n, int64_t upper_a, int64_t upper_b, int64_t ld_stash, const void* x0, const void* stash_a,
-                                     const void* stash_b) {
-  static const bool on = [] { const char* e = getenv("BR_FUSED_SORT"); return !(e && e[0] == '0'); }();
-  const int wvec = dim / 32;
-  return on && wave_rows_enabled() && dim % 32 == 0 && (wvec == 2 || wvec == 4) && ld_stash % wvec == 0 &&
-         ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(stash_a) | reinterpret_cast<uintptr_t>(stash_b)) & (4 * wvec - 1)) == 0 &&
-         n > kChunkSwitchN && rank_path_ok(n, upper_a) && rank_path_ok(n, upper_b);
-}
-int br::lookup_with_index(const LookupArgs& la, int dim, int id_type, const IndexPairArgs& ix, brStream stream, const StepAdvance* adv) {
-  const int64_t n = la.batch;
-  BR_CHECK_ARG(ix.sorted_ids_a && ix.sorted_ids_b && ix.sorted_pos_a && ix.sorted_pos_b && ix.ws_a && ix.ws_b, "lookup_with_index: null pointer");
-  const int64_t need = brRowIndexWorkspaceBytes(n, id_type);
-  if (ix.ws_a_bytes < need || ix.ws_b_bytes < need) { set_error("lookup_with_index: workspace < required %lld", (long long)need); return BR_ERR_WORKSPACE; }
-  IdxJobs jobs;
-  jobs.j[0] = make_job(la.users, ix.sorted_ids_a, ix.sorted_pos_a, ix.ws_a, n, la.user_rows);
-  jobs.j[1] = make_job(la.items, ix.sorted_ids_b, ix.sorted_pos_b, ix.ws_b, n, la.item_rows);
-  const int n_chunks = (int)ceil_div(n, kChunkL);
-  hipStream_t s = (hipStream_t)stream;
-  const int wvec = dim / 32;
-  const int ppw = wvec == 2 ? lookup_pairs_per_wave() : 1;
-  const unsigned grid = (unsigned)(2 * n_chunks + ceil_div(ceil_div(n, (int64_t)(ppw < 1 ? 1 : ppw)), (int64_t)(kThreadsL / 64)));
-  if (id_type == BR_IDS_I32) {
-    if (wvec == 2 && ppw == 0) lookup_sort_kernel<int32_t, 2, 0><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else if (wvec == 2 && ppw == 2) lookup_sort_kernel<int32_t, 2, 2><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else if (wvec == 2) lookup_sort_kernel<int32_t, 2, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else lookup_sort_kernel<int32_t, 4, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-  } else {
-    if (wvec == 2 && ppw == 0) lookup_sort_kernel<int64_t, 2, 0><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else if (wvec == 2 && ppw == 2) lookup_sort_kernel<int64_t, 2, 2><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else if (wvec == 2) lookup_sort_kernel<int64_t, 2, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else lookup_sort_kernel<int64_t, 4, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-  }
-  BR_CHECK_LAUNCH("lookup_with_index(lookup + sort)");
-  probe_split(BR_TAG_EMBED_FWD, s);
-  const StepAdvance av = adv ? *adv : StepAdvance{};
-  const dim3 g2((unsigned)(ceil_div(n, 256) + (av.st ? 1 : 0)), 2);
-  if (id_type == BR_IDS_I32) chunk_rank_kernel<int32_t, kChunkL><<<g2, 256, 0, s>>>(jobs, n, n_chunks, av);
-  else chunk_rank_kernel<int64_t, kChunkL><<<g2, 256, 0, s>>>(jobs, n, n_chunks, av);
-  BR_CHECK_LAUNCH("lookup_with_index(rank)");
-  return BR_OK;
-}
-
-extern "C" int brGatherRowsDeferredPairWithIndex(const float* table_a, const float* m_a, const float* v_a, const int32_t* last_a, int64_t rows_a, const void* ids_a,
-                                                 float* out_a, void* sorted_ids_a, int32_t* sorted_pos_a, void* ws_a, int64_t ws_a_bytes, const float* table_b,
-                                                 const float* m_b, const float* v_b, const int32_t* last_b, int64_t rows_b, const void* ids_b, float* out_b,
-                                                 void* sorted_ids_b, int32_t* sorted_pos_b, void* ws_b, int64_t ws_b_bytes, int dim, int id_type, int64_t n_a, int64_t n_b,
-                                                 void* step_state, int advance, double lr, double beta1, double beta2, double eps, int64_t ld_out, int* err_flag,
-                                                 brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brGatherRowsDeferredPairWithIndex: bad id_type");
-  BR_CHECK_ARG(table_a && m_a && v_a && last_a && ids_a && out_a && sorted_ids_a && sorted_pos_a && ws_a && table_b && m_b && v_b && last_b && ids_b && out_b &&
-                   sorted_ids_b && sorted_pos_b && ws_b && step_state && rows_a > 0 && rows_b > 0 && n_a > 0 && n_b > 0 && ld_out >= dim,
-               "brGatherRowsDeferredPairWithIndex: bad args");
-  const int wvec = dim / 64;
-  BR_CHECK_ARG(dim % 64 == 0 && (wvec == 1 || wvec == 2 || wvec == 4) && ld_out % wvec == 0 &&
-                   ((reinterpret_cast<uintptr_t>(out_a) | reinterpret_cast<uintptr_t>(out_b)) & (4 * wvec - 1)) == 0,
-               "brGatherRowsDeferredPairWithIndex: rows of 64 / 128 / 256 floats (one wave per row)");
-  BR_CHECK_ARG(rank_path_ok(n_a, rows_a) && rank_path_ok(n_b, rows_b), "brGatherRowsDeferredPairWithIndex: at most %lld ids per stream, table rows < 2^31 - 2", (long long)kRankMaxN);
-  if (ws_a_bytes < brRowIndexWorkspaceBytes(n_a, id_type) || ws_b_bytes < brRowIndexWorkspaceBytes(n_b, id_type)) {
-    set_error("brGatherRowsDeferredPairWithIndex: index workspace too small");
-    return BR_ERR_WORKSPACE;
-  }
-  GatherDefJobs G;
-  G.j[0] = GatherDefJob{table_a, m_a, v_a, last_a, rows_a, ids_a, out_a, n_a};
-  G.j[1] = GatherDefJob{table_b, m_b, v_b, last_b, rows_b, ids_b, out_b, n_b};
-  G.step_add = advance ? 1u : 0u;
-  IdxJobs jobs;
-  jobs.j[0] = make_job(ids_a, sorted_ids_a, sorted_pos_a, ws_a, n_a, rows_a);
-  jobs.j[1] = make_job(ids_b, sorted_ids_b, sorted_pos_b, ws_b, n_b, rows_b);
-  const int ca = (int)ceil_div(n_a, kChunkL), cb = (int)ceil_div(n_b, kChunkL);
-  jobs.j[0].n = n_a; jobs.j[0].n_chunks = ca; jobs.j[1].n = n_b; jobs.j[1].n_chunks = cb;
-  const AdamHp h = make_hp(0.0, beta1, beta2, eps);
-  StepStateDev* ss = (StepStateDev*)step_state;
-  hipStream_t s = (hipStream_t)stream;
-  const int rpw = wvec == 1 ? 4 : (wvec == 2 ? 2 : 1);      // kGatherRowsPerWave
-  static const bool g4env = [] { const char* e = getenv("BR_GATHER_GROUP4"); return !(e && e[0] == '0'); }();
-  const bool g4 = g4env && ((reinterpret_cast<uintptr_t>(table_a) | reinterpret_cast<uintptr_t>(table_b) | reinterpret_cast<uintptr_t>(m_a) | reinterpret_cast<uintptr_t>(m_b) |
-                             reinterpret_cast<uintptr_t>(v_a) | reinterpret_cast<uintptr_t>(v_b) | reinterpret_cast<uintptr_t>(out_a) | reinterpret_cast<uintptr_t>(out_b)) & 15) == 0;
-  const unsigned grid = (unsigned)(ca + cb + ceil_div(ceil_div(n_a + n_b, (int64_t)rpw), (int64_t)(kThreadsL / 64)));
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(wvec, (gather_sort_kernel<int32_t, VEC><<<grid, kThreadsL, 0, s>>>(G, ss, h, ld_out, err_flag, jobs, ca, cb, g4)));
-  else
-    BR_DISPATCH_VEC(wvec, (gather_sort_kernel<int64_t, VEC><<<grid, kThreadsL, 0, s>>>(G, ss, h, ld_out, err_flag, jobs, ca, cb, g4)));
-  BR_CHECK_LAUNCH("brGatherRowsDeferredPairWithIndex(gather + sort)");
-  StepAdvance av;
-  if (advance) { av.st = ss; av.lr = lr; av.b1 = beta1; av.b2 = beta2; }
-  const int64_t nmax = n_a > n_b ? n_a : n_b;
-  const dim3 g2((unsigned)(ceil_div(nmax, 256) + (advance ? 1 : 0)), 2);
-  if (id_type == BR_IDS_I32) chunk_rank_kernel<int32_t, kChunkL><<<g2, 256, 0, s>>>(jobs, nmax, ca > cb ? ca : cb, av);
-  else chunk_rank_kernel<int64_t, kChunkL><<<g2, 256, 0, s>>>(jobs, nmax, ca > cb ? ca : cb, av);
-  BR_CHECK_LAUNCH("brGatherRowsDeferredPairWithIndex(rank)");
-  return BR_OK;
-}
 
 extern "C" int64_t brSegmentScratchFloats(int64_t n, int dim) { return ceil_div(n > 0 ? n : 1, kSegBlock) * (int64_t)dim; }
 
@@ -1139,21 +616,15 @@ static int launch_partials(const SegJob* jobs, int n_jobs, int id_type, int64_t 
   if (blocks <= 0) return BR_OK;
   SegJobs J;
   for (int q = 0; q < 2; ++q) J.j[q] = jobs[q < n_jobs ? q : 0];
-  const int wvec = dim / 64;
-  if (wave_rows_enabled() && dim % 64 == 0 && (wvec == 1 || wvec == 2 || wvec == 4) && g.vec >= wvec) {     // (g.vec: the widest vector the sources' strides honour)
+  const int wvec = wave_row_vec(dim);
+  if (wave_rows_enabled() && wvec && g.vec >= wvec) {     // (g.vec: the widest vector the sources' strides honour)
     const dim3 wgrid((unsigned)ceil_div(blocks, 4), (unsigned)n_jobs);
-    if (id_type == BR_IDS_I32)
-      BR_DISPATCH_VEC(wvec, (segment_partials_wave_kernel<int32_t, VEC><<<wgrid, 256, 0, s>>>(J, n, split)));
-    else
-      BR_DISPATCH_VEC(wvec, (segment_partials_wave_kernel<int64_t, VEC><<<wgrid, 256, 0, s>>>(J, n, split)));
+    BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(wvec, (segment_partials_wave_kernel<IdT, VEC><<<wgrid, 256, 0, s>>>(J, n, split))));
     BR_CHECK_LAUNCH("segment partials (wave)");
     return BR_OK;
   }
   const dim3 grid((unsigned)ceil_div(blocks, 256 >> g.lpr_log2), (unsigned)n_jobs);
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (segment_partials_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(J, n, dim, g.chunks, g.lpr_log2, split)));
-  else
-    BR_DISPATCH_VEC(g.vec, (segment_partials_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(J, n, dim, g.chunks, g.lpr_log2, split)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (segment_partials_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, n, dim, g.chunks, g.lpr_log2, split))));
   BR_CHECK_LAUNCH("segment partials");
   return BR_OK;
 }
@@ -1172,12 +643,8 @@ extern "C" int brSegmentSumRows(const void* sorted_ids, int id_type, const int32
     const int rc = launch_partials(&job, 1, id_type, n, dim, g, dim, s);
     if (rc != BR_OK) return rc;
   }
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (segment_sum_kernel<int32_t, VEC><<<grid, 256, 0, s>>>((const int32_t*)sorted_ids, sorted_pos, n, row_grads,
-                                                                                   ldg, dim, g.chunks, g.lpr_log2, out_rows, head_flag, seg_ws)));
-  else
-    BR_DISPATCH_VEC(g.vec, (segment_sum_kernel<int64_t, VEC><<<grid, 256, 0, s>>>((const int64_t*)sorted_ids, sorted_pos, n, row_grads,
-                                                                                   ldg, dim, g.chunks, g.lpr_log2, out_rows, head_flag, seg_ws)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (segment_sum_kernel<IdT, VEC><<<grid, 256, 0, s>>>((const IdT*)sorted_ids, sorted_pos, n, row_grads, ldg, dim, g.chunks,
+                                                                                                 g.lpr_log2, out_rows, head_flag, seg_ws))));
   BR_CHECK_LAUNCH("brSegmentSumRows");
   return BR_OK;
 }
@@ -1227,11 +694,7 @@ extern "C" int brSegmentSumToSlotsPair(const void* sorted_ids_a, const int32_t* 
   if (!g1_a || !g1_b) { split = dim; g1_a = g0_a; g1_b = g0_b; ldg1 = ldg0; hi_scale = nullptr; }
   BR_CHECK_ARG(split >= 1 && split <= dim && ldg0 >= split && ldg1 >= dim - split, "brSegmentSumToSlotsPair: bad split / strides");
   BR_CHECK_ARG((seg_ws_a == nullptr) == (seg_ws_b == nullptr), "brSegmentSumToSlotsPair: seg_ws for both streams or neither");
-  const uintptr_t al = reinterpret_cast<uintptr_t>(g0_a) | reinterpret_cast<uintptr_t>(g1_a) | reinterpret_cast<uintptr_t>(g0_b) | reinterpret_cast<uintptr_t>(g1_b) |
-                       reinterpret_cast<uintptr_t>(out_slots);
-  const int64_t lm = (ldg0 % 4 == 0 && ldg1 % 4 == 0 && split % 4 == 0 && dim % 4 == 0 && (al & 15) == 0) ? 4
-                     : (ldg0 % 2 == 0 && ldg1 % 2 == 0 && split % 2 == 0 && dim % 2 == 0 && (al & 7) == 0) ? 2 : 1;
-  const RowGeom g = row_geom_ld(dim, lm);
+  const RowGeom g = row_geom_ld(dim, vec_width({ldg0, ldg1, split, dim}, {g0_a, g1_a, g0_b, g1_b, out_slots}));
   hipStream_t s = (hipStream_t)stream;
   if (seg_ws_a) {
     const SegJob segs[2] = {SegJob{sorted_ids_a, sorted_pos_a, g0_a, ldg0, g1_a, ldg1, seg_ws_a, hi_scale}, SegJob{sorted_ids_b, sorted_pos_b, g0_b, ldg0, g1_b, ldg1, seg_ws_b, hi_scale}};
@@ -1242,10 +705,7 @@ extern "C" int brSegmentSumToSlotsPair(const void* sorted_ids_a, const int32_t* 
   J.j[0] = SlotSumJob{sorted_ids_a, sorted_pos_a, slot_a, g0_a, g1_a, seg_ws_a};
   J.j[1] = SlotSumJob{sorted_ids_b, sorted_pos_b, slot_b, g0_b, g1_b, seg_ws_b};
   const dim3 grid((unsigned)ceil_div(n, 256 >> g.lpr_log2), 2);
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (segment_sum_to_slots_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(J, n, ldg0, ldg1, hi_scale, dim, g.chunks, g.lpr_log2, split, out_slots)));
-  else
-    BR_DISPATCH_VEC(g.vec, (segment_sum_to_slots_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(J, n, ldg0, ldg1, hi_scale, dim, g.chunks, g.lpr_log2, split, out_slots)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (segment_sum_to_slots_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, n, ldg0, ldg1, hi_scale, dim, g.chunks, g.lpr_log2, split, out_slots))));
   BR_CHECK_LAUNCH("brSegmentSumToSlotsPair");
   return BR_OK;
 }
@@ -1257,10 +717,7 @@ extern "C" int brScatterAddRows(float* g_table, int64_t table_rows, const void* 
   BR_CHECK_ARG(g_table && rows && dim >= 1 && table_rows > 0, "brScatterAddRows: bad args");
   const unsigned grid = (unsigned)ceil_div(n * dim, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (id_type == BR_IDS_I32)
-    scatter_add_kernel<int32_t><<<grid, 256, 0, s>>>(g_table, table_rows, (const int32_t*)ids, n, rows, dim, err_flag);
-  else
-    scatter_add_kernel<int64_t><<<grid, 256, 0, s>>>(g_table, table_rows, (const int64_t*)ids, n, rows, dim, err_flag);
+  BR_DISPATCH_ID(id_type, (scatter_add_kernel<IdT><<<grid, 256, 0, s>>>(g_table, table_rows, (const IdT*)ids, n, rows, dim, err_flag)));
   BR_CHECK_LAUNCH("brScatterAddRows");
   return BR_OK;
 }
@@ -1278,12 +735,6 @@ struct AdamRowsArgs {      // one table's host-side arguments
   int64_t n = 0;              // positions of this table when the tables of a launch differ in length (wave kernel only)
 };
 
-// BR_WAVE_ROWS=0: keep the row-group kernels (A/B runs)
-static bool wave_rows_enabled() {
-  static const bool on = [] { const char* e = getenv("BR_WAVE_ROWS"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 static int adam_rows_launch(const AdamRowsArgs* a, int n_jobs, int dim, int id_type, int64_t n, int split, double alpha_t, double beta1,
                             double beta2, double eps, const StepStateDev* ss, brStream stream, const KeepArgs* keep = nullptr,
                             const FinalArgs* fin = nullptr, bool* fin_done = nullptr) {
@@ -1300,16 +751,11 @@ static int adam_rows_launch(const AdamRowsArgs* a, int n_jobs, int dim, int id_t
     if (!t.row_grads_hi) { if (n_jobs == 1) split = dim; t.ldg_hi = t.ldg; t.row_grads_hi = t.row_grads; }
     BR_CHECK_ARG(split >= 1 && split <= dim && t.ldg >= split && t.ldg_hi >= dim - split, "brAdamRowsSorted: bad split / strides");
     // widest vector (floats) that every row start of both sources and the split honour
-    const uintptr_t al = reinterpret_cast<uintptr_t>(t.row_grads) | reinterpret_cast<uintptr_t>(t.row_grads_hi);
-    const int64_t lm = (t.ldg % 4 == 0 && t.ldg_hi % 4 == 0 && split % 4 == 0 && (al & 15) == 0) ? 4
-                       : (t.ldg % 2 == 0 && t.ldg_hi % 2 == 0 && split % 2 == 0 && (al & 7) == 0) ? 2 : 1;
-    ldmin = lm < ldmin ? lm : ldmin;
+    ldmin = std::min<int64_t>(ldmin, vec_width({t.ldg, t.ldg_hi, split}, {t.row_grads, t.row_grads_hi}));
     jobs.j[q] = AdamRowsJob{t.table, t.m, t.v, t.table_rows, t.sorted_ids, t.sorted_pos, t.row_grads, t.ldg, t.row_grads_hi, t.ldg_hi, t.hi_scale,
                             t.seg_ws, t.mark, t.last};
     if (t.th_lo && t.th_hi && t.last) {
-      const uintptr_t ta = reinterpret_cast<uintptr_t>(t.th_lo) | reinterpret_cast<uintptr_t>(t.th_hi);
-      const int64_t tm = (t.ld_th % 4 == 0 && (ta & 15) == 0) ? 4 : (t.ld_th % 2 == 0 && (ta & 7) == 0) ? 2 : 1;
-      th_min = tm < th_min ? tm : th_min;
+      th_min = std::min<int64_t>(th_min, vec_width({t.ld_th}, {t.th_lo, t.th_hi}));
       jobs.j[q].th0 = t.th_lo; jobs.j[q].ldt0 = t.ld_th; jobs.j[q].th1 = t.th_hi; jobs.j[q].ldt1 = t.ld_th;
     } else if (t.last) {
       all_stashed = false;
@@ -1324,8 +770,9 @@ static int adam_rows_launch(const AdamRowsArgs* a, int n_jobs, int dim, int id_t
   if (!with_partials)
     for (int q = 0; q < 2; ++q) jobs.j[q].part = nullptr;     // all tables or none
   const RowGeom g = row_geom_ld(dim, ldmin);
-  const int wvec0 = dim / 64;
-  const bool wave_ok = wave_rows_enabled() && dim % 64 == 0 && (wvec0 == 1 || wvec0 == 2 || wvec0 == 4) && ldmin >= wvec0 && th_min >= wvec0 && all_stashed;
+  // rows of 64 / 128 / 256 floats: one wave per row (deferred tables only with the lookup's replayed theta at hand)
+  const int wvec = wave_row_vec(dim);
+  const bool wave_ok = wave_rows_enabled() && wvec && ldmin >= wvec && th_min >= wvec && all_stashed;
   BR_CHECK_ARG(!per_job_n || wave_ok, "brAdamRowsSorted: tables of different lengths in one launch need the one-wave-per-row shapes");
   if (with_partials) {
     const int rc = launch_partials(segs, n_jobs, id_type, n_max, dim, g, split, (hipStream_t)stream);
@@ -1336,46 +783,34 @@ static int adam_rows_launch(const AdamRowsArgs* a, int n_jobs, int dim, int id_t
   AdamHp h = make_hp(alpha_t, beta1, beta2, eps);
   if (ss) h.alpha_ptr = &ss->alpha_t;
   probe_mark(s);
-  // rows of 64 / 128 / 256 floats: one wave per row (deferred tables only with the lookup's replayed theta at hand)
-  const int wvec = dim / 64;
-  if (wave_rows_enabled() && dim % 64 == 0 && (wvec == 1 || wvec == 2 || wvec == 4) && ldmin >= wvec && th_min >= wvec && all_stashed) {
+  // the keep-bit planes of the next step ride in either form of the launch: kf.blocks[i] workgroups for site i
+  KeepFuse kf;
+  kf.total = 0; kf.blocks[0] = kf.blocks[1] = kf.blocks[2] = 0; kf.a = KeepArgs{};
+  if (keep && keep->batch > 0) {
+    kf.a = *keep;
+    for (int i = 0; i < keep->n_sites; ++i) { kf.blocks[i] = (int)ceil_div(keep->batch * keep->s[i].kw, (int64_t)256); kf.total += kf.blocks[i]; }
+  }
+  if (wave_ok) {
     static const int strip = [] { const char* e = getenv("BR_ADAM_STRIP"); return e ? atoi(e) : 4; }();      // knob: 2, 4 (default), 8 - measured at the bench config: 92 / 85 / 115 us with riders
     AdamRiders rd;
-    rd.kf.total = 0; rd.kf.blocks[0] = rd.kf.blocks[1] = rd.kf.blocks[2] = 0; rd.kf.a = KeepArgs{};
+    rd.kf = kf;
     rd.n_final = 0;
-    if (keep && keep->batch > 0) {
-      rd.kf.a = *keep;
-      for (int i = 0; i < keep->n_sites; ++i) { rd.kf.blocks[i] = (int)ceil_div(keep->batch * keep->s[i].kw, (int64_t)256); rd.kf.total += rd.kf.blocks[i]; }
-    }
     if (fin) { rd.fin = *fin; rd.n_final = (int)ceil_div(fin->n, 64); } else { rd.fin = FinalArgs{}; }
     rd.total = rd.kf.total + rd.n_final;
     const int S = (strip == 2 || strip == 8) && wvec <= 2 ? strip : 4;
     rd.rows_x = (int)ceil_div(n_max, 4 * S);
     const unsigned wgrid = (unsigned)((int64_t)rd.rows_x * n_jobs + rd.total);
-#define BR_ADAM_WAVE(IdT, S_) BR_DISPATCH_VEC(wvec, (adam_rows_wave_kernel<IdT, VEC, S_><<<wgrid, 256, 0, s>>>(jobs, n, split, h, ss, rd)))
-    if (id_type == BR_IDS_I32) { if (S == 2) BR_ADAM_WAVE(int32_t, 2); else if (S == 8) BR_ADAM_WAVE(int32_t, 8); else BR_ADAM_WAVE(int32_t, 4); }
-    else { if (S == 2) BR_ADAM_WAVE(int64_t, 2); else if (S == 8) BR_ADAM_WAVE(int64_t, 8); else BR_ADAM_WAVE(int64_t, 4); }
+#define BR_ADAM_WAVE(S_) BR_DISPATCH_VEC(wvec, (adam_rows_wave_kernel<IdT, VEC, S_><<<wgrid, 256, 0, s>>>(jobs, n, split, h, ss, rd)))
+    BR_DISPATCH_ID(id_type, { if (S == 2) BR_ADAM_WAVE(2); else if (S == 8) BR_ADAM_WAVE(8); else BR_ADAM_WAVE(4); });
 #undef BR_ADAM_WAVE
     BR_CHECK_LAUNCH("brAdamRowsSorted(wave)");
     if (fin_done) *fin_done = fin != nullptr;
     return BR_OK;
   }
   for (int q = 0; q < 2; ++q) { jobs.j[q].th0 = jobs.j[q].th1 = nullptr; }
-  KeepFuse kf;
-  kf.total = 0; kf.blocks[0] = kf.blocks[1] = kf.blocks[2] = 0;
-  int keep_x = 0;
-  if (keep && keep->batch > 0) {
-    kf.a = *keep;
-    for (int i = 0; i < keep->n_sites; ++i) { kf.blocks[i] = (int)ceil_div(keep->batch * keep->s[i].kw, (int64_t)256); kf.total += kf.blocks[i]; }
-    keep_x = (int)ceil_div((int64_t)kf.total, (int64_t)n_jobs);
-  } else {
-    kf.a = KeepArgs{};
-  }
+  const int keep_x = (int)ceil_div((int64_t)kf.total, (int64_t)n_jobs);
   const dim3 grid((unsigned)(ceil_div(n, 256 >> g.lpr_log2) + keep_x), (unsigned)n_jobs);
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (adam_rows_sorted_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(jobs, dim, g.chunks, g.lpr_log2, n, split, h, ss, kf, keep_x)));
-  else
-    BR_DISPATCH_VEC(g.vec, (adam_rows_sorted_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(jobs, dim, g.chunks, g.lpr_log2, n, split, h, ss, kf, keep_x)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (adam_rows_sorted_kernel<IdT, VEC><<<grid, 256, 0, s>>>(jobs, dim, g.chunks, g.lpr_log2, n, split, h, ss, kf, keep_x))));
   BR_CHECK_LAUNCH("brAdamRowsSorted");
   return BR_OK;
 }
@@ -1417,11 +852,10 @@ extern "C" int brAdamRowsSortedPair(float* table_a, float* m_a, float* v_a, int6
                                     const float* grads_b, int64_t ldg_b, const float* grads_hi_b, int64_t ldg_hi_b, uint8_t* mark_b, int32_t* last_b,
                                     int dim, int id_type, int64_t n, int split, const float* hi_scale, const void* step_state, double alpha_t,
                                     double beta1, double beta2, double eps, float* seg_ws_a, float* seg_ws_b, brStream stream) {
-  BR_CHECK_ARG((last_a == nullptr) == (last_b == nullptr) && (last_a == nullptr || step_state), "brAdamRowsSortedPair: last arrays for both tables (with step_state) or neither");
-  BR_CHECK_ARG(grads_hi_a && grads_hi_b, "brAdamRowsSortedPair: both gradient halves required");
-  const AdamRowsArgs a[2] = {{table_a, m_a, v_a, rows_a, sorted_ids_a, sorted_pos_a, grads_a, ldg_a, grads_hi_a, ldg_hi_a, mark_a, last_a, seg_ws_a, hi_scale},
-                             {table_b, m_b, v_b, rows_b, sorted_ids_b, sorted_pos_b, grads_b, ldg_b, grads_hi_b, ldg_hi_b, mark_b, last_b, seg_ws_b, hi_scale}};
-  return adam_rows_launch(a, 2, dim, id_type, n, split, alpha_t, beta1, beta2, eps, last_a ? (const StepStateDev*)step_state : nullptr, stream);
+  const AdamPairCall c{table_a, m_a, v_a, rows_a, sorted_ids_a, sorted_pos_a, grads_a, ldg_a, grads_hi_a, ldg_hi_a, mark_a, last_a,
+                       table_b, m_b, v_b, rows_b, sorted_ids_b, sorted_pos_b, grads_b, ldg_b, grads_hi_b, ldg_hi_b, mark_b, last_b,
+                       dim, id_type, n, split, hi_scale, step_state, alpha_t, beta1, beta2, eps, seg_ws_a, seg_ws_b};
+  return adam_rows_pair_keep(c, nullptr, stream);
 }
 
 extern "C" int brAdamRowsSortedPairReplayed(float* table_a, float* m_a, float* v_a, int64_t rows_a, const void* sorted_ids_a, const int32_t* sorted_pos_a,
@@ -1519,14 +953,8 @@ extern "C" int brAdagradRowsSorted(float* table, float* acc, int64_t table_rows,
     const int rc = launch_partials(&job, 1, id_type, n, dim, g, dim, s);
     if (rc != BR_OK) return rc;
   }
-  if (id_type == BR_IDS_I32)
-    BR_DISPATCH_VEC(g.vec, (adagrad_rows_sorted_kernel<int32_t, VEC><<<grid, 256, 0, s>>>(
-                               table, acc, table_rows, dim, g.chunks, g.lpr_log2, (const int32_t*)sorted_ids, sorted_pos, n,
-                               row_grads, ldg, (float)lr, (float)eps, seg_ws)));
-  else
-    BR_DISPATCH_VEC(g.vec, (adagrad_rows_sorted_kernel<int64_t, VEC><<<grid, 256, 0, s>>>(
-                               table, acc, table_rows, dim, g.chunks, g.lpr_log2, (const int64_t*)sorted_ids, sorted_pos, n,
-                               row_grads, ldg, (float)lr, (float)eps, seg_ws)));
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (adagrad_rows_sorted_kernel<IdT, VEC><<<grid, 256, 0, s>>>(table, acc, table_rows, dim, g.chunks, g.lpr_log2, (const IdT*)sorted_ids,
+                                                                                                         sorted_pos, n, row_grads, ldg, (float)lr, (float)eps, seg_ws))));
   BR_CHECK_LAUNCH("brAdagradRowsSorted");
   return BR_OK;
 }
@@ -1536,252 +964,5 @@ extern "C" int brAdagradFlat(float* theta, float* acc, const float* g, int64_t n
   BR_CHECK_ARG(theta && acc && g && n > 0, "brAdagradFlat: bad args");
   adagrad_flat_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(theta, acc, g, n, (float)lr, (float)eps);
   BR_CHECK_LAUNCH("brAdagradFlat");
-  return BR_OK;
-}
-
-extern "C" int64_t brStepStateBytes(void) { return (int64_t)sizeof(StepStateDev); }
-
-extern "C" int brStepStateAdvance(void* step_state, double lr, double beta1, double beta2, double* zero, int64_t n_zero, brStream stream) {
-  BR_CHECK_ARG(step_state != nullptr && n_zero >= 0 && (zero || n_zero == 0), "brStepStateAdvance: bad args");
-  StepAdvance a;
-  a.st = (StepStateDev*)step_state; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.zero = zero; a.n_zero = n_zero;
-  step_state_advance_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a);
-  BR_CHECK_LAUNCH("brStepStateAdvance");
-  return BR_OK;
-}
-
-extern "C" int brStepStateInit(void* step_state, double beta1, double beta2, double eps, int replay_mode, brStream stream) {
-  BR_CHECK_ARG(step_state != nullptr, "brStepStateInit: null state");
-  BR_CHECK_ARG(replay_mode == BR_REPLAY_EXACT || replay_mode == BR_REPLAY_FAST, "brStepStateInit: bad replay_mode %d", replay_mode);
-  BR_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 > 0.0 && beta2 < 1.0 && eps >= 0.0, "brStepStateInit: beta1 in [0,1), beta2 in (0,1), eps >= 0");
-  constexpr size_t off = offsetof(StepStateDev, fast);
-  static_assert(offsetof(StepStateDev, pow2) + sizeof(float) * BR_ALPHA_RING == sizeof(StepStateDev), "StepStateDev tail layout");
-  std::vector<StepStateDev> img(1);                            // a host image of the state; only its tail [fast, end) is copied
-  StepStateDev* h = img.data();
-  // the kernels multiply by the fp32 roundings of beta1 / beta2 (AdamHp): the closed forms below are powers of THOSE numbers - over a lag of
-  // 1000 steps pow(0.999, k) and pow((float)0.999, k) are 1.3e-5 apart
-  beta1 = (double)(float)beta1; beta2 = (double)(float)beta2;
-  const double c = sqrt(beta2), rho = beta1 / c;
-  h->fast = replay_mode == BR_REPLAY_FAST ? 1u : 0u;
-  // theta is replayed over the first `trunc` steps of a lag: the steps behind it move theta by at most 7 rho^trunc / (1 - rho) of the first
-  // step's update (alpha_j varies by less than 7x over any lag, m decays by beta1 and 1 / d grows by at most 1 / c per step); below 2^-23
-  // of it they are under one ulp.  A multiple of 8 (the replay takes eight alphas per scalar load); rho >= 1: never truncated.
-  uint32_t trunc = BR_ALPHA_RING;
-  if (rho < 1.0) {
-    const double need = log(ldexp(1.0, -23) * (1.0 - rho) / 7.0) / log(rho);
-    if (need < (double)BR_ALPHA_RING) trunc = (uint32_t)((((int64_t)ceil(need < 1.0 ? 1.0 : need)) + 7) / 8 * 8);
-  }
-  h->trunc = trunc;
-  h->sqrt_b2 = (float)c;
-  h->eps_c = (float)(eps * (1.0 - c));
-  for (int k = 0; k < BR_ALPHA_RING; ++k) { h->pow1[k] = (float)pow(beta1, (double)k); h->pow2[k] = (float)pow(beta2, (double)k); }
-  const hipError_t ce = hipMemcpyAsync((char*)step_state + off, (const char*)h + off, sizeof(StepStateDev) - off, hipMemcpyHostToDevice, (hipStream_t)stream);
-  if (ce != hipSuccess) {
-    set_error("brStepStateInit: copy failed: %s", hipGetErrorString(ce));
-    return BR_ERR_HIP;
-  }
-  (void)hipStreamSynchronize((hipStream_t)stream);
-  return BR_OK;
-}
-
-extern "C" int brStepStateSet(void* step_state, uint32_t step, double lr, double beta1, double beta2, brStream stream) {
-  BR_CHECK_ARG(step_state != nullptr, "brStepStateSet: null state");
-  struct { uint32_t step; float alpha_t; double p1, p2; } h;
-  static_assert(sizeof(h) == offsetof(StepStateDev, alpha_hist), "StepStateDev head layout");
-  h.step = step;
-  h.p1 = pow(beta1, (double)step);
-  h.p2 = pow(beta2, (double)step);
-  const double tt = step > 0 ? (double)step : 1.0;
-  h.alpha_t = (float)(lr * sqrt(1.0 - pow(beta2, tt)) / (1.0 - pow(beta1, tt)));
-  // pageable source: hipMemcpyAsync returns after the copy has been staged, `h` may leave scope
-  const hipError_t ce = hipMemcpyAsync(step_state, &h, sizeof(h), hipMemcpyHostToDevice, (hipStream_t)stream);
-  if (ce != hipSuccess) {
-    set_error("brStepStateSet: copy failed: %s", hipGetErrorString(ce));
-    return BR_ERR_HIP;
-  }
-  (void)hipStreamSynchronize((hipStream_t)stream);
-  return BR_OK;
-}
-
-extern "C" int brStageBatch(void* dst_users, void* dst_items, float* dst_labels, const void* users, const void* items,
-                            const float* labels, int id_type, int64_t n, brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brStageBatch: bad id_type");
-  if (n == 0) return BR_OK;
-  BR_CHECK_ARG(dst_users && dst_items && users && items && n > 0, "brStageBatch: bad args");
-  const unsigned grid = (unsigned)ceil_div(n, 256);
-  if (id_type == BR_IDS_I32)
-    stage_batch_kernel<int32_t><<<grid, 256, 0, (hipStream_t)stream>>>((int32_t*)dst_users, (int32_t*)dst_items, dst_labels, (const int32_t*)users,
-                                                                        (const int32_t*)items, labels, n);
-  else
-    stage_batch_kernel<int64_t><<<grid, 256, 0, (hipStream_t)stream>>>((int64_t*)dst_users, (int64_t*)dst_items, dst_labels, (const int64_t*)users,
-                                                                        (const int64_t*)items, labels, n);
-  BR_CHECK_LAUNCH("brStageBatch");
-  return BR_OK;
-}
-
-// ---- row-sharded exchange planning (parallel.py ShardExchange.plan): owner(id) = id mod W --------------------------
-// One id stream: dest = id mod W -> stable sort of (dest, position) with the index machinery above -> order[j] = batch
-// position of bucket slot j, inv[b] = bucket slot of position b, send_local[j] = id div W in bucket order, counts[d] =
-// rows for owner d.  4 launches for a PAIR of equally long streams instead of ~10 torch ops per stream.
-template <typename IdT>
-__global__ __launch_bounds__(256) void shard_dest_kernel(const IdT* __restrict__ a, const IdT* __restrict__ b, IdT* __restrict__ da,
-                                                          IdT* __restrict__ db, int64_t n, int world) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const IdT* src = blockIdx.y ? b : a;
-  IdT* dst = blockIdx.y ? db : da;
-  const int64_t id = (int64_t)src[i];
-  const int64_t m = id % world;
-  dst[i] = (IdT)(m < 0 ? m + world : m);
-}
-
-struct ShardFinishJob { const void* ids; const void* sorted_dest; const int32_t* order; int32_t* inv; void* send_local; int64_t* counts; };
-struct ShardFinishJobs { ShardFinishJob j[2]; };
-
-template <typename IdT>
-__global__ __launch_bounds__(256) void shard_finish_kernel(ShardFinishJobs jobs, int64_t n, int world) {
-  const ShardFinishJob& jb = jobs.j[blockIdx.y];
-  const IdT* ids = (const IdT*)jb.ids;
-  const IdT* sd = (const IdT*)jb.sorted_dest;
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < n) {
-    const int32_t b = jb.order[j];
-    jb.inv[b] = (int32_t)j;
-    const int64_t id = (int64_t)ids[b];
-    const int64_t m = id % world;
-    ((IdT*)jb.send_local)[j] = (IdT)((id - (m < 0 ? m + world : m)) / world);      // floor division for every sign
-  }
-  if (j < world) {                                   // rows for owner j: [lower_bound(j), lower_bound(j + 1)) of the sorted dests
-    auto lb = [&](int64_t d) {
-      int64_t lo = 0, hi = n;
-      while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)sd[mid] < d) lo = mid + 1; else hi = mid; }
-      return lo;
-    };
-    jb.counts[j] = lb(j + 1) - lb(j);
-  }
-}
-
-// ---- fixed-capacity form of the exchange plan: every peer gets exactly `cap` slots per stream, so the all-to-alls have equal, static
-// splits and no row count ever crosses to the host.  Slot t = d * cap + k holds the k-th row for owner d (bucket order), pad slots
-// hold the owner's spare row (local index = its row count: the tables of a padded engine carry one extra row whose gradient is always 0).
-struct ShardPadJob {
-  const void* sorted_dest; const int32_t* order; const void* send_local; const int64_t* counts;
-  void* send_pad; int32_t* slot; int32_t* bpos; int64_t total_rows;
-  float* zero_rows; int zero_dim;      // optional [world*cap][zero_dim] buffer whose PAD rows are cleared (gradient send slots)
-};
-struct ShardPadJobs { ShardPadJob j[2]; };
-
-template <typename IdT>
-__global__ __launch_bounds__(256) void shard_pad_kernel(ShardPadJobs jobs, int64_t n, int world, int64_t cap, int* __restrict__ overflow) {
-  const ShardPadJob& jb = jobs.j[blockIdx.y];
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < n) {                                        // bucket position t -> its slot
-    const int64_t d = (int64_t)((const IdT*)jb.sorted_dest)[t];
-    int64_t off = 0;
-    for (int64_t q = 0; q < d; ++q) off += jb.counts[q];
-    int64_t k = t - off;
-    if (k >= cap) { atomicOr(overflow, BR_ERRFLAG_CAPACITY); k = cap - 1; }     // reported by the host's next flag check
-    const int64_t sl = d * cap + k;
-    const int32_t b = jb.order[t];
-    jb.slot[b] = (int32_t)sl;
-    if (t - off < cap) { ((IdT*)jb.send_pad)[sl] = ((const IdT*)jb.send_local)[t]; jb.bpos[sl] = b; }
-  }
-  if (t < (int64_t)world * cap) {                     // pad slots
-    const int64_t d = t / cap, k = t - d * cap;
-    if (k >= jb.counts[d]) {
-      const int64_t spare = jb.total_rows > d ? (jb.total_rows - d + world - 1) / world : 0;   // rows owner d holds = index of its spare row
-      ((IdT*)jb.send_pad)[t] = (IdT)spare;
-      jb.bpos[t] = -1;
-      if (jb.zero_rows)
-        for (int c = 0; c < jb.zero_dim; c += 4) *reinterpret_cast<float4*>(jb.zero_rows + t * jb.zero_dim + c) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-}
-
-extern "C" int brShardPadPair(const void* sorted_dest_a, const void* sorted_dest_b, const int32_t* order_a, const int32_t* order_b,
-                              const void* send_local_a, const void* send_local_b, const int64_t* counts_a, const int64_t* counts_b, int id_type,
-                              int64_t n, int world, int64_t cap, int64_t total_rows_a, int64_t total_rows_b, void* send_pad_a, void* send_pad_b,
-                              int32_t* slot_a, int32_t* slot_b, int32_t* bpos_a, int32_t* bpos_b, float* zero_a, float* zero_b, int zero_dim, int* err_flag,
-                              brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brShardPadPair: bad id_type");
-  BR_CHECK_ARG(!zero_a || (zero_dim >= 4 && zero_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(zero_a) & 15) == 0 && (reinterpret_cast<uintptr_t>(zero_b) & 15) == 0),
-               "brShardPadPair: zero rows need a dim that is a multiple of 4 and 16-byte alignment");
-  BR_CHECK_ARG(world >= 1 && world <= 256 && n >= 0 && cap >= 1 && err_flag, "brShardPadPair: bad world / n / cap / flag");
-  BR_CHECK_ARG(sorted_dest_a && order_a && send_local_a && counts_a && send_pad_a && slot_a && bpos_a, "brShardPadPair: null pointer (stream a)");
-  const int n_jobs = sorted_dest_b ? 2 : 1;
-  BR_CHECK_ARG(!sorted_dest_b || (order_b && send_local_b && counts_b && send_pad_b && slot_b && bpos_b), "brShardPadPair: null pointer (stream b)");
-  ShardPadJobs J;
-  J.j[0] = ShardPadJob{sorted_dest_a, order_a, send_local_a, counts_a, send_pad_a, slot_a, bpos_a, total_rows_a, zero_a, zero_dim};
-  J.j[1] = sorted_dest_b ? ShardPadJob{sorted_dest_b, order_b, send_local_b, counts_b, send_pad_b, slot_b, bpos_b, total_rows_b, zero_b, zero_dim} : J.j[0];
-  const int64_t m = n > (int64_t)world * cap ? n : (int64_t)world * cap;
-  const dim3 g((unsigned)ceil_div(m, 256), (unsigned)n_jobs);
-  if (id_type == BR_IDS_I32) shard_pad_kernel<int32_t><<<g, 256, 0, (hipStream_t)stream>>>(J, n, world, cap, err_flag);
-  else shard_pad_kernel<int64_t><<<g, 256, 0, (hipStream_t)stream>>>(J, n, world, cap, err_flag);
-  BR_CHECK_LAUNCH("brShardPadPair");
-  return BR_OK;
-}
-
-// dst[t] = bpos[t] >= 0 ? src[bpos[t]] : 0 for one or two (src, bpos, dst) sets of equal shape: per-pair rows -> padded send slots
-struct PadRowsJob { const float* src; int64_t ld; const int32_t* bpos; float* dst; };
-struct PadRowsJobs { PadRowsJob j[2]; };
-__global__ __launch_bounds__(256) void rows_to_slots_kernel(PadRowsJobs jobs, int64_t n_slots, int dim) {
-  const PadRowsJob& jb = jobs.j[blockIdx.y];
-  const int q4 = dim >> 2;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_slots * q4) return;
-  const int64_t t = i / q4;
-  const int c = (int)(i - t * q4) << 2;
-  const int32_t b = jb.bpos[t];
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (b >= 0) v = *reinterpret_cast<const float4*>(jb.src + (int64_t)b * jb.ld + c);
-  *reinterpret_cast<float4*>(jb.dst + t * dim + c) = v;
-}
-
-extern "C" int brRowsToSlotsPair(const float* src_a, const float* src_b, int64_t ld, const int32_t* bpos_a, const int32_t* bpos_b, float* dst_a,
-                                 float* dst_b, int64_t n_slots, int dim, brStream stream) {
-  BR_CHECK_ARG(src_a && bpos_a && dst_a && n_slots >= 0 && dim >= 4 && dim % 4 == 0 && ld >= dim && ld % 4 == 0, "brRowsToSlotsPair: bad args (dim, ld multiples of 4)");
-  BR_CHECK_ARG(((reinterpret_cast<uintptr_t>(src_a) | reinterpret_cast<uintptr_t>(dst_a) | reinterpret_cast<uintptr_t>(src_b) | reinterpret_cast<uintptr_t>(dst_b)) & 15) == 0,
-               "brRowsToSlotsPair: rows must be 16-byte aligned");
-  BR_CHECK_ARG(!src_b || (bpos_b && dst_b), "brRowsToSlotsPair: null pointer (set b)");
-  if (n_slots == 0) return BR_OK;
-  PadRowsJobs J;
-  J.j[0] = PadRowsJob{src_a, ld, bpos_a, dst_a};
-  J.j[1] = src_b ? PadRowsJob{src_b, ld, bpos_b, dst_b} : J.j[0];
-  const dim3 g((unsigned)ceil_div(n_slots * (dim >> 2), 256), src_b ? 2u : 1u);
-  rows_to_slots_kernel<<<g, 256, 0, (hipStream_t)stream>>>(J, n_slots, dim);
-  BR_CHECK_LAUNCH("brRowsToSlotsPair");
-  return BR_OK;
-}
-
-extern "C" int brShardPlanPair(const void* ids_a, const void* ids_b, int id_type, int64_t n, int world, void* dest_a, void* dest_b,
-                               void* sorted_dest_a, void* sorted_dest_b, int32_t* order_a, int32_t* order_b, void* ws_a, void* ws_b,
-                               int64_t ws_bytes, int32_t* inv_a, int32_t* inv_b, void* send_local_a, void* send_local_b,
-                               int64_t* counts_a, int64_t* counts_b, brStream stream) {
-  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brShardPlanPair: bad id_type");
-  BR_CHECK_ARG(world >= 1 && world <= 256 && n >= 0, "brShardPlanPair: bad world / n");
-  const int n_jobs = ids_b ? 2 : 1;
-  BR_CHECK_ARG(ids_a && dest_a && sorted_dest_a && order_a && ws_a && inv_a && send_local_a && counts_a, "brShardPlanPair: null pointer (stream a)");
-  BR_CHECK_ARG(!ids_b || (dest_b && sorted_dest_b && order_b && ws_b && inv_b && send_local_b && counts_b), "brShardPlanPair: null pointer (stream b)");
-  hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    (void)hipMemsetAsync(counts_a, 0, sizeof(int64_t) * world, s);
-    if (ids_b) (void)hipMemsetAsync(counts_b, 0, sizeof(int64_t) * world, s);
-    return BR_OK;
-  }
-  const dim3 g((unsigned)ceil_div(n, 256), (unsigned)n_jobs);
-  if (id_type == BR_IDS_I32) shard_dest_kernel<int32_t><<<g, 256, 0, s>>>((const int32_t*)ids_a, (const int32_t*)ids_b, (int32_t*)dest_a, (int32_t*)dest_b, n, world);
-  else shard_dest_kernel<int64_t><<<g, 256, 0, s>>>((const int64_t*)ids_a, (const int64_t*)ids_b, (int64_t*)dest_a, (int64_t*)dest_b, n, world);
-  BR_CHECK_LAUNCH("brShardPlanPair(dest)");
-  int rc;
-  if (ids_b) rc = brRowIndexBuildPair(dest_a, world, sorted_dest_a, order_a, ws_a, ws_bytes, dest_b, world, sorted_dest_b, order_b, ws_b, ws_bytes, id_type, n, stream);
-  else rc = brRowIndexBuild(dest_a, id_type, n, world, sorted_dest_a, order_a, ws_a, ws_bytes, stream);
-  if (rc != BR_OK) return rc;
-  ShardFinishJobs J;
-  J.j[0] = ShardFinishJob{ids_a, sorted_dest_a, order_a, inv_a, send_local_a, counts_a};
-  J.j[1] = ids_b ? ShardFinishJob{ids_b, sorted_dest_b, order_b, inv_b, send_local_b, counts_b} : J.j[0];
-  const dim3 g2((unsigned)ceil_div(n > world ? n : world, 256), (unsigned)n_jobs);
-  if (id_type == BR_IDS_I32) shard_finish_kernel<int32_t><<<g2, 256, 0, s>>>(J, n, world);
-  else shard_finish_kernel<int64_t><<<g2, 256, 0, s>>>(J, n, world);
-  BR_CHECK_LAUNCH("brShardPlanPair(finish)");
   return BR_OK;
 }
