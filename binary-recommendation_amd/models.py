@@ -511,9 +511,16 @@ class TwoTowerModel:
                  rdZero=False, resKey=None, semb=100, device="cuda:0", max_batch=65536, learningRate=0.1, optimiser="Adagrad"):
         self.userKey, self.itemKey, self.resKey, self.rdZero, self.eval_batch_size = userKey, itemKey, resKey, rdZero, eval_batch_size
         self.userTowerIn, self.itemTowerIn = StringLookup(usersId), StringLookup(itemsId)
-        self.engine = TwoTowerEngine(embedDim, nbrItem, nbrUser, semb, device, max_batch, lr=learningRate, optimizer=optimiser, rd_zero=rdZero)
+        ctx = _dist_ctx()
+        if ctx is not None:      # under a process group the tables are row-sharded over the ranks (as NeuMFModel / BPRModel.compileModel)
+            from .parallel import make_sharded_two_tower
+            self.engine = make_sharded_two_tower(TwoTowerEngine)(embedDim, nbrItem, nbrUser, semb, _rank_device(device, ctx), max_batch, ctx,
+                                                                 lr=learningRate, optimizer=optimiser, rd_zero=rdZero)
+        else:
+            self.engine = TwoTowerEngine(embedDim, nbrItem, nbrUser, semb, device, max_batch, lr=learningRate, optimizer=optimiser, rd_zero=rdZero)
+        self._owners = ctx is not None       # candidates stay with the ranks that own their rows (engine.recommend, a collective)
         self.device = self.engine.device
-        self._cand, self._cand_ids, self._k = None, None, None
+        self._cand, self._cand_ids, self._cand_idx, self._k = None, None, None, None
         self._loss_seen = torch.zeros((), dtype=torch.float64, device=self.device)
 
     def _ids(self, info):
@@ -586,13 +593,18 @@ class TwoTowerModel:
     def setCandidates(self, items, k):
         """BruteForce(k).index(itemTower(items), identifiers=items) (twoTower.py:64-69)."""
         self._cand_ids = list(items)
-        self._cand = self.engine.item_tower(self.itemTowerIn(self._cand_ids, self.device))
+        self._cand_idx = self.itemTowerIn(self._cand_ids, self.device)
+        # (row-sharded engine: no rank indexes the whole candidate list; every owner applies the item tower to its own candidates per query)
+        self._cand = None if self._owners else self.engine.item_tower(self._cand_idx)
         self._k = k
 
     def call(self, users):
         """userTower -> BruteForce top-k (twoTower.py:60-62) -> (scores (U,k), identifiers (U,k))."""
-        q = self.engine.user_tower(self.userTowerIn(users, self.device))
-        ts, ti = ops.topk_rows(ops.score_matrix(q, self._cand), self._k)
+        if self._owners:
+            ts, ti = self.engine.recommend(self.userTowerIn(users, self.device), self._k, self._cand_idx)
+        else:
+            q = self.engine.user_tower(self.userTowerIn(users, self.device))
+            ts, ti = ops.topk_rows(ops.score_matrix(q, self._cand), self._k)
         ids = np.asarray(self._cand_ids, dtype=object)[ti.cpu().numpy()]
         return ts.cpu().numpy(), ids
 
@@ -605,6 +617,10 @@ class TwoTowerModel:
         if method not in ("matrix", "fused"):
             raise ValueError(f"method must be 'matrix' or 'fused', got {method!r}")
         self.setCandidates(itemsId, k)
+        if self._owners:
+            if method != "fused":
+                raise ValueError("topk on a row-sharded engine: method='fused' (the users x items matrix is never formed on one rank)")
+            return self.engine.recommend(self.userTowerIn(usersId, self.device), k, self._cand_idx, exclude=exclude)
         q = self.engine.user_tower(self.userTowerIn(usersId, self.device))
         if method == "fused":
             return ops.dot_catalog_topk(q, self._cand, k, exclude=exclude)

@@ -642,10 +642,8 @@ class NeuMFEngine(RowAdam):
         launch scores, masks and selects (csrc/recommend.hip).  items: the candidate ids (None: every item row); exclude: (off, idx)
         CSR over `users` of candidate POSITIONS never to return (ops.truth_csr; topk_metrics.seen_csr maps raw ids).
         -> (scores (U, k) float32, index (U, k) int32 positions into `items`) on the device, best first, ties to the lower position;
-        slots past the remaining candidates are (-inf, -1).  dump_logits=True also returns every pair's head logit (U x I)."""
-        if self.sharded:
-            raise NotImplementedError("recommend() on the row-sharded engine is not supported: the catalogue scoring needs every table "
-                                      "row on one device (DESIGN.md §7); score with a single-device engine")
+        slots past the remaining candidates are (-inf, -1).  dump_logits=True also returns every pair's head logit (U x I).
+        (The row-sharded engine overrides this with a collective of the same contract: parallel.py recommend_at_owners.)"""
         cfg, dev = self.cfg, self.device
         D, (n1, n2, n3) = cfg.dim, cfg.hidden
         self.flush()                         # deferred-Adam rows lag until then (as _infer)

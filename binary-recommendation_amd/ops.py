@@ -717,6 +717,67 @@ def dot_catalog_topk(Q, C, k, exclude=None, dump_scores=False):
     return (os_, oi, dump) if dump_scores else (os_, oi)
 
 
+# ------------------------------------------------------------------------------ shard-local lists -> one list (csrc/recommend_merge.hip)
+def _i32_dev(t, name: str):
+    if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous int32 device tensor, got {t.dtype} {t.device}")
+    return t
+
+
+def csr_split_by_owner(off, idx, g2l):
+    """(off int64 (rows + 1), idx int32): a CSR of ascending positions into a global candidate list; g2l int32 (n_global): global
+    position -> this owner's local position or -1 -> (out_off (rows + 1), out_idx): the rows restricted to this owner's candidates in
+    local positions (brCsrSplitByOwner).  out_idx keeps the input's capacity: only its first out_off[-1] entries mean anything (no
+    host sync here to cut it)."""
+    n_rows = off.shape[0] - 1
+    off, idx = _csr((off, idx), n_rows, "csr")
+    _i32_dev(g2l, "g2l")
+    lib = _lib.load()
+    ws_bytes = int(lib.brCsrSplitByOwnerWorkspaceBytes(n_rows))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=off.device)
+    out_off = torch.empty(n_rows + 1, dtype=torch.int64, device=off.device)
+    out_idx = torch.empty(max(idx.numel(), 1), dtype=torch.int32, device=off.device)
+    check(lib.brCsrSplitByOwner(off.data_ptr(), idx.data_ptr(), n_rows, _p(g2l) if g2l.numel() else out_idx.data_ptr(), g2l.numel(),
+                                out_off.data_ptr(), out_idx.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "brCsrSplitByOwner")
+    return out_off, out_idx
+
+
+def topk_lists_merge(scores, index, n_lists: int, n_users: int, k: int, l2g, l2g_off, list_stride=None, user_stride=None):
+    """scores float32 / index int32: n_lists lists of k (score, local position) entries per user, entry e of list w of user u at element
+    [w * list_stride + u * user_stride + e] (defaults: the (n_lists, n_users, k) stack of n_lists launches); l2g int32 / l2g_off int64
+    (n_lists + 1): list w's local position l is global position l2g[l2g_off[w] + l], ascending per list -> (scores (n_users, k),
+    index (n_users, k) int32 GLOBAL positions): the k best of the union, ties to the lower global position, (-inf, -1) past the
+    entries there are (brTopKListsMerge)."""
+    k, n_lists, n_users = int(k), int(n_lists), int(n_users)
+    if not 1 <= k <= 256:
+        raise ValueError(f"k = {k}: 1 <= k <= 256")
+    user_stride = k if user_stride is None else int(user_stride)
+    list_stride = n_users * user_stride if list_stride is None else int(list_stride)
+    if scores.dtype != torch.float32 or not scores.is_cuda:
+        raise TypeError("topk_lists_merge: scores must be a float32 device tensor")
+    if index.dtype != torch.int32 or not index.is_cuda:
+        raise TypeError("topk_lists_merge: index must be an int32 device tensor")
+    if n_users:
+        last = (n_lists - 1) * list_stride + (n_users - 1) * user_stride + k       # one past the last element the kernel reads
+        for t, name in ((scores, "scores"), (index, "index")):
+            if not t.is_contiguous() and t.dim() != 2:
+                raise TypeError(f"topk_lists_merge: {name} must be contiguous or a column slice of a 2-D buffer")
+            room = t.numel() if t.is_contiguous() else (t.shape[0] - 1) * t.stride(0) + t.shape[1]
+            if room < last:
+                raise ValueError(f"topk_lists_merge: {name} holds {room} elements, the strides reach {last}")
+    if l2g_off.dtype != torch.int64 or not l2g_off.is_cuda or not l2g_off.is_contiguous() or l2g_off.numel() != n_lists + 1:
+        raise TypeError(f"topk_lists_merge: l2g_off must be a contiguous int64 device tensor of {n_lists + 1} entries")
+    _i32_dev(l2g, "l2g")
+    dev = scores.device
+    os_ = torch.empty(n_users, k, dtype=torch.float32, device=dev)
+    oi = torch.empty(n_users, k, dtype=torch.int32, device=dev)
+    if l2g.numel() == 0:           # a valid pointer for an empty map
+        l2g = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(_lib.load().brTopKListsMerge(scores.data_ptr(), index.data_ptr(), list_stride, user_stride, n_lists, n_users, k, l2g.data_ptr(),
+                                       l2g_off.data_ptr(), os_.data_ptr(), oi.data_ptr(), _stream()), "brTopKListsMerge")
+    return os_, oi
+
+
 # ------------------------------------------------------------------------------ dot-product catalogue AUC (csrc/auc_dot.hip)
 def dot_catalog_auc(Q, C, truth_off, truth_idx, dump_scores=False):
     """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim), truth (ops.truth_csr over the rows of Q: ascending

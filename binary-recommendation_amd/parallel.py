@@ -328,6 +328,118 @@ def load_sharded(engine, path, rank: int, world: int, global_rows: dict):
     engine.load_state_dict(fit(sd))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Catalogue top-k scored where the item rows live.  The candidate rows never travel: every rank scores the queries
+# of ALL ranks against the candidates it owns with the single-device fused launch, the k-entry lists go back to the rank that
+# asked, and brTopKListsMerge merges each user's W lists under the launch's own order - bit for bit the single-device lists.
+# ---------------------------------------------------------------------------------------------------------------------
+def gather_global_rows(ctx: DistCtx, ids: torch.Tensor, serve, width: int):
+    """rows `ids` (global ids, any owner) of a row-sharded table -> (len(ids), width) on this rank, through the id -> owner exchange
+    of the training step; serve(local_rows) -> the owner's rows.  A collective."""
+    from . import ops
+    x = ShardExchange(ctx)
+    if ids.numel():
+        x.plan(ids)
+    else:                                   # nothing to ask for, but the peers' requests are still served: the empty plan
+        x.order = x.inv = torch.empty(0, dtype=torch.int32, device=ids.device)
+        x.send_local, x.send_counts_t = ids, torch.zeros(ctx.world, dtype=torch.int64, device=ids.device)
+    x.exchange_counts()
+    served = x.send_ids()
+    empty = torch.empty(0, width, dtype=torch.float32, device=ids.device)
+    back = x.return_rows(serve(served) if served.numel() else empty)            # bucket order
+    return ops.gather_rows([back], [x.inv.to(ids.dtype)])[0] if ids.numel() else empty
+
+
+def _all_gather_ragged(ctx: DistCtx, t: torch.Tensor, counts):
+    """rank r contributes counts[r] rows of t's shape -> the rows of all ranks, rank after rank (padded to the longest for the
+    collective, the pads dropped again)."""
+    if ctx.local:
+        return t
+    m = max(counts)
+    pad = torch.zeros((m,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    pad[:t.shape[0]].copy_(t)
+    g = ctx.all_gather_rows(pad)
+    return torch.cat([g[r * m:r * m + c] for r, c in enumerate(counts)]) if m else g
+
+
+def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, exclude, fetch_user_rows, queries_of, candidates_of, score):
+    """The single-device `recommend` contract on row-sharded tables.  A collective, like predict_scores: every rank calls it with
+    its own `users` (device ids; counts may differ and may be 0), the SAME `items` (device ids in any order, None = every item row)
+    and optionally an exclusion CSR (off, idx) over its own users in positions of `items`; it gets (scores (U_r, k) float32,
+    index (U_r, k) int32 positions into `items`) for its users.  The engine supplies
+      fetch_user_rows(ids) -> this rank's users' table rows (the id -> owner exchange, gather_global_rows)
+      queries_of(rows)     -> the query rows the fused launch reads, from the user rows of ALL ranks
+      candidates_of(local) -> the candidate operand of the launch from this rank's own item rows `local` (ids div W)
+      score(q, c, k, excl) -> (scores, index) of the fused launch over q x c."""
+    from . import ops
+    W, r, dev = ctx.world, ctx.rank, users.device
+    k = int(k)
+    if not 1 <= k <= 256:
+        raise ValueError(f"k = {k}: 1 <= k <= 256")
+    if items is None:
+        items = torch.arange(n_item_rows, dtype=users.dtype, device=dev)
+    U, I = users.shape[0], items.shape[0]
+    if I < 1:
+        raise ValueError("recommend: empty candidate list")
+    has_ex = exclude is not None
+    if has_ex:
+        ex_off, ex_idx = ops._csr(exclude, U, "exclude")
+        ex_idx = ex_idx[:int(exclude[1].numel())]
+    # what every rank must know about the others, in ONE small all-gather and one host sync: user and exclusion counts, and that the
+    # candidate lists agree (length, k and a position-weighted checksum of the ids)
+    it64 = items.to(torch.int64)
+    fp = (it64 * (torch.arange(I, device=dev, dtype=torch.int64) % 65521 + 1)).sum()
+    meta = torch.tensor([[U, int(exclude[1].numel()) if has_ex else -1, I, k, 0]], dtype=torch.int64).to(dev)
+    meta[0, 4] = fp
+    meta = ctx.all_gather_rows(meta).cpu().tolist()
+    if any(m[2:] != meta[0][2:] for m in meta):
+        raise ValueError("recommend on a row-sharded engine: every rank must pass the same items and k "
+                         f"(rank {r} sees (len, k, checksum) = {[m[2:] for m in meta]})")
+    u_counts, e_counts = [int(m[0]) for m in meta], [int(m[1]) for m in meta]
+    U_all = sum(u_counts)
+    if U_all == 0:
+        return torch.empty(0, k, dtype=torch.float32, device=dev), torch.empty(0, k, dtype=torch.int32, device=dev)
+    # 1. the queries of all ranks on every rank
+    rows_all = _all_gather_ragged(ctx, fetch_user_rows(users), u_counts)
+    q_all = queries_of(rows_all)
+    # 2. this rank's candidates: positions p with items[p] mod W == rank in ascending p (the plan's bucket order is the W ascending
+    #    local -> global maps one after the other), local row items[p] div W
+    plan = ShardExchange(ctx).plan(items)
+    l2g = plan.order.to(torch.int32).contiguous()
+    l2g_off = torch.zeros(W + 1, dtype=torch.int64, device=dev)
+    l2g_off[1:] = plan.send_counts_t.to(torch.int64).cumsum(0)
+    lo, hi = (int(v) for v in l2g_off[r:r + 2].cpu().tolist())
+    n_loc = hi - lo
+    # 3. the exclusion lists of all ranks on every rank.  The two all-gathers depend only on what the meta gather told every rank, never on
+    #    this rank's own candidates: a rank that owns none of `items` still takes part in them
+    csr_all = None
+    if any(c >= 0 for c in e_counts):
+        lens = (ex_off[1:] - ex_off[:-1]) if has_ex else torch.zeros(U, dtype=torch.int64, device=dev)
+        idx = ex_idx if has_ex else torch.empty(0, dtype=torch.int32, device=dev)
+        off_all = torch.zeros(U_all + 1, dtype=torch.int64, device=dev)
+        off_all[1:] = _all_gather_ragged(ctx, lens, u_counts).cumsum(0)
+        csr_all = (off_all, _all_gather_ragged(ctx, idx, [max(c, 0) for c in e_counts]).contiguous())
+    if n_loc:
+        cand = candidates_of(plan.send_local[lo:hi].contiguous())
+        excl = None
+        if csr_all is not None:          # cut down to this rank's candidates, in its local positions
+            g2l = torch.full((I,), -1, dtype=torch.int32, device=dev)
+            g2l[l2g[lo:hi].long()] = torch.arange(n_loc, dtype=torch.int32, device=dev)
+            excl = ops.csr_split_by_owner(csr_all[0], csr_all[1], g2l)
+        s_loc, p_loc = score(q_all, cand, k, excl)
+    else:                        # no candidate of the list lives here: empty lists for everybody
+        s_loc = torch.full((U_all, k), float("-inf"), dtype=torch.float32, device=dev)
+        p_loc = torch.full((U_all, k), -1, dtype=torch.int32, device=dev)
+    # 4. [score bits | positions] of every user back to its rank in one all-to-all, then the merge reads the receive buffer in place:
+    #    list w of user u at row w * U + u
+    send = torch.cat([s_loc.view(torch.int32), p_loc], dim=1)
+    recv = torch.empty(W * U, 2 * k, dtype=torch.int32, device=dev)
+    ctx.all_to_all(recv, send, [U] * W, u_counts)
+    if U == 0:
+        return torch.empty(0, k, dtype=torch.float32, device=dev), torch.empty(0, k, dtype=torch.int32, device=dev)
+    return ops.topk_lists_merge(recv.view(torch.float32), recv[:, k:], W, U, k, l2g, l2g_off, list_stride=U * 2 * k, user_stride=2 * k)
+
+
 def make_sharded_engine(base_cls):
     """ShardedNeuMFEngine = NeuMFEngine with its embed / table-optimizer hooks replaced by the
     row-sharded exchange.  (Factory so this module stays importable without the HIP library.)"""
@@ -540,6 +652,37 @@ def make_sharded_engine(base_cls):
             self.sync_moving_stats()
             return super()._infer(users, items, labels, n)
 
+        def recommend(self, users, k, items=None, exclude=None, dump_logits=None):
+            """NeuMFEngine.recommend on the row-sharded tables (recommend_at_owners): a collective - every rank calls it with its own
+            users (any number, also none), the same `items` and k, and gets the single-device lists of ITS users bit for bit.  Every
+            owner projects and scores only the items whose rows it holds; user rows travel out, k-entry lists travel back."""
+            if dump_logits:
+                raise NotImplementedError("recommend(dump_logits=True) on the row-sharded engine is not supported: no rank forms the "
+                                          "logits of another owner's items; score with a single-device engine")
+            cfg, dev = self.cfg, self.device
+            D, (n1, n2, n3) = cfg.dim, cfg.hidden
+            self.flush()                         # deferred-Adam rows lag until then (as _infer)
+            self.sync_moving_stats()
+            users = torch.as_tensor(users, device=dev)
+            if users.dtype not in (torch.int32, torch.int64):
+                users = users.to(self.id_dtype)
+            if items is not None:
+                items = torch.as_tensor(items, device=dev)
+                items = (items if items.dtype == users.dtype else items.to(users.dtype)).contiguous()
+            th = {name: self.theta.view(name) for name in self.theta.offsets}
+            tower = ops.neumf_catalog_fold(th, self.moving, n1, n2, n3, cfg.mf_first, cfg.bn_eps)
+
+            def queries_of(rows):
+                ar = torch.arange(rows.shape[0], dtype=torch.int32, device=dev)
+                return ops.neumf_catalog_project(rows, ar, th["W1"], n1, D, cfg.item_first, True, b1=th["b1"], err_flag=self.err)
+
+            return recommend_at_owners(
+                self.ctx, users.contiguous(), items, self.num_item_rows, k, exclude,
+                lambda ids: gather_global_rows(self.ctx, ids, lambda loc: ops.gather_rows([self.fused["user"]], [loc], err_flag=self.err)[0], 2 * D),
+                queries_of,
+                lambda loc: ops.neumf_catalog_project(self.fused["item"], loc, th["W1"], n1, D, cfg.item_first, False, col_major=True, err_flag=self.err),
+                lambda q, c, kk, ex: ops.neumf_catalog_topk(q, c, tower, D, (n1, n2, n3), cfg.act, kk, exclude=ex))
+
         def _embed_backward_apply(self, users, items, B):
             cfg, D = self.cfg, self.cfg.dim
             if self.exchange == "padded":
@@ -629,6 +772,26 @@ def make_sharded_two_tower(base_cls):
             gi = ops.gather_rows([self.item_emb], [ri], err_flag=self.err)[0] if ri.numel() else empty
             bu, bi = xu.return_rows(gu), xi.return_rows(gi)                      # bucket order
             ops.gather_rows([bu, bi], [xu.inv.to(self.id_dtype), xi.inv.to(self.id_dtype)], [self.eu[:B], self.ei[:B]])
+
+        def _tower(self, rows, tower):
+            out = torch.empty(rows.shape[0], self.S, device=self.device)
+            Wt, bt = self.W(tower)
+            ops.dense_forward(rows, Wt, bt, out, "linear")
+            return out
+
+        def recommend(self, users, k, items=None, exclude=None):
+            """TwoTowerEngine.recommend on the row-sharded tables (recommend_at_owners): a collective - every rank calls it with its own
+            users (any number, also none), the same `items` (None: every row of the item table) and k, and gets the single-device
+            lists of ITS users bit for bit.  Every owner applies the item tower to the candidates whose rows it holds only."""
+            users = users.contiguous()
+            if items is not None:
+                items = (items if items.dtype == users.dtype else items.to(users.dtype)).contiguous()
+            return recommend_at_owners(
+                self.ctx, users, items, self.item_rows_global, k, exclude,
+                lambda ids: gather_global_rows(self.ctx, ids, lambda loc: ops.gather_rows([self.user_emb], [loc], err_flag=self.err)[0], self.E),
+                lambda rows: self._tower(rows, "user"),
+                lambda loc: self._tower(ops.gather_rows([self.item_emb], [loc], err_flag=self.err)[0], "item"),
+                lambda q, c, kk, ex: ops.dot_catalog_topk(q, c, kk, exclude=ex))
 
         def _softmax(self, q, c, items, B, dq, dc):
             ctx = self.ctx
@@ -763,6 +926,25 @@ def make_sharded_bpr(base_cls):
                 items = torch.arange(self.num_items_global, device=self.device)
             it = self._gather_global("item", items.to(self.id_dtype))
             return u, it
+
+        def recommend(self, users, k, items=None, exclude=None, dump_scores=False, catalog="gather"):
+            """BPREngine.recommend as a collective.  catalog="gather" (default): every candidate row is pulled to every rank
+            (_catalog_rows) and each rank scores its users alone; "owners": every rank scores the users of ALL ranks against the
+            candidates whose rows it holds and the k-entry lists are merged (recommend_at_owners) - the same lists bit for bit, with
+            U x dim user rows and U x W x k list entries on the wire instead of I x dim candidate rows per rank."""
+            if catalog not in ("gather", "owners"):
+                raise ValueError(f"catalog must be 'gather' or 'owners', got {catalog!r}")
+            if catalog == "gather":
+                return super().recommend(users, k, items=items, exclude=exclude, dump_scores=dump_scores)
+            if dump_scores:
+                raise NotImplementedError("recommend(catalog='owners', dump_scores=True): no rank forms the scores of another owner's items")
+            users, items = self._recommend_ids(users, items)
+            self.flush()                         # deferred-Adam rows lag until then
+            rows_of = lambda name: (lambda loc: ops.gather_rows([getattr(self, "_" + name)], [loc], err_flag=self.err)[0])
+            return recommend_at_owners(self.ctx, users, items, self.num_items_global, k, exclude,
+                                       lambda ids: gather_global_rows(self.ctx, ids, rows_of("user"), self.dim),
+                                       lambda rows: rows, rows_of("item"),
+                                       lambda q, c, kk, ex: ops.dot_catalog_topk(q, c, kk, exclude=ex))
 
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 

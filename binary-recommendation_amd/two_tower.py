@@ -138,6 +138,16 @@ class TwoTowerEngine:
         ops.dense_forward(e, Wu, bu, out, "linear")
         return out
 
+    def recommend(self, users, k, items=None, exclude=None):
+        """The k best of the candidates `items` (StringLookup indices; None: every row of the item table) for every user of `users` by
+        the dot of the tower outputs, in one fused launch (ops.dot_catalog_topk) -> (scores (U, k) float32, index (U, k) int32 positions
+        into `items`), best first, ties to the lower position; exclude: (off, idx) CSR over `users` of positions never returned,
+        (-inf, -1) past the remaining candidates.  The row-sharded engine (parallel.py) overrides this with a collective of the
+        same contract."""
+        if items is None:
+            items = torch.arange(self.item_emb.shape[0], dtype=users.dtype, device=self.device)
+        return ops.dot_catalog_topk(self.user_tower(users), self.item_tower(items), k, exclude=exclude)
+
     def enable_graph(self, batch: int | None = None):
         """Replay the step for batches of exactly `batch` pairs as ONE hipGraph (the eager step is ~20 launches from the Python host with
         gaps between them: 0.48 ms at batch 8 192, of which the kernels take 0.40).  Adagrad, single GPU: then no per-step scalar is baked

@@ -486,6 +486,35 @@ int brDotCatalogAuc(const float* Q, int64_t ld_q, int64_t n_users, const float* 
                     const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, void* ws, int64_t ws_bytes,
                     brStream stream);
 
+/* ---- Catalogue top-k on row-sharded engines, scored where the item rows live: csrc/recommend_merge.hip ----------------------------
+ * W owners each run brNeumfCatalogTopK / brDotCatalogTopK over the candidates whose rows they hold (parallel.py recommend_at_owners);
+ * these two turn the W shard-local answers into the answer of ONE launch over the whole candidate list, entry for entry.  The reference
+ * has no counterpart: MultiWorkerMirroredStrategy (src/models/RModel.py:119) mirrors every table on every worker, so its predictForUser
+ * (src/models/NeuMFModel.py:133-150) and topKRatings (trainers/topKmetrics.py:17-43) score the whole catalogue on each worker.
+ * brCsrSplitByOwner: stands in for re-deriving every owner's seen-item lists on the host.  (off (n_rows + 1) int64, idx int32): the
+ *   exclusion CSR of brTopKRowsExclude over the GLOBAL candidate list (ascending positions per row); g2l (n_global) int32: global
+ *   position -> this owner's local position, or -1 where another owner holds the candidate.  -> (out_off (n_rows + 1), out_idx): the
+ *   rows restricted to this owner's candidates, in local positions, in their input order (so ascending when g2l is ascending over the
+ *   positions it keeps).  out_idx needs room for off[n_rows] entries (the kept ones are not known to the host).  Positions outside
+ *   [0, n_global) are dropped.  Integer arithmetic in a fixed order (count per row, prefix sum over the rows, scatter): no float
+ *   atomics, and the output does not depend on the launch shape.  ws: brCsrSplitByOwnerWorkspaceBytes(n_rows) bytes (the per-row counts).
+ *   Limits: n_global < 2^31; BR_ERR_ARG / BR_ERR_WORKSPACE before any launch.
+ * brTopKListsMerge: stands in for the final merge of brNeumfCatalogTopK / brDotCatalogTopK (their item splits -> one list) one level up:
+ *   per user n_lists lists of k entries (score, LOCAL position), entry e of list w of user u at [w * list_stride + u * user_stride + e]
+ *   of scores / index (so the concatenated outputs of n_lists launches, or the receive buffer of one all-to-all, are read in place);
+ *   list w's local position l is global position l2g[l2g_off[w] + l] (l2g_off: n_lists + 1 int64, device), every map ascending, so a
+ *   list's order is the global order.  -> out_scores / out_index (n_users x k): the k best (score, GLOBAL position) of the union,
+ *   descending, ties to the LOWER global position, strict '>' - the one compare of brTopKRows and of the catalogue kernels, NaN scores
+ *   treated as that compare treats them (they never enter a list).  Entries with position -1 (a shard with fewer than k candidates
+ *   left) or outside their map never win and are never used as an index; where fewer than k entries exist over all lists the tail is
+ *   (-inf, -1).  One wave per user, no workspace.  Limits: 1 <= k <= 256, 1 <= n_lists <= 4096, user_stride >= k; BR_ERR_ARG before any
+ *   launch. */
+int64_t brCsrSplitByOwnerWorkspaceBytes(int64_t n_rows);
+int brCsrSplitByOwner(const int64_t* off, const int32_t* idx, int64_t n_rows, const int32_t* g2l, int64_t n_global, int64_t* out_off,
+                      int32_t* out_idx, void* ws, int64_t ws_bytes, brStream stream);
+int brTopKListsMerge(const float* scores, const int32_t* index, int64_t list_stride, int64_t user_stride, int n_lists, int64_t n_users,
+                     int k, const int32_t* l2g, const int64_t* l2g_off, float* out_scores, int32_t* out_index, brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the
