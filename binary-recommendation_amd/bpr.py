@@ -208,22 +208,23 @@ class BPREngine(RowAdam):
 
     def recommend(self, users, k, items=None, exclude=None, dump_scores=False):
         """The k best items of every user of `users` by the dot score predict_scores returns, without the U x I matrix: one fused
-        launch scores, masks and selects (ops.dot_catalog_topk, csrc/recommend_dot.hip).  items: the candidate ids (None: the item
+        launch scores, masks and selects (ops.dot_catalog_topk, csrc/recommend_dot.hip; rows wider than 128 features:
+        ops.dot_catalog_topk_wide, csrc/recommend_dot_wide.hip, up to 512).  items: the candidate ids (None: the item
         table in place); exclude: (off, idx) CSR over `users` of candidate POSITIONS never to return (topk_metrics.seen_csr).
         -> (scores (U, k) float32, index (U, k) int32 positions into `items`) on the device, best first, ties to the lower position;
         slots past the remaining candidates are (-inf, -1).  Ids outside the tables set self.err (check_ids raises).  On the row-sharded
         engine (parallel.py) this is a collective: every rank calls it and gets the lists of ITS users."""
         q, c = self._catalog_rows(users, items)
-        return ops.dot_catalog_topk(q, c, k, exclude=exclude, dump_scores=dump_scores)
+        return ops.dot_topk_for(q.shape[1])(q, c, k, exclude=exclude, dump_scores=dump_scores)
 
     def full_auc(self, users, truth, items=None, dump_scores=False):
         """Per-user full AUC (src/models/bpr.py:230-254) of the dot scores predict_scores returns, without the U x I matrix: the fused
-        launches of ops.dot_catalog_auc (csrc/auc_dot.hip).  truth: (off, idx) CSR over `users` of candidate POSITIONS, ascending
-        (ops.truth_csr); items: the candidate ids (None: the item table in place).  -> float32 (U,) on the device, NaN for a user
+        launches of ops.dot_catalog_auc (csrc/auc_dot.hip; rows wider than 128 features: ops.dot_catalog_auc_wide).  truth: (off, idx)
+        CSR over `users` of candidate POSITIONS, ascending (ops.truth_csr); items: the candidate ids (None: the item table in place).  -> float32 (U,) on the device, NaN for a user
         without positives or without negatives.  Ids outside the tables set self.err (check_ids raises).  On the row-sharded engine
         (parallel.py) this is a collective: every rank calls it and gets the AUCs of ITS users."""
         q, c = self._catalog_rows(users, items)
-        return ops.dot_catalog_auc(q, c, truth[0], truth[1], dump_scores=dump_scores)
+        return ops.dot_auc_for(q.shape[1])(q, c, truth[0], truth[1], dump_scores=dump_scores)
 
     def _catalog_rows(self, users, items):
         """-> (the rows of `users`, the rows of `items` or the item table in place) that recommend / full_auc score (row-sharded

@@ -1,4 +1,4 @@
-// What the dot-product catalogue kernels (recommend_dot.hip: top-k, auc_dot.hip: AUC) share outside their tile loops: the split
+// What the dot-product catalogue kernels (recommend_dot.hip: top-k, auc_dot.hip: AUC, and their _wide forms) share outside their tile loops: the split
 // plan (recommend.hip's too), wave_lds_order and what the two entry points check and choose alike.  The tile loop itself is still
 // written out in both kernels and kept the same by hand: see DESIGN.md 4e "One copy of the tile loop".
 #pragma once
@@ -42,9 +42,12 @@ void dispatch_kb(int dim, F&& f) {
   else f(std::integral_constant<int, 32>{});
 }
 
-// the checks both entry points make on (Q, C); `name`: the entry point, for the message
-int dot_check_args(const char* name, int64_t ld_q, int64_t n_users, int64_t ld_c, int64_t n_items, int dim) {
-  BR_CHECK_ARG(dim >= 1 && dim <= 128, "%s: dim = %d outside [1, 128]", name, dim);
+constexpr int kDotMaxDim = 128;            // widest rows of the whole-row kernels (recommend_dot.hip, auc_dot.hip)
+constexpr int kDotWideMaxDim = 512;        // ... of the block kernels (recommend_dot_wide.hip, auc_dot_wide.hip)
+
+// the checks the entry points make on (Q, C); `name`: the entry point, for the message
+int dot_check_args(const char* name, int64_t ld_q, int64_t n_users, int64_t ld_c, int64_t n_items, int dim, int max_dim = kDotMaxDim) {
+  BR_CHECK_ARG(dim >= 1 && dim <= max_dim, "%s: dim = %d outside [1, %d]", name, dim, max_dim);
   BR_CHECK_ARG(n_users >= 0 && n_items >= 1 && n_items < ((int64_t)1 << 31), "%s: bad sizes (1 <= n_items < 2^31)", name);
   BR_CHECK_ARG(ld_q >= dim && ld_c >= dim, "%s: ld_q, ld_c >= dim (got %lld, %lld, dim %d)", name, (long long)ld_q, (long long)ld_c, dim);
   return BR_OK;

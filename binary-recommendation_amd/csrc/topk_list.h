@@ -97,6 +97,49 @@ struct WaveList {
   }
 };
 
+// Insert (cs, cp) (wave-uniform) into the k-entry list S/P in LDS (entry e at S[e]; lane holds entries lane + 64 r) unless it does
+// not make the list.  Returns the new k-th entry through ts/tp (unchanged when the candidate is rejected).
+template <int SLOTS>
+__device__ void list_insert(float* S, int32_t* P, int k, int lane, float cs, int32_t cp, float& ts, int32_t& tp) {
+  float s[SLOTS];
+  int32_t p[SLOTS];
+  int pos = 0;
+#pragma unroll
+  for (int r = 0; r < SLOTS; ++r) {
+    const int e = r * 64 + lane;
+    s[r] = e < k ? S[e] : -INFINITY;
+    p[r] = e < k ? P[e] : kNoPos;
+    pos += __popcll(__ballot(e < k && beats(s[r], p[r], cs, cp)));
+  }
+  if (pos >= k) return;                            // (every store below depends on pos, so all loads above come first)
+  float ps[SLOTS];
+  int32_t pp[SLOTS];
+#pragma unroll
+  for (int r = 0; r < SLOTS; ++r) {                // entry e - 1 of the old list: lane - 1 of the same slot, or lane 63 of the slot before
+    const float up_s = __shfl_up(s[r], 1, 64);
+    const int32_t up_p = __shfl_up(p[r], 1, 64);
+    const float wr_s = r ? __shfl(s[r - 1], 63, 64) : -INFINITY;
+    const int32_t wr_p = r ? __shfl(p[r - 1], 63, 64) : kNoPos;
+    ps[r] = lane ? up_s : wr_s;
+    pp[r] = lane ? up_p : wr_p;
+  }
+#pragma unroll
+  for (int r = 0; r < SLOTS; ++r) {
+    const int e = r * 64 + lane;
+    if (e < k) {
+      if (e == pos) { S[e] = cs; P[e] = cp; s[r] = cs; p[r] = cp; }
+      else if (e > pos) { S[e] = ps[r]; P[e] = pp[r]; s[r] = ps[r]; p[r] = pp[r]; }
+    }
+  }
+  const int last = k - 1, slot = last >> 6;
+  float ls = s[0];
+  int32_t lp = p[0];
+#pragma unroll
+  for (int r = 1; r < SLOTS; ++r) if (r == slot) { ls = s[r]; lp = p[r]; }   // (no runtime register indexing)
+  ts = __shfl(ls, last & 63, 64);
+  tp = __shfl(lp, last & 63, 64);
+}
+
 // one wave per user: the n_splits lists of k entries -> the final top-k
 __global__ __launch_bounds__(256) void catalog_merge_kernel(const float* __restrict__ part_s, const int32_t* __restrict__ part_p,
                                                              int64_t n_users, int64_t n_splits, int k, float* __restrict__ out_s,

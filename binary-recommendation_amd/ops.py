@@ -679,8 +679,13 @@ def _rows_f32(t, name: str):
     return t
 
 
-def _dot_catalog_args(who: str, Q, C, k=None):
-    """the checks dot_catalog_topk / dot_catalog_auc (`who`) make on Q, C (and k) -> (U, I, dim, ld_q, ld_c, device)"""
+DOT_MAX_DIM = 128          # widest rows of dot_catalog_topk / dot_catalog_auc (the whole-row kernels)
+DOT_WIDE_MAX_DIM = 512     # ... of dot_catalog_topk_wide / dot_catalog_auc_wide (the block kernels)
+
+
+def _dot_catalog_args(who: str, Q, C, k=None, max_dim=DOT_MAX_DIM):
+    """the checks dot_catalog_topk / dot_catalog_auc and their _wide forms (`who`) make on Q, C (and k) -> (U, I, dim, ld_q, ld_c,
+    device)"""
     for t, name in ((Q, "Q"), (C, "C")):
         if not isinstance(t, torch.Tensor) or t.dim() != 2:
             raise ValueError(f"{who}: {name} must be a 2-D tensor")
@@ -688,8 +693,8 @@ def _dot_catalog_args(who: str, Q, C, k=None):
     I = C.shape[0]
     if C.shape[1] != dim:
         raise ValueError(f"{who}: Q has dim {dim}, C has {C.shape[1]}")
-    if not 1 <= dim <= 128:
-        raise ValueError(f"{who}: dim = {dim}: 1 <= dim <= 128")
+    if not 1 <= dim <= max_dim:
+        raise ValueError(f"{who}: dim = {dim}: 1 <= dim <= {max_dim}")
     if k is not None and not 1 <= int(k) <= 256:
         raise ValueError(f"k = {k}: 1 <= k <= 256")
     _rows_f32(Q, "Q"); _rows_f32(C, "C")
@@ -796,6 +801,55 @@ def dot_catalog_auc(Q, C, truth_off, truth_idx, dump_scores=False):
     check(lib.brDotCatalogAuc(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
                               ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogAuc")
     return (out, dump) if dump_scores else out
+
+
+# ------------------------------------------------------------------------------ wide rows (csrc/recommend_dot_wide.hip, auc_dot_wide.hip)
+def dot_catalog_topk_wide(Q, C, k, exclude=None, dump_scores=False, force_wide=False):
+    """dot_catalog_topk for 1 <= dim <= 512 (brDotCatalogTopKWide): the same arguments, results and score contract.  dim <= 128 runs
+    dot_catalog_topk's launches unless force_wide, which sends those rows through the block kernels too (same bits: tests)."""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_topk_wide", Q, C, k, DOT_WIDE_MAX_DIM)
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotCatalogTopKWideWorkspaceBytes(U, I, dim, int(k)))
+    if ws_bytes < 0:
+        raise ValueError(f"dot_catalog_topk_wide: bad sizes U={U} I={I} k={k}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    os_ = torch.empty(U, k, dtype=torch.float32, device=dev)
+    oi = torch.empty(U, k, dtype=torch.int32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    off, idx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
+    flags = _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
+    check(lib.brDotCatalogTopKWide(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(),
+                                   _p(dump), flags, ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogTopKWide")
+    return (os_, oi, dump) if dump_scores else (os_, oi)
+
+
+def dot_catalog_auc_wide(Q, C, truth_off, truth_idx, dump_scores=False, force_wide=False):
+    """dot_catalog_auc for 1 <= dim <= 512 (brDotCatalogAucWide): the same arguments, results and score contract.  dim <= 128 runs
+    dot_catalog_auc's launches unless force_wide, which sends those rows through the block kernels too (same bits: tests)."""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_auc_wide", Q, C, None, DOT_WIDE_MAX_DIM)
+    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
+    off, idx = _csr((truth_off, truth_idx), U, "truth")
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotCatalogAucWideWorkspaceBytes(U, I, dim, n_truth))
+    if ws_bytes < 0:
+        raise ValueError(f"dot_catalog_auc_wide: bad sizes U={U} I={I}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.float32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    flags = _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
+    check(lib.brDotCatalogAucWide(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
+                                  flags, ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogAucWide")
+    return (out, dump) if dump_scores else out
+
+
+def dot_topk_for(dim: int):
+    """the catalogue top-k op the engines call at row width `dim`: the whole-row op up to 128 features exactly as before, the wide op
+    above"""
+    return dot_catalog_topk if dim <= DOT_MAX_DIM else dot_catalog_topk_wide
+
+
+def dot_auc_for(dim: int):
+    return dot_catalog_auc if dim <= DOT_MAX_DIM else dot_catalog_auc_wide
 
 
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts

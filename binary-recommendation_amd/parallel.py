@@ -944,7 +944,7 @@ def make_sharded_bpr(base_cls):
             return recommend_at_owners(self.ctx, users, items, self.num_items_global, k, exclude,
                                        lambda ids: gather_global_rows(self.ctx, ids, rows_of("user"), self.dim),
                                        lambda rows: rows, rows_of("item"),
-                                       lambda q, c, kk, ex: ops.dot_catalog_topk(q, c, kk, exclude=ex))
+                                       lambda q, c, kk, ex: ops.dot_topk_for(self.dim)(q, c, kk, exclude=ex))
 
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 

@@ -486,6 +486,32 @@ int brDotCatalogAuc(const float* Q, int64_t ld_q, int64_t n_users, const float* 
                     const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, void* ws, int64_t ws_bytes,
                     brStream stream);
 
+/* ---- Catalogue top-k and AUC for wide rows (BPR at the reference's latent_dim = 350): csrc/recommend_dot_wide.hip, auc_dot_wide.hip -----
+ * brDotCatalogTopK / brDotCatalogAuc for 1 <= dim <= 512: the same stand-ins (bpr_predict, src/models/bpr.py:122-133, with
+ * full_auc and mean_average_precision_k, bpr.py:230-289, over the whole U x I matrix, which is never stored), the same arguments and
+ * the same contract: score(u, i) = sum_j Q[u][j] C[i][j] in fp32, features in natural order, one fmaf chain from 0 over the
+ * instantiated width (zero padded), so a pair's score depends on its two rows only.
+ * brDotCatalogTopKWide: bpr.py:122-133, :257-289.  dim <= 128 without BR_DOT_FORCE_WIDE: the launches of brDotCatalogTopK (same kernels,
+ *   same plan, same bits).  dim > 128, or BR_DOT_FORCE_WIDE in flags: the block kernels - the item rows stream through LDS 128 features
+ *   at a time and the accumulators are carried from block to block (no per-block partial sums), so the scores are those the whole-row
+ *   kernel would give: at dim <= 128 both paths return the same bits.  Selection, exclusion, dump_scores and the (-inf, -1) tails as
+ *   in brDotCatalogTopK.  Limits: 1 <= dim <= 512, otherwise those of brDotCatalogTopK; flags other than BR_DOT_FORCE_WIDE are
+ *   BR_ERR_ARG.  ws: brDotCatalogTopKWideWorkspaceBytes(n_users, n_items, dim, k) bytes (enough for either path at that dim); -1 for
+ *   sizes outside the limits.
+ * brDotCatalogAucWide: bpr.py:122-133, :230-254.  The same switch for brDotCatalogAuc: the positives are scored over the same padded width
+ *   and chain as the catalogue pass, the Mann-Whitney count is summed in integers and divided once in double, so out_auc equals
+ *   brFullAuc on the same scores bit for bit.  ws: brDotCatalogAucWideWorkspaceBytes(n_users, n_items, dim, truth_off[n_users]) bytes.
+ *   BR_ERR_ARG / BR_ERR_WORKSPACE before any launch, as the narrow entries. */
+enum { BR_DOT_FORCE_WIDE = 1 };
+int64_t brDotCatalogTopKWideWorkspaceBytes(int64_t n_users, int64_t n_items, int dim, int k);
+int brDotCatalogTopKWide(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                         const int64_t* excl_off, const int32_t* excl_idx, int k, float* out_scores, int32_t* out_index,
+                         float* dump_scores, int flags, void* ws, int64_t ws_bytes, brStream stream);
+int64_t brDotCatalogAucWideWorkspaceBytes(int64_t n_users, int64_t n_items, int dim, int64_t n_truth);
+int brDotCatalogAucWide(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                        const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, int flags, void* ws,
+                        int64_t ws_bytes, brStream stream);
+
 /* ---- Catalogue top-k on row-sharded engines, scored where the item rows live: csrc/recommend_merge.hip ----------------------------
  * W owners each run brNeumfCatalogTopK / brDotCatalogTopK over the candidates whose rows they hold (parallel.py recommend_at_owners);
  * these two turn the W shard-local answers into the answer of ONE launch over the whole candidate list, entry for entry.  The reference
