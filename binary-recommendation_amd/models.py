@@ -399,13 +399,19 @@ class BPRModel(RModel):
         it = _to_dev(np.asarray(items), e.device, e.id_dtype)
         return e.predict_scores(u, it)                                   # bpr_predict (bpr.py:122-133) for all users at once
 
-    def full_auc(self, ground_truth, items, method="matrix") -> float:
+    def full_auc(self, ground_truth, items, method="matrix", catalog=None) -> float:
         """full_auc (src/models/bpr.py:230-254): mean over the users that have positives of roc_auc_score(ground truth over all
         `items`, bpr_predict scores).  ground_truth: iterable of (user_id, [true item ids]).
         method="matrix": score_matrix + brFullAuc (the default); "fused": BPREngine.full_auc, the same per-user values without the
-        users x items matrix."""
+        users x items matrix.  catalog (method="fused" on a row-sharded engine, i.e. under a process group): "gather" pulls the candidate
+        rows to every rank, "owners" counts where they live (ShardedBPREngine.full_auc) - the same float; None: the engine's default."""
         if method not in ("matrix", "fused"):
             raise ValueError(f"method must be 'matrix' or 'fused', got {method!r}")
+        if catalog not in (None, "gather", "owners"):
+            raise ValueError(f"catalog must be None, 'gather' or 'owners', got {catalog!r}")
+        sharded = hasattr(self.model, "ctx")
+        if catalog == "owners" and (method != "fused" or not sharded):
+            raise ValueError("catalog='owners' needs method='fused' on a row-sharded engine (a model compiled under a process group)")
         gt = list(ground_truth)
         col = {it: j for j, it in enumerate(items)}
         missing = [p for _u, t in gt for p in t if p not in col]
@@ -417,7 +423,7 @@ class BPRModel(RModel):
         if method == "fused":
             e = self.model
             auc = e.full_auc(_to_dev(np.asarray([u for u, _ in gt]), e.device, e.id_dtype), (off, idx),
-                             items=_to_dev(np.asarray(items), e.device, e.id_dtype))
+                             items=_to_dev(np.asarray(items), e.device, e.id_dtype), **({"catalog": catalog} if sharded and catalog else {}))
             e.check_ids()
             auc = auc.cpu().numpy()
         else:

@@ -852,6 +852,105 @@ def dot_auc_for(dim: int):
     return dot_catalog_auc if dim <= DOT_MAX_DIM else dot_catalog_auc_wide
 
 
+# ------------------------------------------------------------------------------ catalogue AUC counted at the item owners (csrc/auc_owner.hip)
+# dot_catalog_auc[_wide] in four phases, for W owners that each hold a share of the candidates (parallel.auc_at_owners).
+# force_wide as in dot_catalog_auc_wide; the positives and the count of one evaluation take the same value.
+def _wide_flags(force_wide) -> int:
+    return _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
+
+
+def dot_auc_owner_positives(Q, C, pos_off, pos_idx, out=None, force_wide=False):
+    """Q (U x dim), C (I_loc x dim): this owner's candidate rows; (pos_off, pos_idx): per user its positives among them in LOCAL
+    positions (csr_split_by_owner) -> raw float32: raw[pos_off[u] + j] = the catalogue pass's score of the user's j-th entry, NaN for a
+    position outside C.  out: a float32 device buffer of at least pos_off[-1] entries (default: one of pos_idx's capacity)."""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_auc_owner_positives", Q, C, None, DOT_WIDE_MAX_DIM)
+    n_cap = pos_idx.numel() if isinstance(pos_idx, torch.Tensor) else 0
+    off, idx = _csr((pos_off, pos_idx), U, "positives")
+    out = torch.empty(max(n_cap, 1), dtype=torch.float32, device=dev) if out is None else out
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise TypeError("dot_auc_owner_positives: out must be a contiguous float32 device tensor")
+    check(_lib.load().brDotAucOwnerPositives(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(),
+                                             _wide_flags(force_wide), _stream()), "brDotAucOwnerPositives")
+    return out
+
+
+def auc_sort_pieces(raw, piece_off, list_off, cap: int):
+    """raw float32 (any shape, contiguous), piece_off int64 (n_pieces, U + 1): piece w of user u is raw.view(-1)[piece_off[w, u] :
+    piece_off[w, u + 1]]; list_off int64 (U + 1) -> (sorted float32 (cap + 1), pcnt int32 (U,)): per user the entries of all its pieces
+    ascending at sorted[list_off[u]:], NaN dropped, their number in pcnt[u]; -1 for a user whose list lies past `cap` or whose pieces
+    do not fit it (brAucSortPieces).  The pieces' order does not matter."""
+    if raw.dtype != torch.float32 or not raw.is_cuda or not raw.is_contiguous():
+        raise TypeError("auc_sort_pieces: raw must be a contiguous float32 device tensor")
+    for t, name in ((piece_off, "piece_off"), (list_off, "list_off")):
+        if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+            raise TypeError(f"auc_sort_pieces: {name} must be a contiguous int64 device tensor")
+    n_users = list_off.shape[0] - 1
+    if piece_off.dim() != 2 or piece_off.shape[1] != n_users + 1:
+        raise ValueError(f"auc_sort_pieces: piece_off must be (n_pieces, {n_users + 1})")
+    n_pieces, cap, dev = piece_off.shape[0], int(cap), raw.device
+    lib = _lib.load()
+    ws_bytes = int(lib.brAucSortPiecesWorkspaceBytes(n_pieces, cap))
+    if ws_bytes < 0:
+        raise ValueError(f"auc_sort_pieces: n_pieces = {n_pieces}: 1 <= n_pieces <= 4096 (cap = {cap} >= 0)")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    sorted_ = torch.empty(cap + 1, dtype=torch.float32, device=dev)
+    pcnt = torch.empty(max(n_users, 1), dtype=torch.int32, device=dev)[:n_users]
+    check(lib.brAucSortPieces(raw.data_ptr() if raw.numel() else sorted_.data_ptr(), raw.numel(), piece_off.data_ptr(), n_pieces, n_users,
+                              list_off.data_ptr(), sorted_.data_ptr(), cap, pcnt.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+          "brAucSortPieces")
+    return sorted_, pcnt
+
+
+def dot_auc_owner_count(Q, C, skip_off, skip_idx, list_off, sorted_, pcnt, dump_scores=False, force_wide=False):
+    """Q (U x dim), C (I_loc x dim): this owner's candidate rows; (skip_off, skip_idx): its positives per user, ascending LOCAL positions;
+    list_off / sorted_ / pcnt of auc_sort_pieces: every user's FULL list -> per user the integer 2W over these candidates, int64 (U,)
+    (the library's uint64: below 2^63 while P N < 2^62) [, every pair's score (U, I_loc)] (brDotAucOwnerCount)."""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_auc_owner_count", Q, C, None, DOT_WIDE_MAX_DIM)
+    off, idx = _csr((skip_off, skip_idx), U, "skip")
+    if list_off.dtype != torch.int64 or not list_off.is_cuda or not list_off.is_contiguous() or list_off.numel() != U + 1:
+        raise TypeError(f"dot_auc_owner_count: list_off must be a contiguous int64 device tensor of {U + 1} entries")
+    if sorted_.dtype != torch.float32 or not sorted_.is_cuda or not sorted_.is_contiguous() or sorted_.numel() < 1:
+        raise TypeError("dot_auc_owner_count: sorted_ must be a non-empty contiguous float32 device tensor")
+    _i32_dev(pcnt, "pcnt")
+    if pcnt.numel() != U:
+        raise ValueError(f"dot_auc_owner_count: pcnt has {pcnt.numel()} entries for {U} users")
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotAucOwnerCountWorkspaceBytes(U, I, dim))
+    if ws_bytes < 0:
+        raise ValueError(f"dot_auc_owner_count: bad sizes U={U} I={I}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.int64, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    check(lib.brDotAucOwnerCount(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), list_off.data_ptr(),
+                                 sorted_.data_ptr(), pcnt.data_ptr() if U else sorted_.data_ptr(), sorted_.numel() - 1, out.data_ptr() if U else sorted_.data_ptr(),
+                                 _p(dump), _wide_flags(force_wide), ws.data_ptr(), ws_bytes, _stream()), "brDotAucOwnerCount")
+    return (out, dump) if dump_scores else out
+
+
+def auc_finalize_lists(part, n_lists: int, n_users: int, truth_off, pcnt, n_items: int, list_stride=None):
+    """part int64: n_lists partial 2W per user, list w of user u at part.view(-1)[w * list_stride + u] (default stride n_users: the
+    stack of n_lists counts, or the receive buffer of one all-to-all); truth_off int64 (n_users + 1): the GLOBAL truth offsets; pcnt of
+    auc_sort_pieces for these users; n_items: the length of the whole candidate list -> AUC float32 (n_users,), NaN where undefined
+    (brAucFinalizeLists)."""
+    n_lists, n_users = int(n_lists), int(n_users)
+    list_stride = n_users if list_stride is None else int(list_stride)
+    if part.dtype != torch.int64 or not part.is_cuda or not part.is_contiguous():
+        raise TypeError("auc_finalize_lists: part must be a contiguous int64 device tensor")
+    if n_users and n_lists >= 1 and part.numel() < (n_lists - 1) * list_stride + n_users:
+        raise ValueError(f"auc_finalize_lists: part holds {part.numel()} entries, the strides reach {(n_lists - 1) * list_stride + n_users}")
+    if truth_off.dtype != torch.int64 or not truth_off.is_cuda or not truth_off.is_contiguous() or truth_off.numel() != n_users + 1:
+        raise TypeError(f"auc_finalize_lists: truth_off must be a contiguous int64 device tensor of {n_users + 1} entries")
+    _i32_dev(pcnt, "pcnt")
+    if pcnt.numel() != n_users:
+        raise ValueError(f"auc_finalize_lists: pcnt has {pcnt.numel()} entries for {n_users} users")
+    out = torch.empty(n_users, dtype=torch.float32, device=part.device)
+    valid = truth_off.data_ptr()           # a valid pointer where a tensor is empty
+    check(_lib.load().brAucFinalizeLists(part.data_ptr() if part.numel() else valid, list_stride, n_lists, truth_off.data_ptr(),
+                                         pcnt.data_ptr() if n_users else valid, n_users, int(n_items), out.data_ptr() if n_users else valid,
+                                         _stream()), "brAucFinalizeLists")
+    return out
+
+
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts
 def truth_csr(n_users: int, user_rows, item_cols, device):
     """Ground truth of `n_users` rows as the CSR the eval kernels take: (offsets int64 (n_users + 1), column indices int32 ascending

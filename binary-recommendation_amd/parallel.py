@@ -362,6 +362,55 @@ def _all_gather_ragged(ctx: DistCtx, t: torch.Tensor, counts):
     return torch.cat([g[r * m:r * m + c] for r, c in enumerate(counts)]) if m else g
 
 
+def _owners_meta(ctx: DistCtx, what: str, n_users: int, n_csr: int, items, k: int):
+    """What every rank of an owner-side catalogue collective must know about the others, in ONE small all-gather and one host sync: the
+    user and CSR entry counts (n_csr = -1: this rank passes no CSR), and that the candidate lists agree (length, k and a
+    position-weighted checksum of the ids; a mismatch raises on every rank) -> (user counts, CSR counts) per rank."""
+    I, dev = items.shape[0], items.device
+    fp = (items.to(torch.int64) * (torch.arange(I, device=dev, dtype=torch.int64) % 65521 + 1)).sum()
+    meta = torch.tensor([[n_users, n_csr, I, k, 0]], dtype=torch.int64).to(dev)
+    meta[0, 4] = fp
+    meta = ctx.all_gather_rows(meta).cpu().tolist()
+    if any(m[2:] != meta[0][2:] for m in meta):
+        raise ValueError(f"{what} on a row-sharded engine: every rank must pass the same items and k "
+                         f"(rank {ctx.rank} sees (len, k, checksum) = {[m[2:] for m in meta]})")
+    return [int(m[0]) for m in meta], [int(m[1]) for m in meta]
+
+
+def _all_gather_csr(ctx: DistCtx, off, idx, n_users: int, u_counts, c_counts):
+    """the per-user CSRs (off, idx) of all ranks -> one CSR over the users of all ranks, rank after rank (off None: this rank has no
+    lists, its users get empty ones).  Depends only on what the meta gather told every rank: a rank without users or candidates still
+    takes part."""
+    dev = idx.device
+    lens = (off[1:] - off[:-1]) if off is not None else torch.zeros(n_users, dtype=torch.int64, device=dev)
+    off_all = torch.zeros(sum(u_counts) + 1, dtype=torch.int64, device=dev)
+    off_all[1:] = _all_gather_ragged(ctx, lens, u_counts).cumsum(0)
+    return off_all, _all_gather_ragged(ctx, idx, [max(c, 0) for c in c_counts]).contiguous()
+
+
+class _CandidatePlan:
+    """This rank's share of a candidate list every rank holds: positions p with items[p] mod W == rank in ascending p (the exchange
+    plan's bucket order is the W ascending local -> global maps one after the other), local row items[p] div W."""
+
+    def __init__(self, ctx: DistCtx, items):
+        W, r, dev = ctx.world, ctx.rank, items.device
+        plan = ShardExchange(ctx).plan(items)
+        self.n_global = items.shape[0]
+        self.l2g = plan.order.to(torch.int32).contiguous()
+        self.l2g_off = torch.zeros(W + 1, dtype=torch.int64, device=dev)
+        self.l2g_off[1:] = plan.send_counts_t.to(torch.int64).cumsum(0)
+        self.lo, self.hi = (int(v) for v in self.l2g_off[r:r + 2].cpu().tolist())
+        self.n_loc = self.hi - self.lo
+        self.local_rows = plan.send_local[self.lo:self.hi].contiguous()
+
+    def split_csr(self, off, idx):
+        """a CSR of global positions cut down to this rank's candidates, in its local positions (brCsrSplitByOwner)"""
+        from . import ops
+        g2l = torch.full((self.n_global,), -1, dtype=torch.int32, device=off.device)
+        g2l[self.l2g[self.lo:self.hi].long()] = torch.arange(self.n_loc, dtype=torch.int32, device=off.device)
+        return ops.csr_split_by_owner(off, idx, g2l)
+
+
 def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, exclude, fetch_user_rows, queries_of, candidates_of, score):
     """The single-device `recommend` contract on row-sharded tables.  A collective, like predict_scores: every rank calls it with
     its own `users` (device ids; counts may differ and may be 0), the SAME `items` (device ids in any order, None = every item row)
@@ -372,7 +421,7 @@ def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, ex
       candidates_of(local) -> the candidate operand of the launch from this rank's own item rows `local` (ids div W)
       score(q, c, k, excl) -> (scores, index) of the fused launch over q x c."""
     from . import ops
-    W, r, dev = ctx.world, ctx.rank, users.device
+    W, dev = ctx.world, users.device
     k = int(k)
     if not 1 <= k <= 256:
         raise ValueError(f"k = {k}: 1 <= k <= 256")
@@ -385,47 +434,23 @@ def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, ex
     if has_ex:
         ex_off, ex_idx = ops._csr(exclude, U, "exclude")
         ex_idx = ex_idx[:int(exclude[1].numel())]
-    # what every rank must know about the others, in ONE small all-gather and one host sync: user and exclusion counts, and that the
-    # candidate lists agree (length, k and a position-weighted checksum of the ids)
-    it64 = items.to(torch.int64)
-    fp = (it64 * (torch.arange(I, device=dev, dtype=torch.int64) % 65521 + 1)).sum()
-    meta = torch.tensor([[U, int(exclude[1].numel()) if has_ex else -1, I, k, 0]], dtype=torch.int64).to(dev)
-    meta[0, 4] = fp
-    meta = ctx.all_gather_rows(meta).cpu().tolist()
-    if any(m[2:] != meta[0][2:] for m in meta):
-        raise ValueError("recommend on a row-sharded engine: every rank must pass the same items and k "
-                         f"(rank {r} sees (len, k, checksum) = {[m[2:] for m in meta]})")
-    u_counts, e_counts = [int(m[0]) for m in meta], [int(m[1]) for m in meta]
+    u_counts, e_counts = _owners_meta(ctx, "recommend", U, int(exclude[1].numel()) if has_ex else -1, items, k)
     U_all = sum(u_counts)
     if U_all == 0:
         return torch.empty(0, k, dtype=torch.float32, device=dev), torch.empty(0, k, dtype=torch.int32, device=dev)
     # 1. the queries of all ranks on every rank
     rows_all = _all_gather_ragged(ctx, fetch_user_rows(users), u_counts)
     q_all = queries_of(rows_all)
-    # 2. this rank's candidates: positions p with items[p] mod W == rank in ascending p (the plan's bucket order is the W ascending
-    #    local -> global maps one after the other), local row items[p] div W
-    plan = ShardExchange(ctx).plan(items)
-    l2g = plan.order.to(torch.int32).contiguous()
-    l2g_off = torch.zeros(W + 1, dtype=torch.int64, device=dev)
-    l2g_off[1:] = plan.send_counts_t.to(torch.int64).cumsum(0)
-    lo, hi = (int(v) for v in l2g_off[r:r + 2].cpu().tolist())
-    n_loc = hi - lo
-    # 3. the exclusion lists of all ranks on every rank.  The two all-gathers depend only on what the meta gather told every rank, never on
-    #    this rank's own candidates: a rank that owns none of `items` still takes part in them
+    # 2. this rank's candidates
+    plan = _CandidatePlan(ctx, items)
+    # 3. the exclusion lists of all ranks on every rank
     csr_all = None
     if any(c >= 0 for c in e_counts):
-        lens = (ex_off[1:] - ex_off[:-1]) if has_ex else torch.zeros(U, dtype=torch.int64, device=dev)
-        idx = ex_idx if has_ex else torch.empty(0, dtype=torch.int32, device=dev)
-        off_all = torch.zeros(U_all + 1, dtype=torch.int64, device=dev)
-        off_all[1:] = _all_gather_ragged(ctx, lens, u_counts).cumsum(0)
-        csr_all = (off_all, _all_gather_ragged(ctx, idx, [max(c, 0) for c in e_counts]).contiguous())
-    if n_loc:
-        cand = candidates_of(plan.send_local[lo:hi].contiguous())
-        excl = None
-        if csr_all is not None:          # cut down to this rank's candidates, in its local positions
-            g2l = torch.full((I,), -1, dtype=torch.int32, device=dev)
-            g2l[l2g[lo:hi].long()] = torch.arange(n_loc, dtype=torch.int32, device=dev)
-            excl = ops.csr_split_by_owner(csr_all[0], csr_all[1], g2l)
+        csr_all = _all_gather_csr(ctx, ex_off if has_ex else None, ex_idx if has_ex else torch.empty(0, dtype=torch.int32, device=dev), U,
+                                  u_counts, e_counts)
+    if plan.n_loc:
+        cand = candidates_of(plan.local_rows)
+        excl = plan.split_csr(*csr_all) if csr_all is not None else None
         s_loc, p_loc = score(q_all, cand, k, excl)
     else:                        # no candidate of the list lives here: empty lists for everybody
         s_loc = torch.full((U_all, k), float("-inf"), dtype=torch.float32, device=dev)
@@ -437,7 +462,74 @@ def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, ex
     ctx.all_to_all(recv, send, [U] * W, u_counts)
     if U == 0:
         return torch.empty(0, k, dtype=torch.float32, device=dev), torch.empty(0, k, dtype=torch.int32, device=dev)
-    return ops.topk_lists_merge(recv.view(torch.float32), recv[:, k:], W, U, k, l2g, l2g_off, list_stride=U * 2 * k, user_stride=2 * k)
+    return ops.topk_lists_merge(recv.view(torch.float32), recv[:, k:], W, U, k, plan.l2g, plan.l2g_off, list_stride=U * 2 * k, user_stride=2 * k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Full-catalogue AUC counted where the item rows live: recommend_at_owners' turn for full_auc.  Every rank scores the
+# positives it owns, the raw scores of all owners are sorted into every user's full list on every rank, each rank counts the queries
+# of ALL ranks against its own candidates, and the integer partial counts go back to the rank that asked: they add up exactly, so the
+# one division gives the single-device float bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_user_rows, queries_of, candidates_of, dim: int, force_wide: bool = False):
+    """The single-device `full_auc` contract on row-sharded tables.  A collective: every rank calls it with its own `users` (device
+    ids; counts may differ and may be 0), the SAME `items` (None = every item row) and the truth CSR (off, idx) over its own users in
+    ascending positions of `items` (ops.truth_csr); it gets the float32 AUCs of its users, NaN where undefined.  fetch_user_rows,
+    queries_of and candidates_of as in recommend_at_owners; dim: the width of the query and candidate rows."""
+    from . import ops
+    W, r, dev = ctx.world, ctx.rank, users.device
+    if items is None:
+        items = torch.arange(n_item_rows, dtype=users.dtype, device=dev)
+    U, I = users.shape[0], items.shape[0]
+    if I < 1:
+        raise ValueError("full_auc: empty candidate list")
+    n_truth = int(truth[1].numel())
+    t_off, t_idx = ops._csr(truth, U, "truth")
+    t_idx = t_idx[:n_truth]
+    # 1. user and truth counts, and that the candidate lists agree
+    u_counts, t_counts = _owners_meta(ctx, "full_auc", U, n_truth, items, 0)
+    U_all = sum(u_counts)
+    if U_all == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    # 2. the queries and the truth lists (global positions) of all ranks on every rank
+    q_all = queries_of(_all_gather_ragged(ctx, fetch_user_rows(users), u_counts))
+    if q_all.shape[1] != dim:
+        raise ValueError(f"full_auc: the query rows have {q_all.shape[1]} features, dim = {dim}")
+    off_all, idx_all = _all_gather_csr(ctx, t_off, t_idx, U, u_counts, t_counts)
+    T_all = sum(t_counts)
+    # 3. this rank's candidates, and its share of every user's positives in its local positions
+    plan = _CandidatePlan(ctx, items)
+    if plan.n_loc:
+        cand = candidates_of(plan.local_rows)
+        pos_off, pos_idx = plan.split_csr(off_all, idx_all)
+        lens = (pos_off[1:] - pos_off[:-1]).to(torch.int32)
+    else:                        # no candidate of the list lives here: no positives, no counts - but every collective below is joined
+        lens = torch.zeros(U_all, dtype=torch.int32, device=dev)
+    # 4. every owner's per-user counts, then its raw scores, on every rank: each piece padded to the longest (one host sync to learn
+    #    it), and the users' full lists sorted from the receive buffer in place
+    lens_all = ctx.all_gather_rows(lens.view(1, U_all)).to(torch.int64)
+    m = int(lens_all.sum(1).max().item())
+    raw = torch.zeros(1, max(m, 1), dtype=torch.float32, device=dev)
+    if plan.n_loc and m:
+        ops.dot_auc_owner_positives(q_all, cand, pos_off, pos_idx, out=raw, force_wide=force_wide)
+    raw_all = ctx.all_gather_rows(raw) if m else raw.repeat(W, 1)
+    piece_off = torch.zeros(W, U_all + 1, dtype=torch.int64, device=dev)
+    piece_off[:, 1:] = lens_all.cumsum(1)
+    piece_off += (torch.arange(W, dtype=torch.int64, device=dev) * raw.shape[1]).view(W, 1)
+    sorted_, pcnt = ops.auc_sort_pieces(raw_all, piece_off, off_all, T_all)
+    # 5. all queries x the local candidates: one integer 2W per user
+    if plan.n_loc:
+        w2 = ops.dot_auc_owner_count(q_all, cand, pos_off, pos_idx, off_all, sorted_, pcnt, force_wide=force_wide)
+    else:
+        w2 = torch.zeros(U_all, dtype=torch.int64, device=dev)
+    # 6. the partials of every user back to its rank in one all-to-all; the finalize reads the receive buffer in place: list w of user
+    #    u at w * U + u
+    recv = torch.empty(W * U, dtype=torch.int64, device=dev)
+    ctx.all_to_all(recv, w2, [U] * W, u_counts)
+    if U == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    u0 = sum(u_counts[:r])
+    return ops.auc_finalize_lists(recv, W, U, t_off, pcnt[u0:u0 + U], I, list_stride=U)
 
 
 def make_sharded_engine(base_cls):
@@ -945,6 +1037,24 @@ def make_sharded_bpr(base_cls):
                                        lambda ids: gather_global_rows(self.ctx, ids, rows_of("user"), self.dim),
                                        lambda rows: rows, rows_of("item"),
                                        lambda q, c, kk, ex: ops.dot_topk_for(self.dim)(q, c, kk, exclude=ex))
+
+        def full_auc(self, users, truth, items=None, dump_scores=False, catalog="gather"):
+            """BPREngine.full_auc as a collective.  catalog="gather" (default): every candidate row is pulled to every rank
+            (_catalog_rows) and each rank evaluates its users alone; "owners": every rank counts the users of ALL ranks against the
+            candidates whose rows it holds and the integer partial counts are summed (auc_at_owners) - the same floats bit for bit, with
+            U x dim user rows, the truth lists and their scores and U partials on the wire instead of I x dim candidate rows per rank."""
+            if catalog not in ("gather", "owners"):
+                raise ValueError(f"catalog must be 'gather' or 'owners', got {catalog!r}")
+            if catalog == "gather":
+                return super().full_auc(users, truth, items=items, dump_scores=dump_scores)
+            if dump_scores:
+                raise NotImplementedError("full_auc(catalog='owners', dump_scores=True): no rank forms the scores of another owner's items")
+            users, items = self._recommend_ids(users, items)
+            self.flush()                         # deferred-Adam rows lag until then
+            rows_of = lambda name: (lambda loc: ops.gather_rows([getattr(self, "_" + name)], [loc], err_flag=self.err)[0])
+            return auc_at_owners(self.ctx, users, items, self.num_items_global, truth,
+                                 lambda ids: gather_global_rows(self.ctx, ids, rows_of("user"), self.dim),
+                                 lambda rows: rows, rows_of("item"), self.dim)
 
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 

@@ -541,6 +541,49 @@ int brCsrSplitByOwner(const int64_t* off, const int32_t* idx, int64_t n_rows, co
 int brTopKListsMerge(const float* scores, const int32_t* index, int64_t list_stride, int64_t user_stride, int n_lists, int64_t n_users,
                      int k, const int32_t* l2g, const int64_t* l2g_off, float* out_scores, int32_t* out_index, brStream stream);
 
+/* ---- Catalogue AUC on row-sharded engines, counted where the item rows live: csrc/auc_owner.hip -----------------------------------------
+ * brDotCatalogAuc[Wide] (full_auc, src/models/bpr.py:230-254, over bpr_predict, bpr.py:122-133) cut into four phases, so that W owners,
+ * each over the candidates whose rows it holds (parallel.py auc_at_owners), return out_auc of ONE launch over the whole candidate list
+ * bit for bit: a pair's score depends on its two rows only, the Mann-Whitney count is a sum over the other items, and it is summed in
+ * integers.  The reference has no counterpart of the split: MultiWorkerMirroredStrategy (src/models/RModel.py:119) mirrors every table.
+ * flags: BR_DOT_FORCE_WIDE as in brDotCatalogAucWide; the positives and the count must get the same flags.  BR_ERR_ARG /
+ * BR_ERR_WORKSPACE before any launch; n_users == 0 is BR_OK; no allocation and no sync inside.
+ * brDotAucOwnerPositives: bpr.py:122-133 for the pairs (user, positive) alone, the scoring half of brDotCatalogAuc's prepass.  C: this
+ *   owner's candidate rows; (pos_off (n_users + 1), pos_idx): per user its positives among them, LOCAL positions (brCsrSplitByOwner).
+ *   raw[pos_off[u] + j] = score(u, the user's j-th entry) on v_mfma_f32_16x16x4_f32, one chain from 0 over the padded width the count
+ *   instantiates at this dim and flags: the catalogue pass's score bit for bit.  An entry outside [0, n_items) scores NaN.  raw holds
+ *   pos_off[n_users] floats.  Limits: 1 <= dim <= 512, 1 <= n_items < 2^31, ld_q, ld_c >= dim.
+ * brAucSortPieces: the sorting half of that prepass (the ranking roc_auc_score does inside, bpr.py:252) over the pieces of all owners.
+ *   piece_off: n_pieces rows of (n_users + 1) int64: piece w of user u is raw[piece_off[w][u] ... piece_off[w][u + 1]) (so the receive
+ *   buffer of an all-gather is read in place; n_raw: raw's floats).  -> sorted[list_off[u] ...]: the user's entries ascending, NaN
+ *   dropped, their number P' in pcnt[u]: the multiset the single-device prepass produces, whatever the order of the pieces.
+ *   pcnt[u] = -1 (NaN from the finalize) for a user whose list lies past cap (the floats `sorted` holds), whose pieces outnumber
+ *   list_off[u + 1] - list_off[u] or lie outside raw; nothing of such a user is read or written.  O(P^2) compares per user.
+ *   Limits: 1 <= n_pieces <= 4096.  ws: brAucSortPiecesWorkspaceBytes(n_pieces, cap) bytes; -1 outside the limits.
+ * brDotAucOwnerCount: brDotCatalogAuc[Wide]'s catalogue pass (bpr.py:252 without the U x I matrix) over this owner's candidates C with
+ *   two CSRs in two roles: (skip_off, skip_idx) the owner's positives, ascending LOCAL positions, skipped; list_off / sorted / pcnt of
+ *   brAucSortPieces the user's FULL list every other score is counted against (2P' below its minimum, 0 above its maximum, 2 #{> s} +
+ *   #{== s} inside; a NaN score adds 0).  out_w2[u]: the user's 2W over these candidates, uint64, the item splits already summed in
+ *   integers.  dump_scores (optional, n_users x n_items): every pair's score (tests).  Limits: 1 <= dim <= 512 (whole-row kernels up to
+ *   128 unless BR_DOT_FORCE_WIDE, block kernels above), otherwise those of brDotCatalogAuc.
+ *   ws: brDotAucOwnerCountWorkspaceBytes(n_users, n_items, dim) bytes (the per-split partials); -1 outside the limits.
+ * brAucFinalizeLists: the division of roc_auc_score (bpr.py:252) and the skip of a user without positives (bpr.py:251).  n_lists partial
+ *   2W per user, list w of user u at part[w * list_stride + u] (the receive buffer of an all-to-all read in place); truth_off
+ *   (n_users + 1): the GLOBAL truth offsets (P = the user's entries, N = n_items - P over the global n_items); pcnt of brAucSortPieces.
+ *   out_auc[u] = (float)((double)W / ((double)P (double)N)), NaN for P <= 0, N <= 0 or pcnt[u] < 0.
+ *   Limits: 1 <= n_lists <= 4096, list_stride >= n_users, 1 <= n_items < 2^31. */
+int brDotAucOwnerPositives(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                           const int64_t* pos_off, const int32_t* pos_idx, float* raw, int flags, brStream stream);
+int64_t brAucSortPiecesWorkspaceBytes(int n_pieces, int64_t cap);
+int brAucSortPieces(const float* raw, int64_t n_raw, const int64_t* piece_off, int n_pieces, int64_t n_users, const int64_t* list_off,
+                    float* sorted, int64_t cap, int32_t* pcnt, void* ws, int64_t ws_bytes, brStream stream);
+int64_t brDotAucOwnerCountWorkspaceBytes(int64_t n_users, int64_t n_items, int dim);
+int brDotAucOwnerCount(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                       const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off, const float* sorted, const int32_t* pcnt,
+                       int64_t cap, uint64_t* out_w2, float* dump_scores, int flags, void* ws, int64_t ws_bytes, brStream stream);
+int brAucFinalizeLists(const uint64_t* part, int64_t list_stride, int n_lists, const int64_t* truth_off, const int32_t* pcnt,
+                       int64_t n_users, int64_t n_items, float* out_auc, brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the
