@@ -22,8 +22,6 @@ namespace {
 
 constexpr int kMaxLists = 4096;           // pieces per user of brAucSortPieces, lists per user of brAucFinalizeLists (brTopKListsMerge's limit)
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 // one wave per user: raw[off[u] + j] = score(u, the user's j-th entry), NaN for an entry outside [0, n_items); auc_pos_kernel's first half
 template <int KB>
 __global__ __launch_bounds__(256) void auc_pos_scores_kernel(const float* __restrict__ Q, int64_t ld_q, int64_t n_users, const float* __restrict__ C,

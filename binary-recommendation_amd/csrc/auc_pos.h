@@ -10,8 +10,6 @@
 namespace br {
 namespace {
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 // one wave per user: score its truth entries, sort them ascending (NaN dropped) into sorted[off[u] ...], P' into pcnt[u] (-1: the
 // user's entries lie past the workspace's capacity `cap`)
 template <int KB>

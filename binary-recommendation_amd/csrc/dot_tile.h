@@ -11,6 +11,8 @@ namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
+int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }   // workspace sections start on 256 bytes
+
 constexpr int64_t kSplitTargetWgs = 2048;   // splits are added until the grid has about this many workgroups
 
 // `units` steps of the item axis, users_per_wg users per workgroup -> the number of splits (grid.y, <= 65535) and the steps each takes

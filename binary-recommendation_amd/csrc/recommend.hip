@@ -19,38 +19,11 @@
 
 #include "common.h"
 #include "dot_tile.h"
+#include "neumf_tower.h"
 #include "topk_list.h"
 
 namespace br {
 namespace {
-
-// padded width of the second layer (the per-lane accumulator count): one instantiation per width
-int tower_width(int n2) {
-  if (n2 <= 64) return (n2 + 7) / 8 * 8;
-  return n2 <= 96 ? 96 : 128;
-}
-
-// folded tower layout (floats): W2' [n1][W] | b2' [W] | W3'^T [n3][W] | b3' [n3] | w4 of the tower outputs [n3] | w4 of the GMF dot | b4
-struct TowerLayout {
-  int64_t w2, b2, w3t, b3, w4, w4mf, b4, total;
-};
-TowerLayout tower_layout(int n1, int n2, int n3) {
-  const int W = tower_width(n2);
-  TowerLayout t;
-  t.w2 = 0;
-  t.b2 = (int64_t)n1 * W;
-  t.w3t = t.b2 + W;
-  t.b3 = t.w3t + (int64_t)n3 * W;
-  t.w4 = t.b3 + n3;
-  t.w4mf = t.w4 + n3;
-  t.b4 = t.w4mf + 1;
-  t.total = t.b4 + 1;
-  return t;
-}
-
-void catalog_plan(int64_t n_users, int64_t n_items, int64_t* splits, int64_t* chunks_per_split) {
-  split_plan(ceil_div(n_items, 64), n_users, kRecWaves, splits, chunks_per_split);   // (dot_tile.h: the one plan of the catalogue kernels)
-}
 
 template <typename IdT>
 __global__ __launch_bounds__(256) void catalog_project_kernel(const float* __restrict__ table, int64_t ld, int64_t rows,
@@ -281,8 +254,6 @@ void launch_catalog_topk(dim3 grid, hipStream_t st, const float* pu, int64_t ld_
     catalog_topk_kernel<W, BR_ACT_LINEAR><<<grid, 256, 0, st>>>(pu, ld_u, pit, ld_i, U, I, dim, n1, n3, tower, L, ex_off, ex_idx, k, cps, S, ps, pp, dl, dp);
 }
 
-bool tower_shape_ok(int n1, int n2, int n3) { return n1 >= 1 && n1 <= 128 && n2 >= 1 && n2 <= 128 && n3 >= 1 && n3 <= 32; }
-
 }  // namespace
 }  // namespace br
 
@@ -343,11 +314,7 @@ extern "C" int brNeumfCatalogTopK(const float* pu, int64_t ld_u, const float* pi
                                   brStream stream) {
   BR_CHECK_ARG(pu && pit && tower && out_scores && out_index && ws, "brNeumfCatalogTopK: null pointer");
   BR_CHECK_ARG(k >= 1 && k <= kRecMaxK, "brNeumfCatalogTopK: k = %d outside [1, %d]", k, kRecMaxK);
-  BR_CHECK_ARG(tower_shape_ok(n1, n2, n3), "brNeumfCatalogTopK: tower widths n1, n2 <= 128, n3 <= 32 (got %d, %d, %d)", n1, n2, n3);
-  BR_CHECK_ARG(dim >= 1 && 2 * dim <= 256, "brNeumfCatalogTopK: 1 <= dim, 2*dim <= 256 (got %d)", dim);
-  BR_CHECK_ARG(n_users >= 0 && n_items >= 1 && n_items < ((int64_t)1 << 31), "brNeumfCatalogTopK: bad sizes (1 <= n_items < 2^31)");
-  BR_CHECK_ARG(ld_u >= n1 + dim && ld_i >= n_items, "brNeumfCatalogTopK: ld_u >= n1 + dim and ld_i >= n_items");
-  BR_CHECK_ARG(act == BR_ACT_LINEAR || act == BR_ACT_SIGMOID || act == BR_ACT_RELU, "brNeumfCatalogTopK: bad act");
+  if (const int rc = catalog_check_args("brNeumfCatalogTopK", ld_u, n_users, ld_i, n_items, dim, n1, n2, n3, act)) return rc;
   BR_CHECK_ARG((excl_off == nullptr) == (excl_idx == nullptr), "brNeumfCatalogTopK: exclusion needs both excl_off and excl_idx");
   int64_t S, cps;
   catalog_plan(n_users, n_items, &S, &cps);

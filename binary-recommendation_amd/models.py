@@ -81,6 +81,30 @@ def _to_dev(a, device, dtype):
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a)), device=device).to(dtype).contiguous()
 
 
+def _truth_of(ground_truth, items, device_of, strict: bool):
+    """The ranking metrics' set-up (src/models/bpr.py:230-289): -> (gt list, item -> column, truth CSR over the users of gt in positions of
+    `items` on device_of()).  strict: a true item outside `items` raises as the reference's `items.index(p)` (bpr.py:247) - before any
+    engine is touched - otherwise it is left out."""
+    gt = list(ground_truth)
+    col = {it: j for j, it in enumerate(items)}
+    if strict:
+        missing = [p for _u, t in gt for p in t if p not in col]
+        if missing:
+            raise ValueError(f"{missing[0]!r} is not in list")
+    rows = [r for r, (_u, t) in enumerate(gt) for p in t if p in col]
+    cols = [col[p] for _u, t in gt for p in t if p in col]
+    return gt, col, ops.truth_csr(len(gt), rows, cols, device_of())
+
+
+def _ap_scale(gt, col, k):
+    """brMapAtK divides by min(truth items it was given, k); the reference by min(len(actual), k) with EVERY listed item, also those
+    outside `items` (bpr.py:286): the per-user factor between the two (tiny vectors, on the host).  A user without positives: the
+    reference divides by zero there (ZeroDivisionError); here such a user contributes AP 0."""
+    have = np.array([len({p for p in t if p in col}) for _u, t in gt], dtype=np.float64)
+    want = np.array([len(t) for _u, t in gt], dtype=np.float64)
+    return np.where(want > 0, np.minimum(have, k) / np.maximum(np.minimum(want, k), 1.0), 0.0)
+
+
 # the compiled metric lists of the reference, by the names Keras gives them in `history` / `evaluate`
 RMODEL_METRICS = ["mse", "mae", "binary_accuracy"]                                   # RModel.METRICS (RModel.py:20)
 NFC_PLAIN_METRICS = ["binary_crossentropy", "mse", "mae", "false_negatives", "false_positives", "true_negatives", "true_positives",
@@ -318,6 +342,36 @@ class NeuMFModel(RModel):
         return [[(str(items[int(ti[n, j])]), str(ts[n, j])) for j in range(min(k, int(numberOfItem))) if ti[n, j] >= 0]
                 for n in range(len(users))]
 
+    # ---- the ranking metrics of the stand-alone BPR notebook (src/models/bpr.py) over the NeuMF graph, on the GPU ----
+    def full_auc(self, ground_truth, items, method="fused") -> float:
+        """full_auc (src/models/bpr.py:230-254) of the NeuMF probabilities (predictForUser's scores, NeuMFModel.py:133-150): mean over
+        the users that have positives of roc_auc_score(ground truth over all `items`, model.predict).  ground_truth: iterable of
+        (user_id, [true item ids]).  method="fused" (default): NeuMFEngine.full_auc without the users x items matrix; "pairs": every
+        pair through predict, then brFullAuc (single-device engines only).  Under a process group a collective: every rank calls it
+        with its own users and the same `items`."""
+        if method not in ("fused", "pairs"):
+            raise ValueError(f"method must be 'fused' or 'pairs', got {method!r}")
+        gt, _col, (off, idx) = _truth_of(ground_truth, items, lambda: self.model.engine.device, strict=True)
+        e = self.model.engine
+        auc = e.full_auc(_to_dev(np.asarray([u for u, _ in gt]), e.device, e.id_dtype), (off, idx),
+                         items=_to_dev(np.asarray(items), e.device, e.id_dtype), method=method)
+        e.check_ids()
+        auc = auc.cpu().numpy()
+        has = np.array([len(t) > 0 for _u, t in gt], dtype=bool)
+        return float(np.mean(auc[has]))
+
+    def mean_average_precision_k(self, ground_truth, items, k=100) -> float:
+        """mean_average_precision_k (src/models/bpr.py:257-289) of the NeuMF probabilities: AP of each user's top-k from
+        NeuMFEngine.recommend (k <= 256) / min(len(actual), k).  Under a process group a collective."""
+        gt, col, (off, idx) = _truth_of(ground_truth, items, lambda: self.model.engine.device, strict=False)
+        e = self.model.engine
+        k = min(int(k), len(items))
+        _ts, ti = e.recommend(_to_dev(np.asarray([u for u, _ in gt]), e.device, e.id_dtype), k,
+                              items=_to_dev(np.asarray(items), e.device, e.id_dtype))
+        e.check_ids()
+        ap, _ = ops.map_at_k(ti, off, idx, want_hits=False)
+        return float((ap.double().cpu().numpy() * _ap_scale(gt, col, k)).mean())
+
     def predictForUser(self, customerId, numberOfItem=5, sort="float", excludeSeen=False):
         """NeuMFModel.py:133-150 -> [(item, score)] as strings, best first.  excludeSeen=True: the customer's training-split products
         are left out, through recommendForUsers (the fused catalogue top-k); the default keeps the reference's path below.
@@ -412,14 +466,7 @@ class BPRModel(RModel):
         sharded = hasattr(self.model, "ctx")
         if catalog == "owners" and (method != "fused" or not sharded):
             raise ValueError("catalog='owners' needs method='fused' on a row-sharded engine (a model compiled under a process group)")
-        gt = list(ground_truth)
-        col = {it: j for j, it in enumerate(items)}
-        missing = [p for _u, t in gt for p in t if p not in col]
-        if missing:      # the reference's `items.index(p)` (bpr.py:247) raises ValueError for a true item outside `items`
-            raise ValueError(f"{missing[0]!r} is not in list")
-        rows = [r for r, (_u, t) in enumerate(gt) for _ in t]
-        cols = [col[p] for _u, t in gt for p in t]
-        off, idx = ops.truth_csr(len(gt), rows, cols, self.model.device)
+        gt, _col, (off, idx) = _truth_of(ground_truth, items, lambda: self.model.device, strict=True)
         if method == "fused":
             e = self.model
             auc = e.full_auc(_to_dev(np.asarray([u for u, _ in gt]), e.device, e.id_dtype), (off, idx),
@@ -437,12 +484,7 @@ class BPRModel(RModel):
         users x items matrix (k <= 256)."""
         if method not in ("matrix", "fused"):
             raise ValueError(f"method must be 'matrix' or 'fused', got {method!r}")
-        gt = list(ground_truth)
-        col = {it: j for j, it in enumerate(items)}
-        rows = [r for r, (_u, t) in enumerate(gt) for _ in t]
-        cols = [col[p] for _u, t in gt for p in t if p in col]
-        rows = [r for r, (_u, t) in enumerate(gt) for p in t if p in col]
-        off, idx = ops.truth_csr(len(gt), rows, cols, self.model.device)
+        gt, col, (off, idx) = _truth_of(ground_truth, items, lambda: self.model.device, strict=False)
         k = min(int(k), len(items))
         if method == "fused":
             e = self.model
@@ -451,13 +493,7 @@ class BPRModel(RModel):
         else:
             _ts, ti = ops.topk_rows(self._scores([u for u, _ in gt], items), k)
         ap, _ = ops.map_at_k(ti, off, idx, want_hits=False)
-        # brMapAtK divides by min(truth items it was given, k); the reference by min(len(actual), k) with EVERY listed item, also those
-        # outside `items` (bpr.py:286): rescale per user on the host (tiny vectors).  A user without positives: the reference divides by
-        # zero there (ZeroDivisionError); here such a user contributes AP 0.
-        have = np.array([len({p for p in t if p in col}) for _u, t in gt], dtype=np.float64)
-        want = np.array([len(t) for _u, t in gt], dtype=np.float64)
-        scale = np.where(want > 0, np.minimum(have, k) / np.maximum(np.minimum(want, k), 1.0), 0.0)
-        return float((ap.double().cpu().numpy() * scale).mean())
+        return float((ap.double().cpu().numpy() * _ap_scale(gt, col, k)).mean())
 
     # ---- recommendation (the reference's BPRModel has none): the fused dot-product catalogue top-k ----
     def getPredictableUsers(self) -> list:

@@ -636,6 +636,40 @@ class NeuMFEngine(RowAdam):
             out[s:e].copy_(self.prob[:e - s])
         return out
 
+    def _catalog_ids(self, users, items, every_item=True):
+        """What recommend and full_auc do first: flush, then `users` and `items` as contiguous device id tensors of one integer dtype.
+        items None: every item row - or None itself with every_item=False (an owner of a row-sharded engine enumerates its own rows)."""
+        dev = self.device
+        self.flush()                         # deferred-Adam rows lag until then (as _infer)
+        users = torch.as_tensor(users, device=dev)
+        if users.dtype not in (torch.int32, torch.int64):
+            users = users.to(self.id_dtype)
+        if items is None and every_item:
+            items = torch.arange(self.num_item_rows, dtype=users.dtype, device=dev)
+        if items is not None:
+            items = torch.as_tensor(items, device=dev)
+            items = (items if items.dtype == users.dtype else items.to(users.dtype)).contiguous()
+        return users.contiguous(), items
+
+    def _catalog_tower(self):
+        """-> (the dense parameters by name, the tower with BatchNorm folded in: csrc/recommend.hip brNeumfCatalogFold)"""
+        cfg = self.cfg
+        th = {name: self.theta.view(name) for name in self.theta.offsets}
+        return th, ops.neumf_catalog_fold(th, self.moving, *cfg.hidden, cfg.mf_first, cfg.bn_eps)
+
+    def _catalog_project(self, th, table, ids, user_side):
+        """first-layer projection of rows `ids` of `table`: users row-major with the bias, items column-major"""
+        cfg = self.cfg
+        if user_side:
+            return ops.neumf_catalog_project(table, ids, th["W1"], cfg.hidden[0], cfg.dim, cfg.item_first, True, b1=th["b1"], err_flag=self.err)
+        return ops.neumf_catalog_project(table, ids, th["W1"], cfg.hidden[0], cfg.dim, cfg.item_first, False, col_major=True, err_flag=self.err)
+
+    def _catalog_operands(self, users, items):
+        """-> (users, items, tower, pu, pit): what the fused catalogue kernels take"""
+        users, items = self._catalog_ids(users, items)
+        th, tower = self._catalog_tower()
+        return users, items, tower, self._catalog_project(th, self.fused["user"], users, True), self._catalog_project(th, self.fused["item"], items, False)
+
     def recommend(self, users, k, items=None, exclude=None, dump_logits=None):
         """The k best items of every user of `users` in inference mode (the sigmoid output predict returns), without scoring pairs
         one by one: the first layer is split into a user and an item projection, BatchNorm folded into the next layer, and one fused
@@ -644,23 +678,39 @@ class NeuMFEngine(RowAdam):
         -> (scores (U, k) float32, index (U, k) int32 positions into `items`) on the device, best first, ties to the lower position;
         slots past the remaining candidates are (-inf, -1).  dump_logits=True also returns every pair's head logit (U x I).
         (The row-sharded engine overrides this with a collective of the same contract: parallel.py recommend_at_owners.)"""
-        cfg, dev = self.cfg, self.device
-        D, (n1, n2, n3) = cfg.dim, cfg.hidden
-        self.flush()                         # deferred-Adam rows lag until then (as _infer)
-        users = torch.as_tensor(users, device=dev)
-        if users.dtype not in (torch.int32, torch.int64):
-            users = users.to(self.id_dtype)
-        if items is None:
-            items = torch.arange(self.num_item_rows, dtype=users.dtype, device=dev)
-        items = torch.as_tensor(items, device=dev)
-        if items.dtype != users.dtype:
-            items = items.to(users.dtype)
-        users, items = users.contiguous(), items.contiguous()
-        th = {name: self.theta.view(name) for name in self.theta.offsets}
-        tower = ops.neumf_catalog_fold(th, self.moving, n1, n2, n3, cfg.mf_first, cfg.bn_eps)
-        pu = ops.neumf_catalog_project(self.fused["user"], users, th["W1"], n1, D, cfg.item_first, True, b1=th["b1"], err_flag=self.err)
-        pit = ops.neumf_catalog_project(self.fused["item"], items, th["W1"], n1, D, cfg.item_first, False, col_major=True, err_flag=self.err)
-        return ops.neumf_catalog_topk(pu, pit, tower, D, (n1, n2, n3), cfg.act, k, exclude=exclude, dump_logits=bool(dump_logits))
+        cfg = self.cfg
+        users, items, tower, pu, pit = self._catalog_operands(users, items)
+        return ops.neumf_catalog_topk(pu, pit, tower, cfg.dim, tuple(cfg.hidden), cfg.act, k, exclude=exclude, dump_logits=bool(dump_logits))
+
+    PAIR_CHUNK = 1 << 22        # pairs per predict call of full_auc(method="pairs")
+
+    def full_auc(self, users, truth, items=None, dump_probs=False, method="fused"):
+        """Per-user ROC AUC over the whole candidate list (full_auc, src/models/bpr.py:230-254) of the probabilities predict returns, in
+        inference mode.  truth: (off, idx) CSR over `users` of the candidate POSITIONS that are positives (ops.truth_csr); items: the
+        candidate ids (None: every item row).  -> float32 (U,) on the device, NaN where undefined (no positives, or nothing else).
+        method="fused" (default): recommend's set-up, then one fused evaluation that never forms the U x I matrix (csrc/auc_neumf.hip);
+        dump_probs=True also returns every pair's probability (U x I).  method="pairs": the stand-in it replaces - every pair through
+        predict in chunks, the U x I matrix, ops.full_auc - kept as the cross-check and the benchmark's baseline.
+        (The row-sharded engine overrides this with a collective of the same contract: parallel.py auc_at_owners.)"""
+        if method not in ("fused", "pairs"):
+            raise ValueError(f"method must be 'fused' or 'pairs', got {method!r}")
+        cfg = self.cfg
+        off, idx = truth
+        users, items = self._catalog_ids(users, items)
+        U, I = users.shape[0], items.shape[0]
+        if I < 1:
+            raise ValueError("full_auc: empty candidate list")
+        if method == "pairs":
+            probs = torch.empty(U, I, dtype=torch.float32, device=self.device)
+            flat = probs.view(-1)
+            rows = max(1, self.PAIR_CHUNK // I)
+            for u0 in range(0, U, rows):
+                u1 = min(U, u0 + rows)
+                self.predict(users[u0:u1].repeat_interleave(I), items.repeat(u1 - u0), out=flat[u0 * I:u1 * I])
+            auc = ops.full_auc(probs, *ops._csr((off, idx), U, "truth"))
+            return (auc, probs) if dump_probs else auc
+        users, items, tower, pu, pit = self._catalog_operands(users, items)
+        return ops.neumf_catalog_auc(pu, pit, tower, cfg.dim, tuple(cfg.hidden), cfg.act, off, idx, dump_probs=bool(dump_probs))
 
     def evaluate_batch(self, users, items, labels):
         """inference-mode forward + loss/metric sums accumulated into self.msums (no grads)."""

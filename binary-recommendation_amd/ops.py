@@ -951,6 +951,104 @@ def auc_finalize_lists(part, n_lists: int, n_users: int, truth_off, pcnt, n_item
     return out
 
 
+# ------------------------------------------------------------------------------ NeuMF catalogue AUC (csrc/auc_neumf.hip)
+# The operands of neumf_catalog_topk; the score of a pair is the probability that op's dump_probs shows, bit for bit.
+def _neumf_catalog_args(who: str, pu, pit, tower, dim: int, hidden, act: str):
+    """the checks the NeuMF catalogue AUC ops (`who`) make on their operands -> (U, I, n1, n2, n3, device)"""
+    n1, n2, n3 = (int(n) for n in hidden)
+    dim = int(dim)
+    for t, name in ((pu, "pu"), (pit, "pit")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{who}: {name} must be a 2-D tensor")
+    if act not in ACT:
+        raise ValueError(f"{who}: act = {act!r}: one of {sorted(ACT)}")
+    if not (1 <= n1 <= 128 and 1 <= n2 <= 128 and 1 <= n3 <= 32):
+        raise ValueError(f"{who}: tower widths n1, n2 <= 128 and n3 <= 32 (got {n1}, {n2}, {n3})")
+    if not (1 <= dim and 2 * dim <= 256):
+        raise ValueError(f"{who}: dim = {dim}: 1 <= dim, 2 * dim <= 256")
+    _rows_f32(pu, "pu"); _rows_f32(pit, "pit")
+    if not isinstance(tower, torch.Tensor) or tower.dtype != torch.float32 or not tower.is_cuda or not tower.is_contiguous():
+        raise TypeError(f"{who}: tower must be a contiguous float32 device tensor (ops.neumf_catalog_fold)")
+    if pu.shape[1] != n1 + dim or pit.shape[0] != n1 + dim:
+        raise ValueError(f"{who}: pu must be (U, {n1 + dim}) and pit ({n1 + dim}, I) (got {tuple(pu.shape)}, {tuple(pit.shape)})")
+    n_tower = int(_lib.load().brNeumfCatalogTowerFloats(n1, n2, n3))
+    if tower.numel() != n_tower:
+        raise ValueError(f"{who}: tower has {tower.numel()} floats, the widths ({n1}, {n2}, {n3}) need {n_tower}")
+    if pu.device != pit.device or pu.device != tower.device:
+        raise ValueError(f"{who}: pu, pit and tower on different devices")
+    if pit.shape[1] < 1:
+        raise ValueError(f"{who}: empty candidate list")
+    return pu.shape[0], pit.shape[1], n1, n2, n3, pu.device
+
+
+def _neumf_operands(pu, pit, U, I, dim, n1, n2, n3, act, tower):
+    """the C-ABI's leading arguments (pu, ld_u, n_users, pit, ld_i, n_items, dim, n1, n2, n3, act, tower)"""
+    return (pu.data_ptr() if U else tower.data_ptr(), pu.stride(0) if U > 1 else n1 + dim, U, pit.data_ptr(), pit.stride(0), I, int(dim), n1, n2,
+            n3, ACT[act], tower.data_ptr())
+
+
+def neumf_auc_positives(pu, pit, tower, dim: int, hidden, act: str, pos_off, pos_idx, out=None):
+    """pu (U x (n1 + dim)), pit ((n1 + dim) x I_loc), tower: the operands of neumf_catalog_topk over these candidates; (pos_off,
+    pos_idx): per user its positives among them, positions into pit (csr_split_by_owner on a row-sharded engine) -> raw float32:
+    raw[pos_off[u] + j] = the catalogue pass's probability of the user's j-th entry, NaN for a position outside pit.  out: a float32
+    device buffer of at least pos_off[-1] entries (default: one of pos_idx's capacity) (brNeumfAucPositives)."""
+    U, I, n1, n2, n3, dev = _neumf_catalog_args("neumf_auc_positives", pu, pit, tower, dim, hidden, act)
+    n_cap = pos_idx.numel() if isinstance(pos_idx, torch.Tensor) else 0
+    off, idx = _csr((pos_off, pos_idx), U, "positives")
+    out = torch.empty(max(n_cap, 1), dtype=torch.float32, device=dev) if out is None else out
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise TypeError("neumf_auc_positives: out must be a contiguous float32 device tensor")
+    check(_lib.load().brNeumfAucPositives(*_neumf_operands(pu, pit, U, I, dim, n1, n2, n3, act, tower), off.data_ptr(), idx.data_ptr(),
+                                          out.data_ptr(), _stream()), "brNeumfAucPositives")
+    return out
+
+
+def neumf_auc_count(pu, pit, tower, dim: int, hidden, act: str, skip_off, skip_idx, list_off, sorted_, pcnt, dump_probs=False):
+    """the operands of neumf_auc_positives; (skip_off, skip_idx): the users' positives among these candidates, ascending positions;
+    list_off / sorted_ / pcnt of auc_sort_pieces: every user's FULL list -> per user the integer 2W over these candidates, int64 (U,)
+    (the library's uint64: below 2^63 while P N < 2^62) [, every pair's probability (U, I_loc)] (brNeumfAucCount)."""
+    U, I, n1, n2, n3, dev = _neumf_catalog_args("neumf_auc_count", pu, pit, tower, dim, hidden, act)
+    off, idx = _csr((skip_off, skip_idx), U, "skip")
+    if list_off.dtype != torch.int64 or not list_off.is_cuda or not list_off.is_contiguous() or list_off.numel() != U + 1:
+        raise TypeError(f"neumf_auc_count: list_off must be a contiguous int64 device tensor of {U + 1} entries")
+    if sorted_.dtype != torch.float32 or not sorted_.is_cuda or not sorted_.is_contiguous() or sorted_.numel() < 1:
+        raise TypeError("neumf_auc_count: sorted_ must be a non-empty contiguous float32 device tensor")
+    _i32_dev(pcnt, "pcnt")
+    if pcnt.numel() != U:
+        raise ValueError(f"neumf_auc_count: pcnt has {pcnt.numel()} entries for {U} users")
+    lib = _lib.load()
+    ws_bytes = int(lib.brNeumfAucCountWorkspaceBytes(U, I))
+    if ws_bytes < 0:
+        raise ValueError(f"neumf_auc_count: bad sizes U={U} I={I}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.int64, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_probs else None
+    check(lib.brNeumfAucCount(*_neumf_operands(pu, pit, U, I, dim, n1, n2, n3, act, tower), off.data_ptr(), idx.data_ptr(), list_off.data_ptr(),
+                              sorted_.data_ptr(), pcnt.data_ptr() if U else sorted_.data_ptr(), sorted_.numel() - 1,
+                              out.data_ptr() if U else sorted_.data_ptr(), _p(dump), ws.data_ptr(), ws_bytes, _stream()), "brNeumfAucCount")
+    return (out, dump) if dump_probs else out
+
+
+def neumf_catalog_auc(pu, pit, tower, dim: int, hidden, act: str, truth_off, truth_idx, dump_probs=False):
+    """pu (U x (n1 + dim)) and pit ((n1 + dim) x I) from neumf_catalog_project, tower from neumf_catalog_fold, truth (ops.truth_csr over
+    the rows of pu: ascending positions into the item list) -> per-user AUC float32 (U,) [, every pair's probability (U, I)]: full_auc
+    of the probabilities neumf_catalog_topk ranks by, equal bit for bit to full_auc(its dump_probs, truth_off, truth_idx), NaN where
+    undefined; the U x I matrix is not stored (brNeumfCatalogAuc)."""
+    U, I, n1, n2, n3, dev = _neumf_catalog_args("neumf_catalog_auc", pu, pit, tower, dim, hidden, act)
+    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
+    off, idx = _csr((truth_off, truth_idx), U, "truth")
+    lib = _lib.load()
+    ws_bytes = int(lib.brNeumfCatalogAucWorkspaceBytes(U, I, n_truth))
+    if ws_bytes < 0:
+        raise ValueError(f"neumf_catalog_auc: bad sizes U={U} I={I}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.float32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_probs else None
+    check(lib.brNeumfCatalogAuc(*_neumf_operands(pu, pit, U, I, dim, n1, n2, n3, act, tower), off.data_ptr(), idx.data_ptr(),
+                                out.data_ptr() if U else ws.data_ptr(), _p(dump), ws.data_ptr(), ws_bytes, _stream()), "brNeumfCatalogAuc")
+    return (out, dump) if dump_probs else out
+
+
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts
 def truth_csr(n_users: int, user_rows, item_cols, device):
     """Ground truth of `n_users` rows as the CSR the eval kernels take: (offsets int64 (n_users + 1), column indices int32 ascending

@@ -471,12 +471,20 @@ def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, ex
 # of ALL ranks against its own candidates, and the integer partial counts go back to the rank that asked: they add up exactly, so the
 # one division gives the single-device float bit for bit.
 # ---------------------------------------------------------------------------------------------------------------------
-def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_user_rows, queries_of, candidates_of, dim: int, force_wide: bool = False):
+def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_user_rows, queries_of, candidates_of, dim: int = None,
+                  force_wide: bool = False, positives=None, count=None):
     """The single-device `full_auc` contract on row-sharded tables.  A collective: every rank calls it with its own `users` (device
     ids; counts may differ and may be 0), the SAME `items` (None = every item row) and the truth CSR (off, idx) over its own users in
     ascending positions of `items` (ops.truth_csr); it gets the float32 AUCs of its users, NaN where undefined.  fetch_user_rows,
-    queries_of and candidates_of as in recommend_at_owners; dim: the width of the query and candidate rows."""
+    queries_of and candidates_of as in recommend_at_owners; dim: the width of the query and candidate rows (checked when given).
+    positives(q, cand, pos_off, pos_idx, out) and count(q, cand, skip_off, skip_idx, list_off, sorted_, pcnt): the model's scoring
+    phases over this rank's candidates (defaults: the dot-product ones, ops.dot_auc_owner_positives / ops.dot_auc_owner_count with
+    force_wide; NeuMF passes ops.neumf_auc_positives / ops.neumf_auc_count over its projected operands)."""
     from . import ops
+    if positives is None:
+        positives = lambda q, c, po, pi, out: ops.dot_auc_owner_positives(q, c, po, pi, out=out, force_wide=force_wide)
+    if count is None:
+        count = lambda q, c, so, si, lo, srt, pc: ops.dot_auc_owner_count(q, c, so, si, lo, srt, pc, force_wide=force_wide)
     W, r, dev = ctx.world, ctx.rank, users.device
     if items is None:
         items = torch.arange(n_item_rows, dtype=users.dtype, device=dev)
@@ -493,7 +501,7 @@ def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_use
         return torch.empty(0, dtype=torch.float32, device=dev)
     # 2. the queries and the truth lists (global positions) of all ranks on every rank
     q_all = queries_of(_all_gather_ragged(ctx, fetch_user_rows(users), u_counts))
-    if q_all.shape[1] != dim:
+    if dim is not None and q_all.shape[1] != dim:
         raise ValueError(f"full_auc: the query rows have {q_all.shape[1]} features, dim = {dim}")
     off_all, idx_all = _all_gather_csr(ctx, t_off, t_idx, U, u_counts, t_counts)
     T_all = sum(t_counts)
@@ -511,7 +519,7 @@ def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_use
     m = int(lens_all.sum(1).max().item())
     raw = torch.zeros(1, max(m, 1), dtype=torch.float32, device=dev)
     if plan.n_loc and m:
-        ops.dot_auc_owner_positives(q_all, cand, pos_off, pos_idx, out=raw, force_wide=force_wide)
+        positives(q_all, cand, pos_off, pos_idx, raw)
     raw_all = ctx.all_gather_rows(raw) if m else raw.repeat(W, 1)
     piece_off = torch.zeros(W, U_all + 1, dtype=torch.int64, device=dev)
     piece_off[:, 1:] = lens_all.cumsum(1)
@@ -519,7 +527,7 @@ def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_use
     sorted_, pcnt = ops.auc_sort_pieces(raw_all, piece_off, off_all, T_all)
     # 5. all queries x the local candidates: one integer 2W per user
     if plan.n_loc:
-        w2 = ops.dot_auc_owner_count(q_all, cand, pos_off, pos_idx, off_all, sorted_, pcnt, force_wide=force_wide)
+        w2 = count(q_all, cand, pos_off, pos_idx, off_all, sorted_, pcnt)
     else:
         w2 = torch.zeros(U_all, dtype=torch.int64, device=dev)
     # 6. the partials of every user back to its rank in one all-to-all; the finalize reads the receive buffer in place: list w of user
@@ -744,6 +752,19 @@ def make_sharded_engine(base_cls):
             self.sync_moving_stats()
             return super()._infer(users, items, labels, n)
 
+        def _owner_catalog(self, users, items):
+            """What the collectives recommend and full_auc set up alike: -> (users, items, folded tower, and the three callables
+            *_at_owners take: user rows through gather_global_rows, the user projection of fetched rows, the column-major item
+            projection of local rows)"""
+            users, items = self._catalog_ids(users, items, every_item=False)
+            self.sync_moving_stats()
+            th, tower = self._catalog_tower()
+            D, dev = self.cfg.dim, self.device
+            fetch = lambda ids: gather_global_rows(self.ctx, ids, lambda loc: ops.gather_rows([self.fused["user"]], [loc], err_flag=self.err)[0], 2 * D)
+            queries_of = lambda rows: self._catalog_project(th, rows, torch.arange(rows.shape[0], dtype=torch.int32, device=dev), True)
+            candidates_of = lambda loc: self._catalog_project(th, self.fused["item"], loc, False)
+            return users, items, tower, fetch, queries_of, candidates_of
+
         def recommend(self, users, k, items=None, exclude=None, dump_logits=None):
             """NeuMFEngine.recommend on the row-sharded tables (recommend_at_owners): a collective - every rank calls it with its own
             users (any number, also none), the same `items` and k, and gets the single-device lists of ITS users bit for bit.  Every
@@ -751,29 +772,28 @@ def make_sharded_engine(base_cls):
             if dump_logits:
                 raise NotImplementedError("recommend(dump_logits=True) on the row-sharded engine is not supported: no rank forms the "
                                           "logits of another owner's items; score with a single-device engine")
-            cfg, dev = self.cfg, self.device
-            D, (n1, n2, n3) = cfg.dim, cfg.hidden
-            self.flush()                         # deferred-Adam rows lag until then (as _infer)
-            self.sync_moving_stats()
-            users = torch.as_tensor(users, device=dev)
-            if users.dtype not in (torch.int32, torch.int64):
-                users = users.to(self.id_dtype)
-            if items is not None:
-                items = torch.as_tensor(items, device=dev)
-                items = (items if items.dtype == users.dtype else items.to(users.dtype)).contiguous()
-            th = {name: self.theta.view(name) for name in self.theta.offsets}
-            tower = ops.neumf_catalog_fold(th, self.moving, n1, n2, n3, cfg.mf_first, cfg.bn_eps)
+            cfg, hidden = self.cfg, tuple(self.cfg.hidden)
+            users, items, tower, fetch, queries_of, candidates_of = self._owner_catalog(users, items)
+            return recommend_at_owners(self.ctx, users, items, self.num_item_rows, k, exclude, fetch, queries_of, candidates_of,
+                                       lambda q, c, kk, ex: ops.neumf_catalog_topk(q, c, tower, cfg.dim, hidden, cfg.act, kk, exclude=ex))
 
-            def queries_of(rows):
-                ar = torch.arange(rows.shape[0], dtype=torch.int32, device=dev)
-                return ops.neumf_catalog_project(rows, ar, th["W1"], n1, D, cfg.item_first, True, b1=th["b1"], err_flag=self.err)
-
-            return recommend_at_owners(
-                self.ctx, users.contiguous(), items, self.num_item_rows, k, exclude,
-                lambda ids: gather_global_rows(self.ctx, ids, lambda loc: ops.gather_rows([self.fused["user"]], [loc], err_flag=self.err)[0], 2 * D),
-                queries_of,
-                lambda loc: ops.neumf_catalog_project(self.fused["item"], loc, th["W1"], n1, D, cfg.item_first, False, col_major=True, err_flag=self.err),
-                lambda q, c, kk, ex: ops.neumf_catalog_topk(q, c, tower, D, (n1, n2, n3), cfg.act, kk, exclude=ex))
+        def full_auc(self, users, truth, items=None, dump_probs=False, method="fused"):
+            """NeuMFEngine.full_auc on the row-sharded tables (auc_at_owners): a collective - every rank calls it with its own users
+            (any number, also none), their truth CSR and the same `items`, and gets the single-device floats of ITS users bit for bit.
+            Every owner projects, scores and counts only the items whose rows it holds; user rows, the positives' probabilities and
+            one integer count per user travel."""
+            if dump_probs:
+                raise NotImplementedError("full_auc(dump_probs=True) on the row-sharded engine is not supported: no rank forms the "
+                                          "probabilities of another owner's items; score with a single-device engine")
+            if method != "fused":
+                raise NotImplementedError(f"full_auc(method={method!r}) on the row-sharded engine is not supported: predict is a collective "
+                                          "over pairs, every rank's tables hold a share of the rows; use method='fused'")
+            cfg, hidden = self.cfg, tuple(self.cfg.hidden)
+            users, items, tower, fetch, queries_of, candidates_of = self._owner_catalog(users, items)
+            return auc_at_owners(
+                self.ctx, users, items, self.num_item_rows, truth, fetch, queries_of, candidates_of,
+                positives=lambda q, c, po, pi, out: ops.neumf_auc_positives(q, c, tower, cfg.dim, hidden, cfg.act, po, pi, out=out),
+                count=lambda q, c, so, si, lo, srt, pc: ops.neumf_auc_count(q, c, tower, cfg.dim, hidden, cfg.act, so, si, lo, srt, pc))
 
         def _embed_backward_apply(self, users, items, B):
             cfg, D = self.cfg, self.cfg.dim

@@ -584,6 +584,44 @@ int brDotAucOwnerCount(const float* Q, int64_t ld_q, int64_t n_users, const floa
 int brAucFinalizeLists(const uint64_t* part, int64_t list_stride, int n_lists, const int64_t* truth_off, const int32_t* pcnt,
                        int64_t n_users, int64_t n_items, float* out_auc, brStream stream);
 
+/* ---- Catalogue AUC for NeuMF, single-device and at the item owners: csrc/auc_neumf.hip -------------------------------------------------
+ * Stands in for full_auc (src/models/bpr.py:230-254) over the NeuMF graph: every (user, item) pair through model.predict as
+ * predictForUser does for one user (src/models/NeuMFModel.py:133-150), then roc_auc_score per user - without the U x I matrix.
+ * Operands as brNeumfCatalogTopK: pu [n_users][ld_u] (brNeumfCatalogProject, row-major, copy_mf), pit [n1 + dim][ld_i] (col_major,
+ * copy_mf), tower of brNeumfCatalogFold, act = BR_ACT_*.  The score of a pair is the head's sigmoid output in inference mode, formed by
+ * brNeumfCatalogTopK's operation sequence: it equals that entry's dump_probs bit for bit and depends on the user row, the item column and
+ * the tower only.  Limits: those of brNeumfCatalogTopK (2*dim <= 256, n1, n2 <= 128, n3 <= 32, 1 <= n_items < 2^31, ld_u >= n1 + dim,
+ * ld_i >= n_items); BR_ERR_ARG / BR_ERR_WORKSPACE before any launch; n_users == 0 is BR_OK; no allocation and no sync inside.
+ * brNeumfAucPositives: bpr.py:230-254, NeuMFModel.py:133-150 for the pairs (user, positive) alone.  (pos_off (n_users + 1), pos_idx):
+ *   per user its positives among these candidates, positions into pit (LOCAL ones on a row-sharded engine: brCsrSplitByOwner).
+ *   raw[pos_off[u] + j] = score(u, the user's j-th entry); an entry outside [0, n_items) scores NaN.  raw holds pos_off[n_users] floats.
+ * brNeumfAucCount: bpr.py:230-254, NeuMFModel.py:133-150: the catalogue pass over these candidates with two CSRs in two roles, as
+ *   brDotAucOwnerCount: (skip_off, skip_idx) the positives among THESE candidates, ascending positions, skipped; list_off / sorted /
+ *   pcnt / cap of brAucSortPieces: the user's FULL list every other score is counted against (2P' below its minimum, 0 above its
+ *   maximum, 2 #{> s} + #{== s} inside; a NaN score adds 0).  out_w2[u]: the user's 2W over these candidates, uint64, the item splits
+ *   already summed in integers; no float atomics.  dump_probs (optional, n_users x n_items): every pair's score (tests).
+ *   ws: brNeumfAucCountWorkspaceBytes(n_users, n_items) bytes (the per-split partials); -1 outside the limits.
+ * brNeumfCatalogAuc: bpr.py:230-254, NeuMFModel.py:133-150: the single-device call, four phases chained inside the library:
+ *   brNeumfAucPositives, brAucSortPieces with one piece, brNeumfAucCount, brAucFinalizeLists with one list.  truth_off (n_users + 1) /
+ *   truth_idx: per user the ascending, unique positions into the item list of its positives (ops.truth_csr, the CSR of brFullAuc).
+ *   out_auc[u] = (float)((double)W / ((double)P (double)N)) with P = the user's truth entries and N = n_items - P: bit for bit brFullAuc
+ *   on the same scores (while P N < 2^53).  NaN for P == 0 or N == 0.  A NaN score gets no credit on either side.  dump_probs as above.
+ *   ws: brNeumfCatalogAucWorkspaceBytes(n_users, n_items, truth_off[n_users]) bytes (per-split partials, the raw and the sorted positive
+ *   scores and the sort's scratch); -1 for sizes outside the limits.  The truth entries the workspace cannot hold (and any past
+ *   2^31 - 1) are never written: their users get NaN.  The user's positives are sorted by counting rank, O(P^2) compares per user. */
+int brNeumfAucPositives(const float* pu, int64_t ld_u, int64_t n_users, const float* pit, int64_t ld_i, int64_t n_items, int dim, int n1,
+                        int n2, int n3, int act, const float* tower, const int64_t* pos_off, const int32_t* pos_idx, float* raw,
+                        brStream stream);
+int64_t brNeumfAucCountWorkspaceBytes(int64_t n_users, int64_t n_items);
+int brNeumfAucCount(const float* pu, int64_t ld_u, int64_t n_users, const float* pit, int64_t ld_i, int64_t n_items, int dim, int n1, int n2,
+                    int n3, int act, const float* tower, const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off,
+                    const float* sorted, const int32_t* pcnt, int64_t cap, uint64_t* out_w2, float* dump_probs, void* ws, int64_t ws_bytes,
+                    brStream stream);
+int64_t brNeumfCatalogAucWorkspaceBytes(int64_t n_users, int64_t n_items, int64_t n_truth);
+int brNeumfCatalogAuc(const float* pu, int64_t ld_u, int64_t n_users, const float* pit, int64_t ld_i, int64_t n_items, int dim, int n1,
+                      int n2, int n3, int act, const float* tower, const int64_t* truth_off, const int32_t* truth_idx, float* out_auc,
+                      float* dump_probs, void* ws, int64_t ws_bytes, brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the

@@ -1,0 +1,636 @@
+"""-m gpu: the fused full-catalogue AUC for NeuMF (csrc/auc_neumf.hip, NeuMFEngine.full_auc, ShardedNeuMFEngine.full_auc,
+NeuMFModel.full_auc / mean_average_precision_k).
+
+The kernel-level tests allow no tolerance: the per-user AUC equals brFullAuc of the dumped probabilities BIT FOR BIT with NaN in the
+same places, the dump equals brNeumfCatalogTopK's dump_probs bit for bit (what keeps the two copies of the scoring loop the same), and W
+owners over parts of the candidates give the single launch's floats.  Where another summation order enters (float64, the pair path) the
+allowed difference per user is derived in the test from the scores themselves (_flip_bound).
+
+Two ranks on one card over gloo (child processes, each under its own time limit, never run again)."""
+import importlib.util
+import os
+import socket
+import sys
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from oracle import binrec_oracle as O
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+LDS_CAP = 1024          # kNeumfAucLdsCap: a user's sorted positives sit in LDS up to this many
+
+
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+R = _load("test_sharded_auc_cpu")        # owner_maps / built_users / sharded_auc_ref: the numpy restatement
+
+
+def _m(name):
+    return import_module("binary-recommendation_amd." + name)
+
+
+def _equal(a, b):
+    """bit for bit, NaN in the same places"""
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(a[~torch.isnan(a)], b[~torch.isnan(b)])
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _params(variant, dim, U, I, seed, hidden=None):
+    """test_gpu_recommend._params with the tower widths free: every BatchNorm term away from identity, spread-out tables"""
+    spec = O.NeuMFSpec(variant, dim=dim, hidden=hidden)
+    p = O.neumf_init(spec, U, I, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    n1, n2, n3 = spec.hidden
+    for t in ("user_mlp", "item_mlp", "user_mf", "item_mf"):
+        p[t] = (p[t] * 12).astype(np.float32)
+    for i, n in ((1, n1), (2, n2)):
+        p[f"g{i}"] = rng.uniform(0.5, 1.5, n).astype(np.float32)
+        p[f"be{i}"] = rng.uniform(-0.3, 0.3, n).astype(np.float32)
+        p[f"mm{i}"] = rng.uniform(0.05, 0.6, n).astype(np.float32)
+        p[f"mv{i}"] = rng.uniform(0.05, 0.5, n).astype(np.float32)
+    for b, n in (("b1", n1), ("b2", n2), ("b3", n3), ("b4", 1)):
+        p[b] = rng.uniform(-0.2, 0.2, n).astype(np.float32)
+    return spec, p
+
+
+def _engine(dev, variant, dim, U, I, seed=3, id_dtype=torch.int32, hidden=None, p=None, **kw):
+    neumf = _m("neumf")
+    spec, p0 = _params(variant, dim, U, I, seed, hidden)
+    p = p0 if p is None else p
+    eng = neumf.NeuMFEngine(neumf.NeuMFConfig(variant, dim=dim, hidden=hidden, **kw), U, I, dev, max_batch=4096, id_dtype=id_dtype)
+    eng.load_numpy_params(p)
+    return spec, p, eng
+
+
+def _operands(eng, users, items):
+    """what NeuMFEngine.recommend / full_auc hand to the fused launch: (pu, pit, tower) and the trailing (dim, hidden, act)"""
+    ops, cfg = _m("ops"), eng.cfg
+    th = {n: eng.theta.view(n) for n in eng.theta.offsets}
+    tower = ops.neumf_catalog_fold(th, eng.moving, *cfg.hidden, cfg.mf_first, cfg.bn_eps)
+    pu = pit = None
+    if users is not None:
+        pu = ops.neumf_catalog_project(eng.fused["user"], users, th["W1"], cfg.hidden[0], cfg.dim, cfg.item_first, True, b1=th["b1"], err_flag=eng.err)
+    if items is not None:
+        pit = ops.neumf_catalog_project(eng.fused["item"], items, th["W1"], cfg.hidden[0], cfg.dim, cfg.item_first, False, col_major=True,
+                                        err_flag=eng.err)
+    return pu, pit, tower, (cfg.dim, tuple(cfg.hidden), cfg.act)
+
+
+def _built_users(rng, I):
+    """constructed, as R.built_users: 0 no positives, 1 every candidate positive (N = 0, P past the LDS cap), 2 P = 1, 3 P = 70 (> 64: two
+    steps of the positives' kernel), 4 P past the LDS cap, 5.. random lists; 9 users (not a multiple of 4) -> (off, idx) numpy"""
+    assert I > LDS_CAP + 100
+    rows = [np.empty(0, np.int64), np.arange(I), np.array([int(rng.integers(0, I))]), np.sort(rng.choice(I, 70, replace=False)),
+            np.sort(rng.choice(I, LDS_CAP + 76, replace=False))]
+    for _ in range(4):
+        rows.append(np.sort(rng.choice(I, int(rng.integers(2, I // 3)), replace=False)))
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    return off, np.concatenate(rows).astype(np.int32)
+
+
+def _dev_csr(off, idx, dev):
+    return torch.from_numpy(np.asarray(off, np.int64)).to(dev), torch.from_numpy(np.asarray(idx, np.int32)).to(dev)
+
+
+def _flip_bound(probs64, off, idx, bar):
+    """The most a user's AUC can move when every probability moves by up to `bar` relative: a (positive, other) pair can change its
+    order (or enter / leave a tie) only if the two values lie closer together than the sum of their bars, and one such pair moves the
+    statistic W by at most 1 of the P N it is divided by.  So the bound is the share of such pairs.  probs64 (U, I) float64 numpy ->
+    (bound (U,), pairs examined)"""
+    out = np.zeros(len(off) - 1)
+    for u in range(len(off) - 1):
+        pos = np.zeros(probs64.shape[1], bool)
+        pos[idx[off[u]:off[u + 1]]] = True
+        a, b = probs64[u][pos], np.sort(probs64[u][~pos])
+        if len(a) == 0 or len(b) == 0:
+            continue
+        # others b with |a - b| <= bar (|a| + |b|)  <=>  a (1 - bar) / (1 + bar) <= b <= a (1 + bar) / (1 - bar) for a, b >= 0
+        lo = np.searchsorted(b, a * (1 - bar) / (1 + bar), "left")
+        hi = np.searchsorted(b, a * (1 + bar) / (1 - bar), "right")
+        out[u] = (hi - lo).sum() / (len(a) * len(b))
+    return out
+
+
+F32_EPS = float(np.finfo(np.float32).eps)      # the result is rounded to float32 once
+
+
+# --------------------------------------------------------------------------------------------------------------- 1, 2: bit for bit
+CASES = [("A", 10, None, torch.int32), ("A", 64, None, torch.int64), ("B", 32, None, torch.int32), ("B", 64, None, torch.int64),
+         ("B", 128, None, torch.int32), ("A", 32, (100, 96, 10), torch.int64), ("B", 64, (128, 128, 32), torch.int32),
+         ("A", 10, (24, 8, 4), torch.int32), ("B", 16, (40, 40, 8), torch.int64), ("A", 32, (32, 24, 8), torch.int32),
+         ("B", 64, (64, 48, 8), torch.int64)]
+# the padded second-layer widths the kernels are instantiated at, each reached once: A's default tower (100, 50, 10) is 56, B's
+# (dim, dim / 2, dim / 4) is 16 / 32 / 64 at dims 32 / 64 / 128, the given towers are 96, 128, 8, 40, 24 and 48
+
+
+@pytest.mark.parametrize("variant,dim,hidden,idt", CASES)
+def test_bit_exact_against_full_auc_of_the_dump(dev, variant, dim, hidden, idt):
+    ops = _m("ops")
+    rng = np.random.default_rng(dim + (0 if hidden is None else hidden[1]))
+    I = 1237                                                          # not a multiple of 64
+    items = rng.permutation(I + 100)[:I]
+    spec, p, eng = _engine(dev, variant, dim, 50, I + 100, seed=dim, id_dtype=idt, hidden=hidden)
+    off, idx = _built_users(rng, I)
+    U = len(off) - 1
+    assert U % 4 and I % 64
+    users = torch.as_tensor(rng.integers(0, 50, U), dtype=idt, device=dev)
+    pu, pit, tower, tail = _operands(eng, users, torch.as_tensor(items, dtype=idt, device=dev))
+    toff, tidx = _dev_csr(off, idx, dev)
+    auc, dump = ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx, dump_probs=True)
+    eng.check_ids()
+    assert torch.isnan(auc[:2]).all() and not torch.isnan(auc[2:]).any()
+    assert _equal(auc, ops.full_auc(dump, toff, tidx))
+    assert _equal(auc, ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx))
+    probs = ops.neumf_catalog_topk(pu, pit, tower, tail[0], tail[1], tail[2], 10, dump_probs=True)[2]
+    assert _same_bits(dump, probs)                                    # the two copies of the scoring loop are one function
+    assert R.same_bits(auc.cpu().numpy(), R.oracle_auc(dump.cpu().numpy(), off, idx, np.arange(I)))
+    # the engine surface returns the same
+    e_auc, e_dump = eng.full_auc(users, (toff, tidx), items=torch.as_tensor(items, dtype=idt, device=dev), dump_probs=True)
+    assert _equal(e_auc, auc) and _same_bits(e_dump, dump)
+
+
+@pytest.mark.parametrize("variant,dim,hidden", [("A", 10, None), ("B", 64, None), ("B", 64, (128, 128, 32))])
+def test_positives_equal_the_dump_at_the_truth_positions(dev, variant, dim, hidden):
+    ops = _m("ops")
+    rng = np.random.default_rng(dim)
+    I = 1237
+    spec, p, eng = _engine(dev, variant, dim, 50, I, seed=dim + 1, hidden=hidden)
+    off, idx = _built_users(rng, I)
+    U = len(off) - 1
+    users = torch.as_tensor(rng.integers(0, 50, U), dtype=torch.int32, device=dev)
+    pu, pit, tower, tail = _operands(eng, users, torch.arange(I, dtype=torch.int32, device=dev))
+    toff, tidx = _dev_csr(off, idx, dev)
+    _auc, dump = ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx, dump_probs=True)
+    raw = ops.neumf_auc_positives(pu, pit, tower, *tail, toff, tidx)
+    rows = torch.from_numpy(np.repeat(np.arange(U), np.diff(off))).to(dev)
+    assert _same_bits(raw[:len(idx)], dump[rows, tidx.long()])
+    # entries outside [0, I) score NaN, their neighbours keep their scores
+    bad = idx.copy()
+    where = [int(off[2]), int(off[3]) + 5, int(off[4]) + 64, len(idx) - 1]
+    bad[where] = [I, -1, I + 7, -(1 << 31)]
+    raw2 = ops.neumf_auc_positives(pu, pit, tower, *tail, toff, torch.from_numpy(bad).to(dev))
+    keep = np.ones(len(idx), bool); keep[where] = False
+    assert torch.isnan(raw2[torch.tensor(where, device=dev)]).all()
+    assert _same_bits(raw2[:len(idx)][torch.from_numpy(keep).to(dev)], raw[:len(idx)][torch.from_numpy(keep).to(dev)])
+
+
+# --------------------------------------------------------------------------------------------------------------- 3, 4: ties, non-finite
+def test_ties(dev):
+    ops = _m("ops")
+    rng = np.random.default_rng(3)
+    I, U = 1500, 21
+    # duplicated candidates: positions 200 .. 899 name five item rows only, so equal probabilities on both sides of the truth
+    items = rng.permutation(I)
+    items[200:900] = items[np.arange(200, 900) % 5]
+    rows = [np.sort(rng.choice(I, int(rng.integers(1, 400)), replace=False)) for _ in range(U)]
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    idx = np.concatenate(rows).astype(np.int32)
+    toff, tidx = _dev_csr(off, idx, dev)
+    users = torch.arange(U, dtype=torch.int32, device=dev)
+    for variant, saturate in (("A", False), ("B", False), ("A", True), ("B", True)):
+        spec, p = _params(variant, 32, 50, I, seed=9)
+        if saturate:          # a head that saturates: z = 3000 x the GMF dot, so most probabilities are exactly 0.0f or 1.0f
+            p = dict(p)
+            w4 = np.zeros_like(p["W4"])
+            w4.reshape(-1)[0 if spec.head_concat[0] == "mf" else -1] = 3000.0
+            p["W4"], p["b4"] = w4, np.zeros_like(p["b4"])
+        _s, _p, eng = _engine(dev, variant, 32, 50, I, seed=9, p=p)
+        pu, pit, tower, tail = _operands(eng, users, torch.as_tensor(items, dtype=torch.int32, device=dev))
+        auc, dump = ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx, dump_probs=True)
+        d = dump.cpu().numpy()
+        assert np.array_equal(d[:, 200:900].view(np.int32), d[:, np.arange(200, 900) % 5].view(np.int32))      # equal bits, many times
+        if saturate:
+            assert (d == 0.0).mean() > 0.25 and (d == 1.0).mean() > 0.25, ((d == 0.0).mean(), (d == 1.0).mean())
+        assert not torch.isnan(auc).any()
+        assert _equal(auc, ops.full_auc(dump, toff, tidx)), (variant, saturate)
+        assert R.same_bits(auc.cpu().numpy(), R.oracle_auc(d, off, idx, np.arange(I)))
+
+
+def test_non_finite_scores(dev):
+    """an item row with a NaN and one with an Inf in their mf halves, each a positive of some users and a negative of the others"""
+    ops = _m("ops")
+    rng = np.random.default_rng(4)
+    I, U, dim = 700, 24, 32
+    for variant in ("A", "B"):
+        spec, p, eng = _engine(dev, variant, dim, 50, I, seed=12)
+        eng.fused["item"][10, dim + 3] = float("nan")
+        eng.fused["item"][11, dim + 5] = float("inf")
+        eng.fused["item"][12, dim] = float("-inf")
+        items = rng.permutation(I)
+        where = np.empty(I, np.int64); where[items] = np.arange(I)
+        rows = []
+        for u in range(U):
+            base = set(rng.choice(I, 15, replace=False).tolist()) - {int(where[10]), int(where[11]), int(where[12])}
+            for bit, i in enumerate((10, 11, 12)):
+                if (u >> bit) & 1:
+                    base.add(int(where[i]))
+            rows.append(np.sort(np.fromiter(base, np.int64)))
+        off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        idx = np.concatenate(rows).astype(np.int32)
+        toff, tidx = _dev_csr(off, idx, dev)
+        users = torch.arange(U, dtype=torch.int32, device=dev)
+        pu, pit, tower, tail = _operands(eng, users, torch.as_tensor(items, dtype=torch.int32, device=dev))
+        auc, dump = ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx, dump_probs=True)
+        assert torch.isnan(dump[:, int(where[10])]).all()
+        for i in (11, 12):       # an infinite logit is a probability of exactly 0 or 1 (or NaN where inf met a zero)
+            col = dump[:, int(where[i])]
+            assert (torch.isnan(col) | (col == 0) | (col == 1)).all()
+        assert _equal(auc, ops.full_auc(dump, toff, tidx)), variant
+        assert R.same_bits(auc.cpu().numpy(), R.oracle_auc(dump.cpu().numpy(), off, idx, np.arange(I)))
+        raw = ops.neumf_auc_positives(pu, pit, tower, *tail, toff, tidx)
+        rws = torch.from_numpy(np.repeat(np.arange(U), np.diff(off))).to(dev)
+        assert _equal(raw[:len(idx)], dump[rws, tidx.long()])
+
+
+# --------------------------------------------------------------------------------------------------------------- 5: plan independence
+def test_plan_independence(dev):
+    """the same users alone and inside a larger list, and one user against the whole catalogue (many item splits): the same bits"""
+    ops, A = _m("ops"), _load("test_gpu_auc_dot")
+    U, I = 600, 20000
+    spec, p, eng = _engine(dev, "A", 64, U, I, seed=5)
+    sizes = np.random.default_rng(5).integers(0, 40, U)
+    sizes[7] = LDS_CAP + 300
+    off, idx = A._truth(sizes, I, dev, seed=5)
+    users = torch.arange(U, dtype=torch.int32, device=dev)
+    pu, pit, tower, tail = _operands(eng, users, torch.arange(I, dtype=torch.int32, device=dev))
+    full = ops.neumf_catalog_auc(pu, pit, tower, *tail, off, idx)
+    o, x = off.cpu().numpy(), idx.cpu().numpy()
+    for u in (0, 1, 7, 257, U - 1):
+        t = torch.from_numpy(x[o[u]:o[u + 1]]).to(dev)
+        one = ops.neumf_catalog_auc(pu[u:u + 1], pit, tower, *tail, torch.tensor([0, len(t)], dtype=torch.int64, device=dev), t)
+        assert _equal(one, full[u:u + 1]), u
+    some = np.array([7, 3, 599, 100, 101, 102, 8])                        # 7 users: another grid, other splits
+    so, sx = ops.truth_csr(len(some), np.repeat(np.arange(len(some)), sizes[some]), np.concatenate([x[o[u]:o[u + 1]] for u in some]), dev)
+    part = ops.neumf_catalog_auc(pu[torch.from_numpy(some).to(dev)].contiguous(), pit, tower, *tail, so, sx)
+    assert _equal(part, full[torch.from_numpy(some).to(dev)])
+
+
+# --------------------------------------------------------------------------------------------------------------- 6: float64
+def _oracle_probs(spec, p, users, items):
+    uu = np.repeat(users, len(items)); ii = np.tile(items, len(users))
+    return O.neumf_forward(spec, p, uu, ii, training=False, dt=np.float64)["prob"].reshape(len(users), len(items)).astype(np.float64)
+
+
+@pytest.mark.parametrize("variant,dim", [("A", 64), ("B", 32)])
+def test_against_float64(dev, variant, dim):
+    """Against O.full_auc of O.neumf_forward in float64.  The allowed difference per user is derived, not chosen: DESIGN.md 2 holds every
+    probability to 1e-5 relative of the float64 one, so only (positive, other) pairs whose float64 probabilities lie closer together
+    than twice that bar can change order, each moving the AUC by at most 1 / (P N) (_flip_bound); plus the one rounding to float32."""
+    ops = _m("ops")
+    rng = np.random.default_rng(dim)
+    U, I = 24, 3000
+    spec, p, eng = _engine(dev, variant, dim, 60, I + 50, seed=21)
+    users, items = rng.integers(0, 60, U), rng.permutation(I + 50)[:I]
+    rows = [np.sort(rng.choice(I, int(rng.integers(1, 60)), replace=False)) for _ in range(U)]
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    idx = np.concatenate(rows).astype(np.int32)
+    toff, tidx = _dev_csr(off, idx, dev)
+    got = eng.full_auc(torch.as_tensor(users, dtype=torch.int32, device=dev), (toff, tidx), items=torch.as_tensor(items, dtype=torch.int32, device=dev))
+    eng.check_ids()
+    p64 = _oracle_probs(spec, p, users, items)
+    it = [int(i) for i in items]
+    gt = [(int(users[u]), [it[j] for j in idx[off[u]:off[u + 1]]]) for u in range(U)]
+    _mean, want = O.full_auc([p64[u] for u in range(U)], gt, it)
+    bound = _flip_bound(p64, off, idx, 1e-5) + F32_EPS
+    diff = np.abs(got.double().cpu().numpy() - np.asarray(want))
+    print(f"float64 [{variant} dim {dim}]: max |auc - float64| = {diff.max():.3e}, max bound = {bound.max():.3e}, "
+          f"max observed / bound = {(diff / bound).max():.3f}")
+    assert (diff <= bound).all(), (diff, bound)
+
+
+# --------------------------------------------------------------------------------------------------------------- 7: the engine
+def test_engine_fused_against_pairs(dev):
+    """method="pairs" (chunked predict, the U x I matrix, brFullAuc) sums in another order, so its probabilities differ from the fused
+    ones within DESIGN.md 2's 1e-5 relative each: a (positive, other) pair can order differently only if its two pair-path
+    probabilities lie within the sum of twice their bars (either side may have moved), each such pair moving the AUC by at most
+    1 / (P N) (_flip_bound with bar 2e-5 on the pair path's own matrix); plus one float32 rounding on each side."""
+    A = _load("test_gpu_auc_dot")
+    U, I = 64, 5000
+    spec, p, eng = _engine(dev, "A", 64, U, I, seed=30)
+    eng.PAIR_CHUNK = 1 << 16                                        # several predict chunks
+    users = torch.arange(U, dtype=torch.int32, device=dev)
+    sizes = np.random.default_rng(30).integers(0, 50, U)
+    truth = A._truth(sizes, I, dev, seed=30)
+    fused = eng.full_auc(users, truth)
+    pairs, probs = eng.full_auc(users, truth, method="pairs", dump_probs=True)
+    eng.check_ids()
+    assert fused.shape == (U,) and fused.dtype == torch.float32 and fused.device == probs.device
+    assert torch.equal(torch.isnan(fused), torch.isnan(pairs)) and torch.equal(torch.isnan(fused).cpu(), torch.from_numpy(sizes == 0))
+    bound = _flip_bound(probs.double().cpu().numpy(), truth[0].cpu().numpy(), truth[1].cpu().numpy(), 2e-5) + 2 * F32_EPS
+    ok = ~torch.isnan(fused).cpu().numpy()
+    diff = np.abs(fused.double().cpu().numpy() - pairs.double().cpu().numpy())[ok]
+    print(f"fused against pairs: max diff = {diff.max():.3e}, max bound = {bound[ok].max():.3e}, max observed / bound = {(diff / bound[ok]).max():.3f}")
+    assert (diff <= bound[ok]).all()
+    with pytest.raises(ValueError):
+        eng.full_auc(users, truth, method="matrix")
+
+
+def test_engine_flushes_deferred_rows_and_checks_ids(dev):
+    A, N = _load("test_gpu_auc_dot"), _load("test_gpu_neumf")
+    B, U, I = 48, 1500, 400
+    sw, de = N._two_engines(dev, B, U, I)                            # the same model by per-step sweep and by deferred replay ("exact")
+    rng = np.random.default_rng(5)
+    td = lambda a, dt: torch.from_numpy(a).to(dev).to(dt)
+    for step in range(6):
+        uu, ii = rng.integers(0, U, B), rng.integers(0, I, B)
+        yy = (rng.random(B) < 0.3).astype(np.float32)
+        for e in (sw, de):
+            e.train_step(td(uu, torch.int32), td(ii, torch.int32), td(yy, torch.float32))
+    assert de.deferred and de._stale
+    users = torch.arange(0, 1500, 5, dtype=torch.int32, device=dev)
+    truth = A._truth(np.random.default_rng(2).integers(0, 30, 300), I, dev, seed=2)
+    a = de.full_auc(users, truth)                                    # no explicit flush: full_auc flushes
+    assert _equal(a, sw.full_auc(users, truth))
+    de.flush()
+    assert _equal(a, de.full_auc(users, truth))
+    assert _equal(a, de.full_auc(users.long(), truth, items=torch.arange(I, dtype=torch.int64, device=dev)))
+    de.check_ids()
+    # an id out of range raises through check_ids, it does not fault
+    de.full_auc(torch.tensor([0, U], dtype=torch.int32, device=dev), A._truth([1, 1], I, dev))
+    with pytest.raises(IndexError):
+        de.check_ids()
+    de.full_auc(users[:2], A._truth([1, 1], 2, dev), items=torch.tensor([1, -1], dtype=torch.int32, device=dev))
+    with pytest.raises(IndexError):
+        de.check_ids()
+
+
+def test_engine_full_auc_memory(dev):
+    """the allocator's peak rise stays far below the U x I matrix (test_gpu_auc_dot.py::test_bpr_full_auc_memory's check)"""
+    neumf, A = _m("neumf"), _load("test_gpu_auc_dot")
+    U, I = 8192, 100000
+    eng = neumf.NeuMFEngine(neumf.NeuMFConfig("A", dim=64), U, I, dev, max_batch=1024)
+    users = torch.arange(U, dtype=torch.int32, device=dev)
+    truth = A._truth(np.full(U, 20), I, dev, seed=7)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    auc = eng.full_auc(users, truth)
+    torch.cuda.synchronize()
+    eng.check_ids()
+    rise = torch.cuda.max_memory_allocated(dev) - before
+    assert rise < U * I * 4 / 8, rise
+    assert auc.shape == (U,) and not torch.isnan(auc).any()
+
+
+# --------------------------------------------------------------------------------------------------------------- 8: virtual ranks
+def _through_owners(dev, W, items, eng, users, off, idx, idt, order=None, dump=None, pad=0):
+    """test_gpu_sharded_auc._through_owners with the NeuMF phases: the four phases over the W parts of `items` (every owner projects the
+    candidates it holds) -> (auc (U,), sorted, pcnt).  order: the order the owners' pieces lie in the sort's input; dump: the whole
+    launch's (U, I) probabilities, every part's dump is held to its columns; pad: padding in the strided buffers"""
+    ops = _m("ops")
+    maps, g2l = R.owner_maps(items, W)
+    toff, tidx = _dev_csr(off, idx, dev)
+    ids = torch.as_tensor(items, dtype=idt, device=dev)
+    U, T = users.shape[0], len(idx)
+    pu, _none, tower, tail = _operands(eng, users, None)
+    parts, raws, lens = {}, [], []
+    for r in range(W):
+        if len(maps[r]) == 0:               # an owner without a candidate of the list: no piece, a zero count
+            raws.append(torch.empty(0, device=dev)); lens.append(torch.zeros(U, dtype=torch.int64, device=dev))
+            continue
+        pit = _operands(eng, None, ids[torch.from_numpy(maps[r].astype(np.int64)).to(dev)].contiguous())[1]
+        po, pi = ops.csr_split_by_owner(toff, tidx, torch.from_numpy(g2l[r]).to(dev))
+        raw = ops.neumf_auc_positives(pu, pit, tower, *tail, po, pi)
+        parts[r] = (pit, po, pi)
+        raws.append(raw[:int(po[-1])]); lens.append(po[1:] - po[:-1])
+    order = list(range(W)) if order is None else list(order)
+    m = max(1, max(x.numel() for x in raws)) + pad
+    buf = torch.full((W, m), 123.0, device=dev)                          # the all-gather's receive buffer, padded rows
+    piece_off = torch.zeros(W, U + 1, dtype=torch.int64, device=dev)
+    for slot, r in enumerate(order):
+        buf[slot, :raws[r].numel()] = raws[r]
+        piece_off[slot, 1:] = lens[r].cumsum(0)
+        piece_off[slot] += slot * m
+    sorted_, pcnt = ops.auc_sort_pieces(buf, piece_off, toff, T)
+    stride = U + pad
+    w2 = torch.full((W * stride,), 7, dtype=torch.int64, device=dev)       # (the pads must never be read)
+    for r in range(W):
+        if r in parts:
+            pit, po, pi = parts[r]
+            got = ops.neumf_auc_count(pu, pit, tower, *tail, po, pi, toff, sorted_, pcnt, dump_probs=dump is not None)
+            if dump is not None:
+                got, d = got
+                assert _same_bits(d, dump[:, torch.from_numpy(maps[r].astype(np.int64)).to(dev)])
+            w2[r * stride:r * stride + U] = got
+        else:
+            w2[r * stride:r * stride + U] = 0
+    return ops.auc_finalize_lists(w2, W, U, toff, pcnt, len(items), list_stride=stride), sorted_, pcnt
+
+
+@pytest.mark.parametrize("W", [1, 2, 3, 8])
+@pytest.mark.parametrize("variant,dim,idt", [("A", 64, torch.int32), ("B", 32, torch.int64)])
+def test_virtual_ranks_equal_the_single_launch(dev, W, variant, dim, idt):
+    """a shuffled subset of the rows as candidates, dealt to W owners by id mod W; R.built_users (no positives, every candidate, all on
+    owner 0, all on the last owner, P > 64 and P past the LDS cap); every part's dump against the whole dump; pieces in another order"""
+    ops = _m("ops")
+    rng = np.random.default_rng(7 * W + dim)
+    rows, I = 4000, 2600
+    spec, p, eng = _engine(dev, variant, dim, 50, rows, seed=dim + W, id_dtype=idt)
+    items = rng.permutation(rows)[:I]
+    off, idx = R.built_users(rng, items, W, big=(100, LDS_CAP + 500))
+    U = len(off) - 1
+    users = torch.as_tensor(rng.integers(0, 50, U), dtype=idt, device=dev)
+    toff, tidx = _dev_csr(off, idx, dev)
+    pu, pit, tower, tail = _operands(eng, users, torch.as_tensor(items, dtype=idt, device=dev))
+    want, dump = ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx, dump_probs=True)
+    got, _s, pcnt = _through_owners(dev, W, items, eng, users, off, idx, idt, dump=dump, pad=3)
+    eng.check_ids()
+    assert torch.isnan(want[:2]).all() and not torch.isnan(want[4:]).any()
+    assert _equal(got, want), (got, want)
+    assert pcnt.cpu().tolist() == np.diff(off).tolist()
+    assert R.same_bits(got.cpu().numpy(), R.sharded_auc_ref(dump.cpu().numpy(), off, idx, items, W))
+    back = _through_owners(dev, W, items, eng, users, off, idx, idt, order=list(reversed(range(W))))[0]
+    assert _equal(back, want)
+
+
+def test_an_owner_without_candidates(dev):
+    """W = 8 over ids of three residue classes: five owners hold no candidate and send zeros"""
+    ops = _m("ops")
+    rng = np.random.default_rng(3)
+    ids_all = np.concatenate([8 * np.arange(100), 8 * np.arange(100) + 1, 8 * np.arange(100) + 5])
+    items = rng.permutation(ids_all)[:250]
+    assert sum(len(m) == 0 for m in R.owner_maps(items, 8)[0]) == 5
+    spec, p, eng = _engine(dev, "A", 10, 50, 1000, seed=6)
+    off, idx = R.built_users(rng, items, 8, big=(100,))
+    users = torch.as_tensor(rng.integers(0, 50, len(off) - 1), dtype=torch.int32, device=dev)
+    pu, pit, tower, tail = _operands(eng, users, torch.as_tensor(items, dtype=torch.int32, device=dev))
+    want = ops.neumf_catalog_auc(pu, pit, tower, *tail, *_dev_csr(off, idx, dev))
+    assert _equal(_through_owners(dev, 8, items, eng, users, off, idx, torch.int32, order=[5, 0, 7, 1, 2, 6, 3, 4])[0], want)
+
+
+# --------------------------------------------------------------------------------------------------------------- 9: 2 ranks, gloo staging
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _check_engine(rank, world, ctx, dev):
+    par, neumf = _m("parallel"), _m("neumf")
+    G, S = _load("test_gpu_sharded_recommend"), _load("test_gpu_sharded_auc")
+    U, I, dim = 50, 300, 16
+    for variant, idt, exchange in (("A", torch.int32, "padded"), ("B", torch.int64, "exact")):
+        spec, p, single = _engine(dev, variant, dim, U, I, seed=4, id_dtype=idt)
+        p["item_mlp"][50:200] = p["item_mlp"][np.arange(50, 200) % 4]; p["item_mf"][50:200] = p["item_mf"][np.arange(50, 200) % 4]
+        single.load_numpy_params(p)                                       # ties across the two owners
+        sh = par.make_sharded_engine(neumf.NeuMFEngine)(single.cfg, U, I, dev, 4096, ctx, full_tables={k: torch.from_numpy(p[k]) for k in neumf.TABLES},
+                                                        id_dtype=idt, exchange=exchange)
+        sh.theta.buf.copy_(single.theta.buf)
+        for k in single.moving:
+            sh.moving[k].copy_(single.moving[k])
+        # unequal user counts, one rank without users, a rank that owns no candidate of the list
+        for counts, how in (((13, 5), "perm"), ((7, 0), None), ((0, 9), "perm"), ((6, 4), "even"), ((2, 3), "one")):
+            rng = np.random.default_rng(23 + len(how or ""))
+            users = torch.as_tensor(G._rank_users(rng, rank, U, counts), dtype=idt, device=dev)
+            items, n_it = G._items(rng, how, I, idt, dev)
+            truth = S._rank_truth(np.random.default_rng(200 + rank), counts[rank], n_it, dev)
+            got = sh.full_auc(users, truth, items=items)
+            assert got.shape == (counts[rank],) and got.dtype == torch.float32
+            if counts[rank]:
+                want = single.full_auc(users, truth, items=items)
+                assert _equal(got, want), (variant, counts, how, got, want)
+                assert torch.isnan(got[0])
+        sh.check_ids()
+        bad = torch.arange(40 + rank, dtype=idt, device=dev)
+        with pytest.raises(ValueError, match="same items"):
+            sh.full_auc(users, S._rank_truth(np.random.default_rng(1), users.shape[0], 40, dev), items=bad)
+        with pytest.raises(NotImplementedError, match="dump_probs"):
+            sh.full_auc(users, truth, dump_probs=True)
+        with pytest.raises(NotImplementedError):
+            sh.full_auc(users, truth, method="pairs")
+
+
+def _check_model(rank, world, ctx, dev):
+    import torch.distributed as dist
+    par, neumf, models = _m("parallel"), _m("neumf"), _m("models")
+    U, I, dim = 50, 300, 16
+    m = models.NeuMFModel(device="cuda:0", max_batch=4096)
+    m.compileModel(None, U, I, dim)
+    eng = m.model.engine
+    assert getattr(eng, "sharded", False) and eng.ctx.world == world
+    shards = [None] * world
+    dist.all_gather_object(shards, {k: eng.tables[k].cpu() for k in neumf.TABLES})
+    ref = neumf.NeuMFEngine(eng.cfg, U, I, dev, 4096, id_dtype=torch.int32)
+    for k in neumf.TABLES:
+        rows = U if k.startswith("user") else I
+        for r in range(world):
+            ref.tables[k][r::world] = shards[r][k][:par.shard_rows(rows, r, world)].to(dev)
+    th = eng.theta.buf.cpu()
+    dist.broadcast(th, 0)                 # (an untrained model: make sure both ranks score with one tower)
+    eng.theta.buf.copy_(th)
+    ref.theta.buf.copy_(eng.theta.buf)
+    for k in ref.moving:
+        ref.moving[k].copy_(eng.moving[k])
+    m1 = models.NeuMFModel(device="cuda:0", max_batch=4096)
+    m1.model = models.KerasLikeNeuMF(ref)
+    rng = np.random.default_rng(8)
+    items = rng.permutation(I)[:150].tolist()
+    rng = np.random.default_rng(80 + rank)
+    gt = [(int(u), [items[j] for j in rng.choice(150, int(rng.integers(0, 30)), replace=False)]) for u in rng.integers(0, U, [9, 4][rank])]
+    gt[0] = (gt[0][0], [items[3]])
+    assert m.full_auc(gt, items) == m1.full_auc(gt, items)
+    assert m.mean_average_precision_k(gt, items, k=10) == m1.mean_average_precision_k(gt, items, k=10)
+
+
+def _worker(rank, world, port, kind, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import torch.distributed as dist
+    try:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        dev = torch.device("cuda:0")
+        ctx = _m("parallel").DistCtx()
+        {"engine": _check_engine, "model": _check_model}[kind](rank, world, ctx, dev)
+        torch.cuda.synchronize()
+        ctx.barrier()
+        q.put((rank, "ok"))
+    except Exception:  # noqa: BLE001
+        import traceback
+        q.put((rank, "FAIL: " + traceback.format_exc()[-2500:]))
+    finally:
+        try:
+            dist.destroy_process_group()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+@pytest.mark.parametrize("kind", ["engine", "model"])
+def test_sharded_full_auc_two_ranks_one_gpu(dev, kind):
+    """2 ranks (3 GPU processes with this one); every child has its own time limit and is never run again"""
+    world, port = 2, _free_port()
+    ctxm = mp.get_context("spawn")
+    q = ctxm.Queue()
+    procs = [ctxm.Process(target=_worker, args=(r, world, port, kind, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        res = [q.get(timeout=300) for _ in procs]
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+        for p in procs:      # never leave a child behind: the interpreter would wait for it at exit
+            if p.is_alive():
+                p.kill()
+    for r in res:
+        assert r[1] == "ok", f"rank {r[0]}: {r[1]}"
+
+
+# --------------------------------------------------------------------------------------------------------------- 10: the model surface
+def test_neumf_model_surface(dev):
+    models = _m("models")
+    U, I = 60, 400
+    spec, p, eng = _engine(dev, "B", 16, U, I, seed=14)
+    m = models.NeuMFModel(device="cuda:0", max_batch=4096)
+    m.model = models.KerasLikeNeuMF(eng)
+    rng = np.random.default_rng(14)
+    items = rng.permutation(I)[:250].tolist()
+    # 17 users with 1 to 29 positives each, then one of them without any and one with exactly one: 16 users count
+    gt = [(int(u), [items[j] for j in rng.choice(250, int(rng.integers(1, 30)), replace=False)]) for u in rng.integers(0, U, 17)]
+    gt[0], gt[1] = (gt[0][0], []), (gt[1][0], [items[3]])
+    users = torch.as_tensor([u for u, _ in gt], dtype=eng.id_dtype, device=dev)
+    col = {it: j for j, it in enumerate(items)}
+    off, idx = _m("ops").truth_csr(len(gt), [r for r, (_u, t) in enumerate(gt) for _ in t], [col[q] for _u, t in gt for q in t], dev)
+    _auc, dump = eng.full_auc(users, (off, idx), items=torch.as_tensor(items, dtype=eng.id_dtype, device=dev), dump_probs=True)
+    d = dump.cpu().numpy()
+    want_auc, _vals = O.full_auc([d[u] for u in range(len(gt))], gt, items)
+    got_auc = m.full_auc(gt, items)
+    # per user the device value is O.full_auc's rounded to float32 once; the mean over n users of such values
+    n = sum(1 for _u, t in gt if t)
+    assert abs(got_auc - want_auc) <= F32_EPS, (got_auc, want_auc)
+    assert got_auc == m.full_auc(gt, items, method="fused")
+    # the pair path: within the mean of the per-user bounds of test_engine_fused_against_pairs, derived from its own probabilities
+    _pa, probs = eng.full_auc(users, (off, idx), items=torch.as_tensor(items, dtype=eng.id_dtype, device=dev), method="pairs", dump_probs=True)
+    bound = _flip_bound(probs.double().cpu().numpy(), off.cpu().numpy(), idx.cpu().numpy(), 2e-5) + 2 * F32_EPS
+    has = np.array([len(t) > 0 for _u, t in gt])
+    assert n == 16 and abs(m.full_auc(gt, items, method="pairs") - got_auc) <= bound[has].mean()
+    # MAP@k: users without positives break the reference's division (ZeroDivisionError); the oracle sees the others, the model counts 0
+    some = [g for g in gt if g[1]]
+    rows = [r for r, g in enumerate(gt) if g[1]]
+    for k in (1, 10, 100):
+        want_map, _s = O.mean_average_precision_k([d[r] for r in rows], some, items, k=k)
+        got_map = m.mean_average_precision_k(some, items, k=k)
+        assert abs(got_map - want_map) <= (k + 2) * F32_EPS, (k, got_map, want_map)      # a float32 sum of at most k terms <= 1, one division
+        assert abs(m.mean_average_precision_k(gt, items, k=k) * len(gt) - got_map * len(some)) <= 1e-12 * len(gt)
+    # a true item outside `items` raises as BPRModel.full_auc does (the reference's items.index(p)); MAP@k rescales instead
+    outside = next(i for i in range(I) if i not in col)
+    with pytest.raises(ValueError, match="is not in list"):
+        m.full_auc([(3, [items[0], outside])], items)
+    a = m.mean_average_precision_k([(3, [items[0], outside])], items, k=10)
+    b = m.mean_average_precision_k([(3, [items[0]])], items, k=10)
+    assert abs(a - b / 2) <= 1e-7
+    with pytest.raises(ValueError):
+        m.full_auc(gt, items, method="matrix")
