@@ -226,6 +226,24 @@ class BPREngine(RowAdam):
         q, c = self._catalog_rows(users, items)
         return ops.dot_auc_for(q.shape[1])(q, c, truth[0], truth[1], dump_scores=dump_scores)
 
+    def catalog_ranks(self, users, truth, items=None, exclude=None, dump_scores=False):
+        """Per truth entry, in the order of the CSR, how many candidates score above it and how many tie with it, over the whole
+        catalogue and without the U x I matrix (ops.dot_catalog_ranks, csrc/ranks_dot.hip; rows up to 512 features).  truth / items as
+        in full_auc; exclude: (off, idx) CSR over `users` of candidate POSITIONS never offered (topk_metrics.seen_csr): an excluded
+        truth entry is still ranked, against the others.  -> (above, tied) int32 on the device, (-1, -1) for a positive whose score is
+        NaN.  Ids outside the tables set self.err (check_ids raises).  On the row-sharded engine this is a collective through the
+        gathered rows (every rank calls it and gets the counts of ITS users)."""
+        q, c = self._catalog_rows(users, items)
+        return ops.dot_catalog_ranks(q, c, truth[0], truth[1], exclude=exclude, dump_scores=dump_scores)
+
+    def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
+        """Per-user MRR and, for every cutoff of ks (at most 8), NDCG@k, recall@k and hit rate@k over the whole catalogue, from the exact
+        ranks of catalog_ranks: r = 1 + above + tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that
+        scores everything equal earns nothing.  -> {"mrr", "ndcg@k", "recall@k", "hr@k"} float32 (U,) on the device, NaN for a user
+        without positives (ops.rank_metrics)."""
+        above, tied = self.catalog_ranks(users, truth, items=items, exclude=exclude)
+        return ops.rank_metrics(above, tied, truth[0], ks)
+
     def _catalog_rows(self, users, items):
         """-> (the rows of `users`, the rows of `items` or the item table in place) that recommend / full_auc score (row-sharded
         engines override this: parallel.py)"""

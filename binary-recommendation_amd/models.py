@@ -96,6 +96,16 @@ def _truth_of(ground_truth, items, device_of, strict: bool):
     return gt, col, ops.truth_csr(len(gt), rows, cols, device_of())
 
 
+def _mean_over_users_with_positives(per_user: dict) -> dict:
+    """the per-user device vectors of ops.rank_metrics (NaN = a user without positives) -> their means over the other users, as floats"""
+    out = {}
+    for name, v in per_user.items():
+        a = v.double().cpu().numpy()
+        has = ~np.isnan(a)
+        out[name] = float(a[has].mean()) if has.any() else float("nan")
+    return out
+
+
 def _ap_scale(gt, col, k):
     """brMapAtK divides by min(truth items it was given, k); the reference by min(len(actual), k) with EVERY listed item, also those
     outside `items` (bpr.py:286): the per-user factor between the two (tiny vectors, on the host).  A user without positives: the
@@ -495,6 +505,24 @@ class BPRModel(RModel):
         ap, _ = ops.map_at_k(ti, off, idx, want_hits=False)
         return float((ap.double().cpu().numpy() * _ap_scale(gt, col, k)).mean())
 
+    def rank_metrics(self, ground_truth, items, ks=(10,), excludeSeen=False) -> dict:
+        """MRR and, per cutoff k of ks (at most 8), NDCG@k, recall@k and hit rate@k over all `items`, from the exact rank of every true
+        item among them (BPREngine.rank_metrics: one fused pass, no users x items matrix, no limit on the rank): the means over the
+        users that have positives, as Python floats {"mrr", "ndcg@k", "recall@k", "hr@k"}.  ground_truth: iterable of (user_id, [true
+        item ids]); a true item outside `items` raises, as in full_auc.  excludeSeen: the products a customer has in the training
+        split are no candidates (a true item among them is still ranked, against the others).  The rank is pessimistic: r = 1 + the
+        candidates scoring above + those scoring EQUAL, so a model that scores everything equal earns nothing.  On a row-sharded
+        engine this is a collective through the gathered rows."""
+        from .topk_metrics import seen_csr
+        gt, _col, truth = _truth_of(ground_truth, items, lambda: self.model.device, strict=True)
+        e = self.model
+        users = [u for u, _ in gt]
+        ex = seen_csr(users, list(items), self.trainDf.CUSTOMER_ID.tolist(), self.trainDf.PRODUCT_ID.tolist(), e.device) if excludeSeen else None
+        res = e.rank_metrics(_to_dev(np.asarray(users), e.device, e.id_dtype), truth, ks=ks,
+                             items=_to_dev(np.asarray(items), e.device, e.id_dtype), exclude=ex)
+        e.check_ids()
+        return _mean_over_users_with_positives(res)
+
     # ---- recommendation (the reference's BPRModel has none): the fused dot-product catalogue top-k ----
     def getPredictableUsers(self) -> list:
         """the customers of the training split: the users whose rows the model has learned"""
@@ -651,6 +679,21 @@ class TwoTowerModel:
         return ts.cpu().numpy(), ids
 
     predict = call
+
+    def rank_metrics(self, usersId, itemsId, positives, ks=(10,), exclude=None) -> dict:
+        """MRR and, per cutoff k of ks (at most 8), NDCG@k, recall@k and hit rate@k of the candidates itemsId for the users usersId by
+        the dot of the tower outputs, from the exact rank of every positive (TwoTowerEngine.rank_metrics: one fused pass, no users x
+        items matrix): the means over the users that have positives, as Python floats {"mrr", "ndcg@k", "recall@k", "hr@k"}.
+        positives: iterable of (user, item) pairs as topKMetrics takes them (pairs outside the two lists are ignored); exclude: (off,
+        idx) CSR over usersId of candidate positions never offered (topk_metrics.seen_csr).  The rank is pessimistic: r = 1 + the
+        candidates scoring above + those scoring EQUAL, so a model that scores everything equal earns nothing."""
+        from .topk_metrics import seen_csr
+        pairs = list(positives)
+        truth = seen_csr(list(usersId), list(itemsId), [u for u, _i in pairs], [i for _u, i in pairs], self.device)
+        res = self.engine.rank_metrics(self.userTowerIn(usersId, self.device), truth, ks=ks, items=self.itemTowerIn(list(itemsId), self.device),
+                                       exclude=exclude)
+        self.engine.check_ids()
+        return _mean_over_users_with_positives(res)
 
     def topk(self, usersId, itemsId, k, exclude=None, method="matrix"):
         """exclude: (off, idx) CSR over usersId of candidate positions never returned (topk_metrics.seen_csr); (-inf, -1) pads.

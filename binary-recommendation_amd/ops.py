@@ -852,6 +852,73 @@ def dot_auc_for(dim: int):
     return dot_catalog_auc if dim <= DOT_MAX_DIM else dot_catalog_auc_wide
 
 
+# ------------------------------------------------------------------------------ dot-product catalogue ranks (csrc/ranks_dot.hip)
+RANK_MAX_KS = 8            # cutoffs of one rank_metrics call
+
+
+def dot_catalog_ranks(Q, C, truth_off, truth_idx, exclude=None, dump_scores=False, force_wide=False):
+    """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim, 1 <= dim <= 512), truth (ops.truth_csr over the rows of Q:
+    ascending positions into C), exclude: (off, idx) CSR over the rows of Q of positions never offered as candidates
+    (topk_metrics.seen_csr) -> (above, tied) int32, one entry per truth entry in CSR order [, every pair's score (U, I)]: how many
+    candidates (every non-excluded item but the entry itself, the user's other positives included) score above the positive and how
+    many tie with it, counted exactly on the scores dot_catalog_auc / dot_catalog_topk form (same bits); the U x I matrix is not
+    stored.  An excluded position that is a truth entry is still ranked (against the non-excluded others).  (-1, -1) for a positive
+    whose score is NaN; a NaN candidate is never above and never tied.  force_wide as in dot_catalog_auc_wide (brDotCatalogRanks)."""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_ranks", Q, C, None, DOT_WIDE_MAX_DIM)
+    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
+    off, idx = _csr((truth_off, truth_idx), U, "truth")
+    xoff, xidx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotCatalogRanksWorkspaceBytes(U, I, dim, n_truth))
+    if ws_bytes < 0:
+        raise ValueError(f"dot_catalog_ranks: bad sizes U={U} I={I} truth entries={n_truth}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    above = torch.empty(n_truth, dtype=torch.int32, device=dev)
+    tied = torch.empty(n_truth, dtype=torch.int32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    check(lib.brDotCatalogRanks(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), n_truth, _p(xoff), _p(xidx),
+                                above.data_ptr() if n_truth else ws.data_ptr(), tied.data_ptr() if n_truth else ws.data_ptr(), _p(dump),
+                                _wide_flags(force_wide), ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogRanks")
+    return (above, tied, dump) if dump_scores else (above, tied)
+
+
+def rank_metrics(above, tied, truth_off, ks):
+    """above / tied int32 (one per truth entry) and truth_off int64 (U + 1) of dot_catalog_ranks, ks: 1 to 8 cutoffs k >= 1 -> dict of
+    float32 device tensors (U,): "mrr" and per k "ndcg@k", "recall@k", "hr@k"; NaN for a user without positives.  The rank of a positive
+    is r = 1 + above + tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that scores everything equal
+    earns nothing.  An entry with above = -1 has no rank: a miss that still counts in P.  NDCG@k = sum over r <= k of 1 / log2(1 + r)
+    over the same sum for the ranks 1 .. min(P, k); recall@k = #{r <= k} / P; hr@k = [min r <= k]; mrr = 1 / min r, 0 without a ranked
+    positive.  Summed in double on the device (brRankMetrics)."""
+    import ctypes
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= RANK_MAX_KS:
+        raise ValueError(f"rank_metrics: {len(ks)} cutoffs: 1 <= len(ks) <= {RANK_MAX_KS}")
+    if min(ks) < 1 or max(ks) >= 1 << 31:
+        raise ValueError(f"rank_metrics: ks = {ks}: every cutoff 1 <= k < 2^31")
+    for t, name in ((above, "above"), (tied, "tied")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"rank_metrics: {name} must be a 1-D tensor")
+    if above.shape != tied.shape:
+        raise ValueError(f"rank_metrics: above has {above.numel()} entries, tied {tied.numel()}")
+    if not isinstance(truth_off, torch.Tensor) or truth_off.dtype != torch.int64 or not truth_off.is_cuda or not truth_off.is_contiguous() \
+            or truth_off.dim() != 1 or truth_off.numel() < 1:
+        raise TypeError("rank_metrics: truth_off must be a contiguous int64 device tensor (U + 1)")
+    _i32_dev(above, "above"); _i32_dev(tied, "tied")
+    U, dev = truth_off.numel() - 1, truth_off.device
+    mrr = torch.empty(U, dtype=torch.float32, device=dev)
+    out = torch.empty(3, len(ks), U, dtype=torch.float32, device=dev)
+    if above.numel() == 0:         # a valid pointer for an empty list
+        above = tied = torch.zeros(1, dtype=torch.int32, device=dev)
+    kk = (ctypes.c_int32 * len(ks))(*ks)
+    if U:
+        check(_lib.load().brRankMetrics(above.data_ptr(), tied.data_ptr(), truth_off.data_ptr(), U, ctypes.addressof(kk), len(ks), mrr.data_ptr(),
+                                        out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream()), "brRankMetrics")
+    res = {"mrr": mrr}
+    for j, k in enumerate(ks):
+        res[f"ndcg@{k}"], res[f"recall@{k}"], res[f"hr@{k}"] = out[0, j], out[1, j], out[2, j]
+    return res
+
+
 # ------------------------------------------------------------------------------ catalogue AUC counted at the item owners (csrc/auc_owner.hip)
 # dot_catalog_auc[_wide] in four phases, for W owners that each hold a share of the candidates (parallel.auc_at_owners, DESIGN.md 4i).
 # force_wide as in dot_catalog_auc_wide; the positives and the count of one evaluation take the same value.

@@ -905,6 +905,10 @@ def make_sharded_two_tower(base_cls):
                 lambda loc: self._tower(ops.gather_rows([self.item_emb], [loc], err_flag=self.err)[0], "item"),
                 lambda q, c, kk, ex: ops.dot_catalog_topk(q, c, kk, exclude=ex))
 
+        def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
+            raise NotImplementedError("rank_metrics on the row-sharded TwoTower engine: the exact ranks are counted on one device "
+                                      "(ops.dot_catalog_ranks); counting at the item owners is not built (DESIGN.md 7)")
+
         def _softmax(self, q, c, items, B, dq, dc):
             ctx = self.ctx
             off = ctx.rank * B

@@ -148,6 +148,18 @@ class TwoTowerEngine:
             items = torch.arange(self.item_emb.shape[0], dtype=users.dtype, device=self.device)
         return ops.dot_catalog_topk(self.user_tower(users), self.item_tower(items), k, exclude=exclude)
 
+    def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
+        """Per-user MRR and, for every cutoff of ks (at most 8), NDCG@k, recall@k and hit rate@k of the candidates `items` (None: every row
+        of the item table) by the dot of the tower outputs, as recommend forms them, from the exact ranks of ops.dot_catalog_ranks
+        (csrc/ranks_dot.hip) without the U x I matrix.  truth: (off, idx) CSR over `users` of candidate POSITIONS, ascending
+        (ops.truth_csr); exclude: CSR of positions never offered (topk_metrics.seen_csr).  The rank of a positive is r = 1 + above +
+        tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that scores everything equal earns nothing.
+        -> {"mrr", "ndcg@k", "recall@k", "hr@k"} float32 (U,) on the device, NaN for a user without positives."""
+        if items is None:
+            items = torch.arange(self.item_emb.shape[0], dtype=users.dtype, device=self.device)
+        above, tied = ops.dot_catalog_ranks(self.user_tower(users), self.item_tower(items), truth[0], truth[1], exclude=exclude)
+        return ops.rank_metrics(above, tied, truth[0], ks)
+
     def enable_graph(self, batch: int | None = None):
         """Replay the step for batches of exactly `batch` pairs as ONE hipGraph (the eager step is ~20 launches from the Python host with
         gaps between them: 0.48 ms at batch 8 192, of which the kernels take 0.40).  Adagrad, single GPU: then no per-step scalar is baked

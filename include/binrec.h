@@ -512,6 +512,38 @@ int brDotCatalogAucWide(const float* Q, int64_t ld_q, int64_t n_users, const flo
                         const int64_t* truth_off, const int32_t* truth_idx, float* out_auc, float* dump_scores, int flags, void* ws,
                         int64_t ws_bytes, brStream stream);
 
+/* ---- Catalogue ranks for dot-product models (BPR, TwoTower): NDCG@k, MRR, recall@k, hit@k over the whole catalogue: csrc/ranks_dot.hip ----
+ * The reference evaluates with full_auc and mean_average_precision_k (src/models/bpr.py:230-289) and HR@k (trainers/topKmetrics.py:74-99);
+ * these two entries add the ranking measures it lacks over the same scores (bpr_predict, bpr.py:122-133), without the U x I matrix.
+ * brDotCatalogRanks: Q, C, dim, the score contract and BR_DOT_FORCE_WIDE of brDotCatalogAucWide (1 <= dim <= 512; whole-row kernel up to
+ *   128 features unless forced, block kernel above): a pair's score is bit for bit the one brDotCatalogAuc[Wide] / brDotCatalogTopK[Wide]
+ *   form and dump.  truth_off (n_users + 1) / truth_idx: the CSR of brDotCatalogAuc, n_truth = truth_off[n_users] entries; excl_off /
+ *   excl_idx (optional, both or neither): per user the ascending, unique positions into C never offered as candidates (the exclusion CSR
+ *   of brDotCatalogTopK).  Per truth entry e = (u, p), in truth-CSR order, over the candidates i != p that are not excluded for u:
+ *     out_above[e] = #{i: score(u, i) > score(u, p)},  out_tied[e] = #{i: score(u, i) == score(u, p)}.
+ *   The user's other positives are candidates like any other item.  Exclusion never removes a truth entry: a position in both CSRs is
+ *   ranked against the non-excluded others (and is no candidate for them).  A positive whose score is NaN (or whose position lies
+ *   outside [0, n_items)) gets (-1, -1); a candidate whose score is NaN is never above and never tied; +-inf compare as floats do.  All
+ *   counting is in integers (integer atomics only): the result does not depend on the plan, the user order or the order of arrival.
+ *   dump_scores (optional, n_users x n_items): every pair's score (tests).  Limits: those of brDotCatalogAucWide and
+ *   n_truth + n_users < 2^31; BR_ERR_ARG / BR_ERR_WORKSPACE before any launch; n_users == 0 is BR_OK.
+ *   ws: brDotCatalogRanksWorkspaceBytes(n_users, n_items, dim, n_truth) bytes (the positives' raw and sorted scores and two int32 bins per
+ *   truth entry and user); -1 for sizes outside the limits.  The user's positives are sorted by counting rank, O(P^2) compares per user.
+ * brRankMetrics: above / tied / truth_off of brDotCatalogRanks, ks: n_ks cutoffs on the HOST (1 <= n_ks <= 8, every k >= 1).  The rank of
+ *   a positive is r = 1 + above + tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that scores everything
+ *   equal earns nothing.  A positive with above < 0 has no rank: a miss that still counts in P = the user's truth entries.  Per user, in
+ *   double, stored float32, NaN for P == 0:
+ *     out_mrr[u] = 1 / min r (0 if no positive has a rank);  for cutoff j, at [j * n_users + u]:
+ *     out_ndcg = sum over r <= k of 1 / log2(1 + r)  /  sum over i = 1 .. min(P, k) of 1 / log2(1 + i);
+ *     out_recall = #{r <= k} / P;  out_hit = [min r <= k]. */
+int64_t brDotCatalogRanksWorkspaceBytes(int64_t n_users, int64_t n_items, int dim, int64_t n_truth);
+int brDotCatalogRanks(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                      const int64_t* truth_off, const int32_t* truth_idx, int64_t n_truth, const int64_t* excl_off,
+                      const int32_t* excl_idx, int32_t* out_above, int32_t* out_tied, float* dump_scores, int flags, void* ws,
+                      int64_t ws_bytes, brStream stream);
+int brRankMetrics(const int32_t* above, const int32_t* tied, const int64_t* truth_off, int64_t n_users, const int32_t* ks, int n_ks,
+                  float* out_mrr, float* out_ndcg, float* out_recall, float* out_hit, brStream stream);
+
 /* ---- Catalogue top-k on row-sharded engines, scored where the item rows live: csrc/recommend_merge.hip ----------------------------
  * W owners each run brNeumfCatalogTopK / brDotCatalogTopK over the candidates whose rows they hold (parallel.py recommend_at_owners);
  * these two turn the W shard-local answers into the answer of ONE launch over the whole candidate list, entry for entry.  The reference
