@@ -1,11 +1,12 @@
 // The catalogue pass of the dot-product AUC with its two CSRs in two separate roles, for the owner-side count of a row-sharded engine
-// (auc_owner.hip).  The two passes are dot_auc_kernel's (auc_dot.hip) and dot_auc_wide_kernel's (auc_dot_wide.hip) bodies, statement for
-// statement, kept the same by hand as those two are among themselves (DESIGN.md 4e "One copy of the tile loop", 4i), except that
+// (auc_owner.hip).  The two passes are dot_auc_kernel's and dot_auc_wide_kernel's bodies (auc_dot.hip), statement for statement, kept the
+// same by hand as those two are among themselves (DESIGN.md 4e "One copy of the tile loop", 4i), except that
 //   - (off, idx) is only what the cursor and the window mask skip: this owner's positives, ascending LOCAL positions into C;
 //   - loff says where a user's sorted list lies in `sorted` (loff[u], pcnt[u] entries): ALL the user's positives, of every owner.
-// With loff == off they are the single-device kernels.  Those keep their own text: routing them through these bodies changed their
-// gfx950 register allocation and instruction order, and they are the measured ones.  The kernels own the LDS arrays
-// (tile, pos_s, xm_s) and hand them in.
+// With loff == off they are the single-device kernels.  Those keep their own text: as wrappers of these bodies they compile to the same
+// register, LDS and occupancy budgets (profiles/recommend/auc_one_body_resources.json) but not to the same instructions, and the
+// alternating measurement that has to decide it has not been taken yet.  The kernels own the LDS arrays (tile, pos_s,
+// xm_s) and hand them in.  Here too, once for every kernel that runs a pass: the tile shape, the LDS cap and the split plan.
 #pragma once
 #include <math.h>
 
@@ -19,6 +20,11 @@ namespace {
 constexpr int kAucRT = 2, kAucCT = 4;     // 32 users per wave (whole-row kernel; the block kernel: kWideUW), 64 items per step
 constexpr int kAucUW = 16 * kAucRT, kAucNT = 16 * kAucCT;
 constexpr int kAucLdsCap = 2048;          // sorted positives of a wave's users kept in LDS up to this many (8 KB per wave)
+
+// the split plan of a pass: 4 waves of kAucUW (wide: kWideUW) users per workgroup, kAucNT items per step
+void auc_plan(bool wide, int64_t n_users, int64_t n_items, int64_t* splits, int64_t* steps_per_split) {
+  split_plan(ceil_div(n_items, kAucNT), n_users, 4 * (wide ? kWideUW : kAucUW), splits, steps_per_split);
+}
 
 // the whole-row pass (dim <= 128, 4 KB >= dim): tile float [kAucNT * (4 KB + 4)] 16-B aligned, pos_s float [4 * kAucLdsCap], xm_s uint64 [4 * kAucUW]
 template <int KB>

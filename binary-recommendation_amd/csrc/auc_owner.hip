@@ -1,5 +1,5 @@
 // Full-catalogue AUC of dot-product models on row-sharded engines, counted where the item rows live (include/binrec.h "Catalogue AUC on
-// row-sharded engines"; parallel.py auc_at_owners).  brDotCatalogAuc[Wide]'s three launches cut into four phases, so that
+// row-sharded engines"; parallel.py auc_at_owners).  brDotCatalogAuc[Wide]'s three launches (auc_dot.hip) cut into four phases, so that
 // W owners, each holding a share of the candidates, together compute what one launch over all candidates computes, bit for bit:
 //
 //   - brDotAucOwnerPositives: auc_pos_kernel's scoring half (auc_pos.h) over the owner's candidates: the same v_mfma_f32_16x16x4_f32,
@@ -164,19 +164,11 @@ __global__ __launch_bounds__(256) void auc_finalize_lists_kernel(const uint64_t*
   auc[u] = (float)((double)w2 * 0.5 / ((double)P * (double)N));
 }
 
-// the count pass's split plans: those of brDotCatalogAuc (auc_dot.hip) and brDotCatalogAucWide (auc_dot_wide.hip)
-void owner_plan(bool wide, int64_t n_users, int64_t n_items, int64_t* splits, int64_t* steps_per_split) {
-  split_plan(ceil_div(n_items, kAucNT), n_users, 4 * (wide ? kWideUW : kAucUW), splits, steps_per_split);
-}
-
 int64_t owner_part_bytes(bool wide, int64_t n_users, int64_t n_items) {
   int64_t S, sps;
-  owner_plan(wide, n_users, n_items, &S, &sps);
+  auc_plan(wide, n_users, n_items, &S, &sps);
   return align256(n_users * S * 8);
 }
-
-// the block kernels for these rows?  (brDotCatalogAucWide's switch: the positives and the count must take the same one)
-bool use_wide(int dim, int flags) { return dim > kDotMaxDim || (flags & BR_DOT_FORCE_WIDE); }
 
 }  // namespace
 }  // namespace br
@@ -191,7 +183,7 @@ extern "C" int brDotAucOwnerPositives(const float* Q, int64_t ld_q, int64_t n_us
   if (n_users == 0) return BR_OK;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)ceil_div(n_users, 4);
-  if (use_wide(dim, flags))
+  if (dot_use_wide(dim, flags))
     dispatch_nb(dim, [&](auto nb) {
       auc_pos_scores_kernel<decltype(nb)::value * kWideKB><<<grid, 256, 0, st>>>(Q, ld_q, n_users, C, ld_c, n_items, dim, pos_off, pos_idx, raw);
     });
@@ -250,9 +242,9 @@ extern "C" int brDotAucOwnerCount(const float* Q, int64_t ld_q, int64_t n_users,
     return BR_ERR_WORKSPACE;
   }
   if (n_users == 0) return BR_OK;
-  const bool wide = use_wide(dim, flags);
+  const bool wide = dot_use_wide(dim, flags);
   int64_t S, sps;
-  owner_plan(wide, n_users, n_items, &S, &sps);
+  auc_plan(wide, n_users, n_items, &S, &sps);
   if (cap > INT32_MAX) cap = INT32_MAX;
   uint64_t* part = (uint64_t*)ws;
   const int vec = rows_vec4(C, ld_c, dim);

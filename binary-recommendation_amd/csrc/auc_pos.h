@@ -1,4 +1,4 @@
-// What the dot-product catalogue AUC entry points (auc_dot.hip, auc_dot_wide.hip) launch around their catalogue pass: the positives'
+// What the dot-product catalogue AUC entry points (auc_dot.hip, either width) and the ranks (ranks_dot.hip) launch around their catalogue pass: the positives'
 // kernel (templated on the instantiated width 4 KB; one accumulator chain over all of it, so a positive's score is the catalogue
 // pass's whatever way that pass streams the features) and the finalize.
 #pragma once

@@ -1,6 +1,7 @@
-// What the dot-product catalogue kernels (recommend_dot.hip: top-k, auc_dot.hip: AUC, and their _wide forms) share outside their tile loops: the split
-// plan (recommend.hip's too), wave_lds_order and what the two entry points check and choose alike.  The tile loop itself is still
-// written out in both kernels and kept the same by hand: see DESIGN.md 4e "One copy of the tile loop".
+// What the dot-product catalogue kernels (recommend_dot.hip / recommend_dot_wide.hip: top-k, auc_count.h: AUC, ranks_dot.hip: ranks)
+// share outside their tile loops: the split plan (recommend.hip's too), wave_lds_order, the CSR row cursor (RowCursor: the rank kernels use
+// it, the AUC bodies still spell it inline) and what the entry points check and choose alike.  The tile loop itself is still written out
+// in every kernel and kept the same by hand: see DESIGN.md 4e "One copy of the tile loop".
 #pragma once
 #include <type_traits>
 
@@ -32,6 +33,33 @@ __device__ __forceinline__ void wave_lds_order() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// the cursor of one CSR row over the item axis: the first entry at or after p0 (cur), the row's end and that entry's position
+struct RowCursor {
+  int64_t cur = 0, end = 0, nxt = INT64_MAX;
+};
+__device__ __forceinline__ RowCursor cursor_at(const int64_t* off, const int32_t* __restrict__ idx, int64_t u, int64_t p0) {
+  RowCursor c;
+  int64_t lo = off[u], hi = off[u + 1];
+  c.end = hi;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)idx[mid] < p0) lo = mid + 1; else hi = mid;
+  }
+  c.cur = lo;
+  if (c.cur < c.end) c.nxt = idx[c.cur];
+  return c;
+}
+// the row's entries inside the window [base, base + NT) as a mask; the cursor moves past them
+__device__ __forceinline__ uint64_t cursor_window(RowCursor& c, const int32_t* __restrict__ idx, int64_t base, int NT) {
+  uint64_t m = 0;
+  while (c.nxt < base + NT) {
+    if (c.nxt >= base) m |= 1ull << (c.nxt - base);
+    ++c.cur;
+    c.nxt = c.cur < c.end ? (int64_t)idx[c.cur] : INT64_MAX;
+  }
+  return m;
+}
+
 // float4 item loads: every row of C 16-B aligned and whole chunks only
 int rows_vec4(const float* C, int64_t ld_c, int dim) { return dim % 4 == 0 && ld_c % 4 == 0 && ((uintptr_t)C & 15) == 0; }
 
@@ -44,8 +72,8 @@ void dispatch_kb(int dim, F&& f) {
   else f(std::integral_constant<int, 32>{});
 }
 
-constexpr int kDotMaxDim = 128;            // widest rows of the whole-row kernels (recommend_dot.hip, auc_dot.hip)
-constexpr int kDotWideMaxDim = 512;        // ... of the block kernels (recommend_dot_wide.hip, auc_dot_wide.hip)
+constexpr int kDotMaxDim = 128;            // widest rows of the whole-row kernels (recommend_dot.hip, auc_count.h dot_auc_pass)
+constexpr int kDotWideMaxDim = 512;        // ... of the block kernels (recommend_dot_wide.hip, auc_count.h dot_auc_wide_pass)
 
 // the checks the entry points make on (Q, C); `name`: the entry point, for the message
 int dot_check_args(const char* name, int64_t ld_q, int64_t n_users, int64_t ld_c, int64_t n_items, int dim, int max_dim = kDotMaxDim) {

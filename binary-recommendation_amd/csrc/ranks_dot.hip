@@ -9,9 +9,9 @@
 //   - rank_init_kernel: the bins zeroed, the outputs -1;
 //   - auc_pos_kernel (auc_pos.h), as the AUC entries launch it: a positive's score bit for bit the catalogue pass's, the user's
 //     non-NaN positives sorted ascending v_0 <= ... <= v_{n-1};
-//   - dot_ranks_kernel / dot_ranks_wide_kernel: the tile streams of dot_auc_kernel (auc_dot.hip) and dot_auc_wide_kernel
-//     (auc_dot_wide.hip), copies kept the same by hand (DESIGN.md 4e "One copy of the tile loop"), with two cursors behind the window
-//     mask (truth and exclusion).  Behind the scores, per candidate score s of a user with n sorted positives (rank_count): s below
+//   - dot_ranks_kernel / dot_ranks_wide_kernel: the tile streams of dot_auc_pass and dot_auc_wide_pass (auc_count.h), copies kept the
+//     same by hand (DESIGN.md 4e "One copy of the tile loop"), with two cursors (dot_tile.h RowCursor) behind the
+//     window mask (truth and exclusion).  Behind the scores, per candidate score s of a user with n sorted positives (rank_count): s below
 //     v_0 or NaN touches nothing; s above v_{n-1} bumps a register counter; s inside searches lo = #{v < s} as the AUC does and adds
 //     1 to the user's bin lo (n + 1 bins per user: the candidate outranks the positives 0 .. lo - 1), and on the rare tie path
 //     (hi = #{v <= s} > lo) 1 to the tie bin lo.  The bins of a wave's users sit in LDS beside their sorted lists while those fit
@@ -128,33 +128,6 @@ __device__ __forceinline__ void rank_count(const f32x4 (&acc)[CT], uint32_t ok, 
         atomicAdd(&H[hb[r] + lo[ct][r]], 1);
         if (hi[ct][r] > lo[ct][r]) atomicAdd(&T[hb[r] + lo[ct][r]], 1);
       }
-}
-
-// the cursor of one CSR row over the item axis: the first entry at or after p0 (cur), the row's end and that entry's position
-struct RowCursor {
-  int64_t cur = 0, end = 0, nxt = INT64_MAX;
-};
-__device__ __forceinline__ RowCursor cursor_at(const int64_t* off, const int32_t* __restrict__ idx, int64_t u, int64_t p0) {
-  RowCursor c;
-  int64_t lo = off[u], hi = off[u + 1];
-  c.end = hi;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)idx[mid] < p0) lo = mid + 1; else hi = mid;
-  }
-  c.cur = lo;
-  if (c.cur < c.end) c.nxt = idx[c.cur];
-  return c;
-}
-// the row's entries inside the window [base, base + NT) as a mask; the cursor moves past them
-__device__ __forceinline__ uint64_t cursor_window(RowCursor& c, const int32_t* __restrict__ idx, int64_t base, int NT) {
-  uint64_t m = 0;
-  while (c.nxt < base + NT) {
-    if (c.nxt >= base) m |= 1ull << (c.nxt - base);
-    ++c.cur;
-    c.nxt = c.cur < c.end ? (int64_t)idx[c.cur] : INT64_MAX;
-  }
-  return m;
 }
 
 // the whole-row pass (dim <= 128, 4 KB >= dim)
@@ -714,7 +687,7 @@ extern "C" int brDotCatalogRanks(const float* Q, int64_t ld_q, int64_t n_users, 
   BR_CHECK_LAUNCH("brDotCatalogRanks init");
   const unsigned per_user = (unsigned)ceil_div(n_users, 4);
   int64_t S, sps;
-  if (dim <= kDotMaxDim && !(flags & BR_DOT_FORCE_WIDE)) {
+  if (!dot_use_wide(dim, flags)) {
     ranks_plan(n_users, n_items, kRankUW, &S, &sps);
     const dim3 grid((unsigned)ceil_div(n_users, 4 * kRankUW), (unsigned)S);
     dispatch_kb(dim, [&](auto kb) {

@@ -703,23 +703,33 @@ def _dot_catalog_args(who: str, Q, C, k=None, max_dim=DOT_MAX_DIM):
     return U, I, dim, (Q.stride(0) if U > 1 else dim), (C.stride(0) if I > 1 else dim), Q.device
 
 
-def dot_catalog_topk(Q, C, k, exclude=None, dump_scores=False):
-    """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim) -> (scores (U, k) float32, index (U, k) int32 positions
-    into C) [, every pair's score (U, I)]: per user the k best Q[u] . C[i], best first, ties to the lower position, exclude positions
-    (ops.truth_csr over the rows of Q) never returned, (-inf, -1) past the remaining candidates; the U x I matrix is not stored."""
-    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_topk", Q, C, k)
+def _wide_flags(force_wide) -> int:
+    return _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
+
+
+def _dot_topk(who: str, wide: bool, Q, C, k, exclude, dump_scores, force_wide=False):
+    """dot_catalog_topk (brDotCatalogTopK) and dot_catalog_topk_wide (wide: brDotCatalogTopKWide, with dim and the flags)"""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args(who, Q, C, k, DOT_WIDE_MAX_DIM if wide else DOT_MAX_DIM)
     lib = _lib.load()
-    ws_bytes = int(lib.brDotCatalogTopKWorkspaceBytes(U, I, int(k)))
+    ws_bytes = int(lib.brDotCatalogTopKWideWorkspaceBytes(U, I, dim, int(k)) if wide else lib.brDotCatalogTopKWorkspaceBytes(U, I, int(k)))
     if ws_bytes < 0:
-        raise ValueError(f"dot_catalog_topk: bad sizes U={U} I={I} k={k}")
+        raise ValueError(f"{who}: bad sizes U={U} I={I} k={k}")
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
     os_ = torch.empty(U, k, dtype=torch.float32, device=dev)
     oi = torch.empty(U, k, dtype=torch.int32, device=dev)
     dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
     off, idx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
-    check(lib.brDotCatalogTopK(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(),
-                               _p(dump), ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogTopK")
+    fn, name = (lib.brDotCatalogTopKWide, "brDotCatalogTopKWide") if wide else (lib.brDotCatalogTopK, "brDotCatalogTopK")
+    check(fn(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(), _p(dump),
+             *((_wide_flags(force_wide),) if wide else ()), ws.data_ptr(), ws_bytes, _stream()), name)
     return (os_, oi, dump) if dump_scores else (os_, oi)
+
+
+def dot_catalog_topk(Q, C, k, exclude=None, dump_scores=False):
+    """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim) -> (scores (U, k) float32, index (U, k) int32 positions
+    into C) [, every pair's score (U, I)]: per user the k best Q[u] . C[i], best first, ties to the lower position, exclude positions
+    (ops.truth_csr over the rows of Q) never returned, (-inf, -1) past the remaining candidates; the U x I matrix is not stored."""
+    return _dot_topk("dot_catalog_topk", False, Q, C, k, exclude, dump_scores)
 
 
 # ------------------------------------------------------------------------------ shard-local lists -> one list (csrc/recommend_merge.hip)
@@ -784,62 +794,42 @@ def topk_lists_merge(scores, index, n_lists: int, n_users: int, k: int, l2g, l2g
 
 
 # ------------------------------------------------------------------------------ dot-product catalogue AUC (csrc/auc_dot.hip)
+def _dot_auc(who: str, wide: bool, Q, C, truth_off, truth_idx, dump_scores, force_wide=False):
+    """dot_catalog_auc (brDotCatalogAuc) and dot_catalog_auc_wide (wide: brDotCatalogAucWide, with dim and the flags)"""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args(who, Q, C, None, DOT_WIDE_MAX_DIM if wide else DOT_MAX_DIM)
+    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
+    off, idx = _csr((truth_off, truth_idx), U, "truth")
+    lib = _lib.load()
+    ws_bytes = int(lib.brDotCatalogAucWideWorkspaceBytes(U, I, dim, n_truth) if wide else lib.brDotCatalogAucWorkspaceBytes(U, I, n_truth))
+    if ws_bytes < 0:
+        raise ValueError(f"{who}: bad sizes U={U} I={I}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.float32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    fn, name = (lib.brDotCatalogAucWide, "brDotCatalogAucWide") if wide else (lib.brDotCatalogAuc, "brDotCatalogAuc")
+    check(fn(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
+             *((_wide_flags(force_wide),) if wide else ()), ws.data_ptr(), ws_bytes, _stream()), name)
+    return (out, dump) if dump_scores else out
+
+
 def dot_catalog_auc(Q, C, truth_off, truth_idx, dump_scores=False):
     """Q (U x dim) user rows, C (I x dim) item rows (any row stride >= dim), truth (ops.truth_csr over the rows of Q: ascending
     positions into C) -> per-user AUC float32 (U,) [, every pair's score (U, I)]: full_auc of the scores Q[u] . C[i], equal bit for
     bit to full_auc(score_matrix(Q, C), truth_off, truth_idx) on the same scores, NaN where undefined; the U x I matrix is not stored."""
-    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_auc", Q, C)
-    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
-    off, idx = _csr((truth_off, truth_idx), U, "truth")
-    lib = _lib.load()
-    ws_bytes = int(lib.brDotCatalogAucWorkspaceBytes(U, I, n_truth))
-    if ws_bytes < 0:
-        raise ValueError(f"dot_catalog_auc: bad sizes U={U} I={I}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(U, dtype=torch.float32, device=dev)
-    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
-    check(lib.brDotCatalogAuc(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
-                              ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogAuc")
-    return (out, dump) if dump_scores else out
+    return _dot_auc("dot_catalog_auc", False, Q, C, truth_off, truth_idx, dump_scores)
 
 
-# ------------------------------------------------------------------------------ wide rows (csrc/recommend_dot_wide.hip, auc_dot_wide.hip)
+# ------------------------------------------------------------------------------ wide rows (csrc/recommend_dot_wide.hip, auc_dot.hip)
 def dot_catalog_topk_wide(Q, C, k, exclude=None, dump_scores=False, force_wide=False):
     """dot_catalog_topk for 1 <= dim <= 512 (brDotCatalogTopKWide): the same arguments, results and score contract.  dim <= 128 runs
     dot_catalog_topk's launches unless force_wide, which sends those rows through the block kernels too (same bits: tests)."""
-    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_topk_wide", Q, C, k, DOT_WIDE_MAX_DIM)
-    lib = _lib.load()
-    ws_bytes = int(lib.brDotCatalogTopKWideWorkspaceBytes(U, I, dim, int(k)))
-    if ws_bytes < 0:
-        raise ValueError(f"dot_catalog_topk_wide: bad sizes U={U} I={I} k={k}")
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    os_ = torch.empty(U, k, dtype=torch.float32, device=dev)
-    oi = torch.empty(U, k, dtype=torch.int32, device=dev)
-    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
-    off, idx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
-    flags = _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
-    check(lib.brDotCatalogTopKWide(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, _p(off), _p(idx), int(k), os_.data_ptr(), oi.data_ptr(),
-                                   _p(dump), flags, ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogTopKWide")
-    return (os_, oi, dump) if dump_scores else (os_, oi)
+    return _dot_topk("dot_catalog_topk_wide", True, Q, C, k, exclude, dump_scores, force_wide)
 
 
 def dot_catalog_auc_wide(Q, C, truth_off, truth_idx, dump_scores=False, force_wide=False):
     """dot_catalog_auc for 1 <= dim <= 512 (brDotCatalogAucWide): the same arguments, results and score contract.  dim <= 128 runs
     dot_catalog_auc's launches unless force_wide, which sends those rows through the block kernels too (same bits: tests)."""
-    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_catalog_auc_wide", Q, C, None, DOT_WIDE_MAX_DIM)
-    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
-    off, idx = _csr((truth_off, truth_idx), U, "truth")
-    lib = _lib.load()
-    ws_bytes = int(lib.brDotCatalogAucWideWorkspaceBytes(U, I, dim, n_truth))
-    if ws_bytes < 0:
-        raise ValueError(f"dot_catalog_auc_wide: bad sizes U={U} I={I}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(U, dtype=torch.float32, device=dev)
-    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
-    flags = _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
-    check(lib.brDotCatalogAucWide(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), out.data_ptr(), _p(dump),
-                                  flags, ws.data_ptr(), ws_bytes, _stream()), "brDotCatalogAucWide")
-    return (out, dump) if dump_scores else out
+    return _dot_auc("dot_catalog_auc_wide", True, Q, C, truth_off, truth_idx, dump_scores, force_wide)
 
 
 def dot_topk_for(dim: int):
@@ -922,8 +912,15 @@ def rank_metrics(above, tied, truth_off, ks):
 # ------------------------------------------------------------------------------ catalogue AUC counted at the item owners (csrc/auc_owner.hip)
 # dot_catalog_auc[_wide] in four phases, for W owners that each hold a share of the candidates (parallel.auc_at_owners).
 # force_wide as in dot_catalog_auc_wide; the positives and the count of one evaluation take the same value.
-def _wide_flags(force_wide) -> int:
-    return _lib.parse_enums()["BR_DOT_FORCE_WIDE"] if force_wide else 0
+def _auc_list_args(who: str, U: int, list_off, sorted_, pcnt):
+    """the checks the owner-side counts (`who`) make on the users' full lists (list_off / sorted_ / pcnt of auc_sort_pieces)"""
+    if list_off.dtype != torch.int64 or not list_off.is_cuda or not list_off.is_contiguous() or list_off.numel() != U + 1:
+        raise TypeError(f"{who}: list_off must be a contiguous int64 device tensor of {U + 1} entries")
+    if sorted_.dtype != torch.float32 or not sorted_.is_cuda or not sorted_.is_contiguous() or sorted_.numel() < 1:
+        raise TypeError(f"{who}: sorted_ must be a non-empty contiguous float32 device tensor")
+    _i32_dev(pcnt, "pcnt")
+    if pcnt.numel() != U:
+        raise ValueError(f"{who}: pcnt has {pcnt.numel()} entries for {U} users")
 
 
 def dot_auc_owner_positives(Q, C, pos_off, pos_idx, out=None, force_wide=False):
@@ -974,13 +971,7 @@ def dot_auc_owner_count(Q, C, skip_off, skip_idx, list_off, sorted_, pcnt, dump_
     (the library's uint64: below 2^63 while P N < 2^62) [, every pair's score (U, I_loc)] (brDotAucOwnerCount)."""
     U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_auc_owner_count", Q, C, None, DOT_WIDE_MAX_DIM)
     off, idx = _csr((skip_off, skip_idx), U, "skip")
-    if list_off.dtype != torch.int64 or not list_off.is_cuda or not list_off.is_contiguous() or list_off.numel() != U + 1:
-        raise TypeError(f"dot_auc_owner_count: list_off must be a contiguous int64 device tensor of {U + 1} entries")
-    if sorted_.dtype != torch.float32 or not sorted_.is_cuda or not sorted_.is_contiguous() or sorted_.numel() < 1:
-        raise TypeError("dot_auc_owner_count: sorted_ must be a non-empty contiguous float32 device tensor")
-    _i32_dev(pcnt, "pcnt")
-    if pcnt.numel() != U:
-        raise ValueError(f"dot_auc_owner_count: pcnt has {pcnt.numel()} entries for {U} users")
+    _auc_list_args("dot_auc_owner_count", U, list_off, sorted_, pcnt)
     lib = _lib.load()
     ws_bytes = int(lib.brDotAucOwnerCountWorkspaceBytes(U, I, dim))
     if ws_bytes < 0:
@@ -1076,13 +1067,7 @@ def neumf_auc_count(pu, pit, tower, dim: int, hidden, act: str, skip_off, skip_i
     (the library's uint64: below 2^63 while P N < 2^62) [, every pair's probability (U, I_loc)] (brNeumfAucCount)."""
     U, I, n1, n2, n3, dev = _neumf_catalog_args("neumf_auc_count", pu, pit, tower, dim, hidden, act)
     off, idx = _csr((skip_off, skip_idx), U, "skip")
-    if list_off.dtype != torch.int64 or not list_off.is_cuda or not list_off.is_contiguous() or list_off.numel() != U + 1:
-        raise TypeError(f"neumf_auc_count: list_off must be a contiguous int64 device tensor of {U + 1} entries")
-    if sorted_.dtype != torch.float32 or not sorted_.is_cuda or not sorted_.is_contiguous() or sorted_.numel() < 1:
-        raise TypeError("neumf_auc_count: sorted_ must be a non-empty contiguous float32 device tensor")
-    _i32_dev(pcnt, "pcnt")
-    if pcnt.numel() != U:
-        raise ValueError(f"neumf_auc_count: pcnt has {pcnt.numel()} entries for {U} users")
+    _auc_list_args("neumf_auc_count", U, list_off, sorted_, pcnt)
     lib = _lib.load()
     ws_bytes = int(lib.brNeumfAucCountWorkspaceBytes(U, I))
     if ws_bytes < 0:

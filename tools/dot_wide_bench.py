@@ -1,5 +1,5 @@
 """Dot-product catalogue top-k and AUC for rows wider than 128 features (ops.dot_catalog_topk_wide / dot_catalog_auc_wide,
-csrc/recommend_dot_wide.hip, csrc/auc_dot_wide.hip) against a matrix path at the same width, in one process, alternating, device
+csrc/recommend_dot_wide.hip, csrc/auc_dot.hip) against a matrix path at the same width, in one process, alternating, device
 events around synchronised work.
 
 brScoreMatrix stops at 128 features, so the project has no matrix path of its own at these widths.  The matrix leg here is the vendor
@@ -84,7 +84,7 @@ def main():
                                 "fused_pairs_per_s": pairs / mf, "gemm_matrix_s": mm, "gemm_matrix_s_all": tm, "speedup": mm / mf,
                                 "fraction_of_floor": floor_s / mf, **more})
 
-        for k in [int(x) for x in a.ks.split(",")]:
+        for k in [int(x) for x in a.ks.split(",") if x]:      # (--ks "": the AUC legs alone)
             def matrix(n_users=a.users):
                 out_s = torch.empty(n_users, k, device=dev)
                 out_i = torch.empty(n_users, k, dtype=torch.int32, device=dev)

@@ -1,7 +1,7 @@
 """What counting the full-catalogue AUC at the item owners costs beside counting it in one launch, on ONE device with W virtual ranks
 (the item table dealt r::W, as tests/test_gpu_sharded_auc.py does): per row width the times of
 
-  whole       : the one brDotCatalogAuc[Wide] call over all users x all candidates (csrc/auc_dot.hip, auc_dot_wide.hip: the kernels the
+  whole       : the one brDotCatalogAuc[Wide] call over all users x all candidates (csrc/auc_dot.hip: the kernels the
                 single-device engines run), its three launches together
   (c) counts  : the W brDotAucOwnerCount calls over all users x one owner's candidates, summed
   (a) around  : the W brDotAucOwnerPositives calls + brAucSortPieces over the W pieces of every user + brAucFinalizeLists
