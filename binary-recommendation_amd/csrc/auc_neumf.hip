@@ -4,11 +4,11 @@
 //
 //   AUC(u) = W / (P N),  2W = sum over positives p and the other items i of 2 [s_i < s_p] + [s_i == s_p]
 //
-// The scoring loop of catalog_topk_kernel<W, ACT> is restated here (neumf_score: acc = b2', the fmaf chain over n1 with
+// The scoring loop of catalog_topk_kernel<W, ACT> is restated in neumf_score.h (neumf_score: acc = b2', the fmaf chain over n1 with
 // act(urow[i] + x), the W3'^T chain, the head with w4mf . dot, sigmoidf_acc), statement for statement, so a pair's probability depends on
 // its user row, its item column and the folded tower only - not on the lane, the split or the kernel that forms it.  The two copies are
 // held equal by a test that compares their dumps bit for bit (tests/test_gpu_neumf_auc.py); recommend.hip keeps its own text because it
-// is the measured kernel.  Four phases, the two in the middle and at the end shared with the dot-product models (auc_owner.hip):
+// is the measured kernel; the ranks (ranks_neumf.hip) include the same header.  Four phases, the two in the middle and at the end shared with the dot-product models (auc_owner.hip):
 //   - neumf_auc_pos_kernel: one wave per user, lane = one of the user's truth entries, 64 at a time: raw[pos_off[u] + j];
 //   - brAucSortPieces: per user one ascending list, NaN dropped, the count P' beside;
 //   - neumf_auc_count_kernel: catalog_topk_kernel's grid and split plan (4 users per workgroup, lane = item, 64 items per step).  The
@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "dot_tile.h"
+#include "neumf_score.h"
 #include "neumf_tower.h"
 #include "topk_list.h"
 
@@ -31,74 +32,6 @@ namespace {
 // sorted positives of a wave's user kept in LDS up to this many: 4 KB per wave, 16 KB per workgroup, so ten workgroups fit the 160 KB
 // of a compute unit - more than the eight (32 waves) it can hold at all: LDS never bounds the occupancy
 constexpr int kNeumfAucLdsCap = 1024;
-
-// catalog_topk_kernel's scoring loop for the item column pcol (lane-private), restated: the head probability of (urow, pcol)
-template <int W, int ACT>
-__device__ __forceinline__ float neumf_score(const float* __restrict__ urow, const float* __restrict__ pcol, int64_t ld_i, int dim, int n1,
-                                             int n3, const float* __restrict__ W2, const float* __restrict__ b2,
-                                             const float* __restrict__ W3t, const float* __restrict__ b3, const float* __restrict__ w4,
-                                             float w4mf, float b4) {
-  float acc[W];
-#pragma unroll
-  for (int j = 0; j < W; ++j) acc[j] = b2[j];
-  float xn = pcol[0];
-#pragma unroll 1
-  for (int i = 0; i < n1; ++i) {                             // the next feature's load is in flight while this one is consumed
-    const float x = xn;
-    xn = pcol[(int64_t)(i + 1 < n1 ? i + 1 : i) * ld_i];
-    const float h = act_apply(urow[i] + x, ACT);
-    const float* __restrict__ w = W2 + (int64_t)i * W;
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] = fmaf(h, w[j], acc[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < W; ++j) acc[j] = act_apply(acc[j], ACT);     // padded columns: W3' rows are zero there
-  float z = b4;
-  for (int m = 0; m < n3; ++m) {
-    const float* __restrict__ w = W3t + (int64_t)m * W;
-    float s = b3[m];
-#pragma unroll
-    for (int j = 0; j < W; ++j) s = fmaf(acc[j], w[j], s);
-    z = fmaf(act_apply(s, ACT), w4[m], z);
-  }
-  float dot = 0.f;
-  for (int d = 0; d < dim; ++d) dot = fmaf(urow[n1 + d], pcol[(int64_t)(n1 + d) * ld_i], dot);
-  z = fmaf(w4mf, dot, z);
-  return sigmoidf_acc(z);                                    // the engine's head probability (predict)
-}
-
-// one wave per user: raw[off[u] + j] = the probability of (u, the user's j-th entry), NaN for an entry outside [0, n_items).  A user
-// whose entries lie past `cap` floats of raw is left alone (brAucSortPieces gives it pcnt -1)
-template <int W, int ACT>
-__global__ __launch_bounds__(256) void neumf_auc_pos_kernel(const float* __restrict__ pu, int64_t ld_u, const float* __restrict__ pit,
-                                                             int64_t ld_i, int64_t n_users, int64_t n_items, int dim, int n1, int n3,
-                                                             const float* __restrict__ tower, TowerLayout L,
-                                                             const int64_t* __restrict__ off, const int32_t* __restrict__ idx,
-                                                             float* __restrict__ raw, int64_t cap) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t u = (int64_t)blockIdx.x * kRecWaves + wave;
-  if (u >= n_users) return;
-  const int64_t o0 = off[u], o1 = off[u + 1], P = o1 - o0;
-  if (P <= 0 || o0 < 0 || o1 > cap) return;
-
-  const float* __restrict__ urow = pu + u * ld_u;            // [Pu (b1 included) | user mf]
-  const float* __restrict__ W2 = tower + L.w2;
-  const float* __restrict__ b2 = tower + L.b2;
-  const float* __restrict__ W3t = tower + L.w3t;
-  const float* __restrict__ b3 = tower + L.b3;
-  const float* __restrict__ w4 = tower + L.w4;
-  const float w4mf = tower[L.w4mf], b4 = tower[L.b4];
-
-  for (int64_t j0 = 0; j0 < P; j0 += 64) {
-    const int64_t j = j0 + lane;
-    const int64_t p = j < P ? (int64_t)idx[o0 + j] : -1;
-    const bool ok = p >= 0 && p < n_items;
-    const int64_t pc = ok ? p : 0;                           // (a lane without an entry scores item 0: every load stays in bounds)
-    const float prob = neumf_score<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, W2, b2, W3t, b3, w4, w4mf, b4);
-    if (j < P) raw[o0 + j] = ok ? prob : __builtin_nanf("");
-  }
-}
 
 template <int W, int ACT>
 __global__ __launch_bounds__(256) void neumf_auc_count_kernel(const float* __restrict__ pu, int64_t ld_u, const float* __restrict__ pit,
@@ -216,39 +149,12 @@ __global__ __launch_bounds__(256) void neumf_auc_sum_splits_kernel(const uint64_
   out[u] = w2;
 }
 
-struct Operands {
-  const float* pu; int64_t ld_u; const float* pit; int64_t ld_i; int64_t U, I; int dim, n1, n3; const float* tower; TowerLayout L;
-};
-
-template <int W, int ACT>
-void launch_pos(hipStream_t st, const Operands& a, const int64_t* off, const int32_t* idx, float* raw, int64_t cap) {
-  neumf_auc_pos_kernel<W, ACT><<<(unsigned)ceil_div(a.U, kRecWaves), 256, 0, st>>>(a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3,
-                                                                                   a.tower, a.L, off, idx, raw, cap);
-}
-
 template <int W, int ACT>
 void launch_count(hipStream_t st, const Operands& a, const int64_t* ex_off, const int32_t* ex_idx, const int64_t* loff, const float* sorted,
                   const int32_t* pcnt, int64_t cap, int64_t cps, int64_t S, uint64_t* part, float* dump) {
   const dim3 grid((unsigned)ceil_div(a.U, kRecWaves), (unsigned)S);
   neumf_auc_count_kernel<W, ACT><<<grid, 256, 0, st>>>(a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3, a.tower, a.L, ex_off, ex_idx,
                                                        loff, sorted, pcnt, cap, cps, S, part, dump);
-}
-
-// f(integral_constant<W>, integral_constant<ACT>) at the instantiated tower width and activation; false: no kernel for n2
-template <typename F>
-bool dispatch_tower(int n2, int act, F&& f) {
-  auto with_act = [&](auto w) {
-    if (act == BR_ACT_SIGMOID) f(w, std::integral_constant<int, BR_ACT_SIGMOID>{});
-    else if (act == BR_ACT_RELU) f(w, std::integral_constant<int, BR_ACT_RELU>{});
-    else f(w, std::integral_constant<int, BR_ACT_LINEAR>{});
-  };
-#define BR_TOWER_W(WW) case WW: with_act(std::integral_constant<int, WW>{}); return true;
-  switch (tower_width(n2)) {
-    BR_TOWER_W(8) BR_TOWER_W(16) BR_TOWER_W(24) BR_TOWER_W(32) BR_TOWER_W(40) BR_TOWER_W(48) BR_TOWER_W(56)
-    BR_TOWER_W(64) BR_TOWER_W(96) BR_TOWER_W(128)
-  }
-#undef BR_TOWER_W
-  return false;
 }
 
 int64_t count_part_bytes(int64_t n_users, int64_t n_items) {
@@ -260,16 +166,6 @@ int64_t count_part_bytes(int64_t n_users, int64_t n_items) {
 // brNeumfCatalogAuc's workspace ahead of the three float arrays: the count's partials, 2W uint64 [n_users], P' int32 [n_users]
 int64_t auc_fixed_bytes(int64_t n_users, int64_t n_items) {
   return count_part_bytes(n_users, n_items) + align256(n_users * 8) + align256(n_users * 4);
-}
-
-int positives(const char* name, const Operands& a, int n2, int act, const int64_t* off, const int32_t* idx, float* raw, int64_t cap,
-              hipStream_t st) {
-  if (!dispatch_tower(n2, act, [&](auto w, auto ac) { launch_pos<decltype(w)::value, decltype(ac)::value>(st, a, off, idx, raw, cap); })) {
-    br::set_error("%s: no kernel for n2 = %d", name, n2);
-    return BR_ERR_UNSUPPORTED;
-  }
-  BR_CHECK_LAUNCH(name);
-  return BR_OK;
 }
 
 int count(const char* name, const Operands& a, int n2, int act, const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off,

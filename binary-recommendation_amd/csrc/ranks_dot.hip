@@ -6,7 +6,8 @@
 // without the U x I score matrix, and from those integers NDCG@k, recall@k, hit@k and MRR (brRankMetrics).  DESIGN.md 4k.
 //
 // The launches of brDotCatalogRanks:
-//   - rank_init_kernel: the bins zeroed, the outputs -1;
+//   - rank_init_kernel (rank_bins.h, as the excluded and the finalize kernels below: one text with ranks_neumf.hip): the bins zeroed,
+//     the outputs -1;
 //   - auc_pos_kernel (auc_pos.h), as the AUC entries launch it: a positive's score bit for bit the catalogue pass's, the user's
 //     non-NaN positives sorted ascending v_0 <= ... <= v_{n-1};
 //   - dot_ranks_kernel / dot_ranks_wide_kernel: the tile streams of dot_auc_pass and dot_auc_wide_pass (auc_count.h), copies kept the
@@ -28,6 +29,7 @@
 #include "common.h"
 #include "dot_tile.h"
 #include "dot_wide.h"
+#include "rank_bins.h"
 
 namespace br {
 namespace {
@@ -43,30 +45,6 @@ constexpr int kRankMaxKs = 8;
 
 void ranks_plan(int64_t n_users, int64_t n_items, int users_per_wave, int64_t* splits, int64_t* steps_per_split) {
   split_plan(ceil_div(n_items, kRankNT), n_users, 4 * users_per_wave, splits, steps_per_split);
-}
-
-// workspace: P' int32 [n_users], the raw and the sorted positive scores float [n_truth + 1] each, the bins and the tie bins int32
-// [n_truth + n_users] each (user u: n + 1 bins from off[u] + u on)
-struct RanksWs {
-  int64_t pcnt, raw, sorted, bins, ties, total, n_bins;
-};
-RanksWs ranks_ws(int64_t n_users, int64_t n_truth) {
-  RanksWs w;
-  w.n_bins = n_truth + n_users;
-  w.pcnt = 0;
-  w.raw = w.pcnt + align256(4 * n_users);
-  w.sorted = w.raw + align256(4 * (n_truth + 1));
-  w.bins = w.sorted + align256(4 * (n_truth + 1));
-  w.ties = w.bins + align256(4 * w.n_bins);
-  w.total = w.ties + align256(4 * w.n_bins);
-  return w;
-}
-
-__global__ __launch_bounds__(256) void rank_init_kernel(int32_t* __restrict__ bins, int64_t n_bins, int32_t* __restrict__ above,
-                                                         int32_t* __restrict__ tied, int64_t n_truth) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_bins; i += stride) bins[i] = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_truth; i += stride) above[i] = tied[i] = -1;
 }
 
 // One row tile's 16 scores of a lane (CT column tiles x the lane's 4 users r) against their users' sorted lists.  ok: bit 4 ct + r
@@ -497,96 +475,6 @@ __global__ __launch_bounds__(256) void dot_ranks_wide_kernel(const float* __rest
   }
 }
 
-// #{entries < s} and #{entries <= s} of the ascending v[0 .. n)
-__device__ __forceinline__ void sorted_bounds(const float* v, int n, float s, int* lo_out, int* hi_out) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (v[mid] < s) lo = mid + 1; else hi = mid;
-  }
-  *lo_out = lo;
-  hi = n;
-  int l2 = lo;
-  while (l2 < hi) {
-    const int mid = (l2 + hi) >> 1;
-    if (v[mid] <= s) l2 = mid + 1; else hi = mid;
-  }
-  *hi_out = l2;
-}
-
-__device__ __forceinline__ bool row_has(const int32_t* __restrict__ v, int64_t lo, int64_t hi, int32_t x) {
-  const int64_t end = hi;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (v[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo < end && v[lo] == x;
-}
-
-// one wave per user: a positive that is excluded too is no candidate of the user's positives (itself included): -1 where the list
-// terms of rank_finalize_kernel count it
-__global__ __launch_bounds__(256) void rank_excluded_kernel(const int64_t* __restrict__ off, const int32_t* __restrict__ idx,
-                                                             const int64_t* __restrict__ xoff, const int32_t* __restrict__ xidx,
-                                                             const float* __restrict__ raw, const float* __restrict__ sorted,
-                                                             const int32_t* __restrict__ pcnt, int64_t n_users, int32_t* bins, int32_t* ties) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (u >= n_users) return;
-  const int n = pcnt[u];
-  if (n <= 0) return;
-  const int64_t o0 = off[u], o1 = off[u + 1], x0 = xoff[u], x1 = xoff[u + 1];
-  if (x1 <= x0) return;
-  for (int64_t e = o0 + lane; e < o1; e += 64) {
-    const float s = raw[e];
-    if (s != s || !row_has(xidx, x0, x1, idx[e])) continue;
-    int lo, hi;
-    sorted_bounds(sorted + o0, n, s, &lo, &hi);
-    atomicAdd(&bins[o0 + u + lo], -1);
-    atomicAdd(&ties[o0 + u + lo], -1);
-  }
-}
-
-// one wave per user: S[b] = sum of the bins b .. n in place, then the user's entries
-__global__ __launch_bounds__(256) void rank_finalize_kernel(const int64_t* __restrict__ off, const int32_t* __restrict__ idx,
-                                                             const int64_t* __restrict__ xoff, const int32_t* __restrict__ xidx,
-                                                             const float* __restrict__ raw, const float* __restrict__ sorted,
-                                                             const int32_t* __restrict__ pcnt, int64_t n_users, int32_t* bins,
-                                                             const int32_t* __restrict__ ties, int32_t* __restrict__ above,
-                                                             int32_t* __restrict__ tied) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (u >= n_users) return;
-  const int n = pcnt[u];
-  if (n <= 0) return;                                                 // no positive with a rank: the entries keep (-1, -1)
-  const int64_t o0 = off[u], o1 = off[u + 1];
-  int32_t* const B = bins + o0 + u;
-  int carry = 0;
-  for (int t = n; t >= 0; t -= 64) {                                  // lane l: bin t - l, the higher bins first
-    const int b = t - lane;
-    int x = b >= 0 ? B[b] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    x += carry;
-    if (b >= 0) B[b] = x;
-    carry = __shfl(x, 63, 64);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");             // this wave's stores before its loads below
-  __builtin_amdgcn_wave_barrier();
-  const int64_t x0 = xoff ? xoff[u] : 0, x1 = xoff ? xoff[u + 1] : 0;
-  for (int64_t e = o0 + lane; e < o1; e += 64) {
-    const float s = raw[e];
-    if (s != s) continue;
-    int lo, hi;
-    sorted_bounds(sorted + o0, n, s, &lo, &hi);
-    const bool excluded = x1 > x0 && row_has(xidx, x0, x1, idx[e]);
-    above[e] = B[hi] + (n - hi);
-    tied[e] = ties[o0 + u + lo] + (hi - lo) - (excluded ? 0 : 1);
-  }
-}
-
 struct RankKs {
   int32_t k[kRankMaxKs];
 };
@@ -677,13 +565,10 @@ extern "C" int brDotCatalogRanks(const float* Q, int64_t ld_q, int64_t n_users, 
   float* sorted = (float*)((char*)ws + w.sorted);
   int32_t* bins = (int32_t*)((char*)ws + w.bins);
   int32_t* ties = (int32_t*)((char*)ws + w.ties);
-  const int64_t n_init = (w.ties - w.bins) / 4 + w.n_bins;         // the bins, their padding and the tie bins: one run of int32
   const int64_t cap = n_truth;                                       // truth entries [0, cap) fit; a user past them keeps (-1, -1)
   const int vec = rows_vec4(C, ld_c, dim);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t most = n_init > n_truth ? n_init : n_truth;
-  rank_init_kernel<<<(unsigned)(ceil_div(most, 256) < 4096 ? ceil_div(most, 256) : 4096), 256, 0, st>>>(bins, n_init, out_above, out_tied,
-                                                                                                    n_truth);
+  launch_rank_init(st, w, ws, out_above, out_tied, n_truth);
   BR_CHECK_LAUNCH("brDotCatalogRanks init");
   const unsigned per_user = (unsigned)ceil_div(n_users, 4);
   int64_t S, sps;
@@ -709,11 +594,12 @@ extern "C" int brDotCatalogRanks(const float* Q, int64_t ld_q, int64_t n_users, 
   }
   BR_CHECK_LAUNCH("brDotCatalogRanks");
   if (excl_off) {
-    rank_excluded_kernel<<<per_user, 256, 0, st>>>(truth_off, truth_idx, excl_off, excl_idx, raw, sorted, pcnt, n_users, bins, ties);
+    rank_excluded_kernel<<<per_user, 256, 0, st>>>(truth_off, truth_idx, excl_off, excl_idx, raw, truth_off, sorted, pcnt, cap, n_users, bins,
+                                                   ties);
     BR_CHECK_LAUNCH("brDotCatalogRanks excluded positives");
   }
-  rank_finalize_kernel<<<per_user, 256, 0, st>>>(truth_off, truth_idx, excl_off, excl_idx, raw, sorted, pcnt, n_users, bins, ties, out_above,
-                                                 out_tied);
+  rank_finalize_kernel<<<per_user, 256, 0, st>>>(truth_off, truth_idx, excl_off, excl_idx, raw, truth_off, sorted, pcnt, cap, n_users, bins, ties,
+                                                 out_above, out_tied);
   BR_CHECK_LAUNCH("brDotCatalogRanks finalize");
   return BR_OK;
 }

@@ -370,6 +370,27 @@ class NeuMFModel(RModel):
         has = np.array([len(t) > 0 for _u, t in gt], dtype=bool)
         return float(np.mean(auc[has]))
 
+    def rank_metrics(self, ground_truth, items, ks=(10,), excludeSeen=False) -> dict:
+        """MRR and, per cutoff k of ks (at most 8), NDCG@k, recall@k and hit rate@k of the NeuMF probabilities over all `items`, from the
+        exact rank of every true item among them (NeuMFEngine.rank_metrics: one fused pass, no users x items matrix, no limit on the
+        rank): the means over the users that have positives, as Python floats {"mrr", "ndcg@k", "recall@k", "hr@k"}.  ground_truth:
+        iterable of (user_id, [true item ids]); a true item outside `items` raises, as in full_auc.  excludeSeen: the products a
+        customer has in the training split (prepareToTrain) are no candidates (a true item among them is still ranked, against the
+        others).  The rank is pessimistic: r = 1 + the candidates scoring above + those scoring EQUAL.  Under a process group a
+        collective: every rank calls it with its own users and the same `items` (ShardedNeuMFEngine.catalog_ranks)."""
+        from .topk_metrics import seen_csr
+        gt, _col, truth = _truth_of(ground_truth, items, lambda: self.model.engine.device, strict=True)
+        e = self.model.engine
+        users = [u for u, _ in gt]
+        ex = None
+        if excludeSeen:
+            su, si = getattr(self, "_seen", ((), ()))
+            ex = seen_csr(users, list(items), su.tolist() if hasattr(su, "tolist") else su, si.tolist() if hasattr(si, "tolist") else si, e.device)
+        res = e.rank_metrics(_to_dev(np.asarray(users), e.device, e.id_dtype), truth, ks=ks,
+                             items=_to_dev(np.asarray(items), e.device, e.id_dtype), exclude=ex)
+        e.check_ids()
+        return _mean_over_users_with_positives(res)
+
     def mean_average_precision_k(self, ground_truth, items, k=100) -> float:
         """mean_average_precision_k (src/models/bpr.py:257-289) of the NeuMF probabilities: AP of each user's top-k from
         NeuMFEngine.recommend (k <= 256) / min(len(actual), k).  Under a process group a collective."""

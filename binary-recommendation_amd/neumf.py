@@ -712,6 +712,25 @@ class NeuMFEngine(RowAdam):
         users, items, tower, pu, pit = self._catalog_operands(users, items)
         return ops.neumf_catalog_auc(pu, pit, tower, cfg.dim, tuple(cfg.hidden), cfg.act, off, idx, dump_probs=bool(dump_probs))
 
+    def catalog_ranks(self, users, truth, items=None, exclude=None, dump_probs=False):
+        """Per truth entry, in CSR order, the exact (above, tied) int32 counts of the probability predict returns over the whole candidate
+        list, in inference mode: recommend's set-up, then one fused evaluation without the U x I matrix (ops.neumf_catalog_ranks,
+        csrc/ranks_neumf.hip).  truth / items as in full_auc; exclude: (off, idx) CSR over `users` of candidate POSITIONS never offered
+        (topk_metrics.seen_csr): an excluded truth entry is still ranked, against the others.  dump_probs=True also returns every pair's
+        probability (U x I).
+        (The row-sharded engine overrides this with a collective of the same contract: parallel.py ranks_at_owners.)"""
+        cfg = self.cfg
+        users, items, tower, pu, pit = self._catalog_operands(users, items)
+        return ops.neumf_catalog_ranks(pu, pit, tower, cfg.dim, tuple(cfg.hidden), cfg.act, truth[0], truth[1], exclude=exclude,
+                                       dump_probs=bool(dump_probs))
+
+    def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
+        """{"mrr", "ndcg@k", "recall@k", "hr@k"} per user (float32 (U,) on the device) over the whole candidate list, from the exact
+        ranks of catalog_ranks: r = 1 + above + tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that
+        scores everything equal earns nothing.  ks: up to 8 cutoffs; NaN for a user without positives (ops.rank_metrics)."""
+        above, tied = self.catalog_ranks(users, truth, items=items, exclude=exclude)
+        return ops.rank_metrics(above, tied, truth[0], ks)
+
     def evaluate_batch(self, users, items, labels):
         """inference-mode forward + loss/metric sums accumulated into self.msums (no grads)."""
         self._infer(users, items, labels, users.shape[0])

@@ -1101,6 +1101,105 @@ def neumf_catalog_auc(pu, pit, tower, dim: int, hidden, act: str, truth_off, tru
     return (out, dump) if dump_probs else out
 
 
+# ------------------------------------------------------------------------------ NeuMF catalogue ranks (csrc/ranks_neumf.hip)
+# dot_catalog_ranks' contract over the operands and the probabilities of neumf_catalog_auc; rank_metrics takes the integers.
+def neumf_catalog_ranks(pu, pit, tower, dim: int, hidden, act: str, truth_off, truth_idx, exclude=None, dump_probs=False):
+    """The operands of neumf_catalog_auc, truth (ops.truth_csr over the rows of pu: ascending positions into the item list), exclude:
+    (off, idx) CSR over the rows of pu of positions never offered as candidates (topk_metrics.seen_csr) -> (above, tied) int32, one
+    entry per truth entry in CSR order [, every pair's probability (U, I)]: how many candidates (every non-excluded item but the entry
+    itself, the user's other positives included) have a probability above the positive's and how many tie with it, counted exactly on
+    the probabilities neumf_catalog_auc / neumf_catalog_topk form (same bits); the U x I matrix is not stored.  An excluded position
+    that is a truth entry is still ranked (against the non-excluded others).  (-1, -1) for a positive whose probability is NaN; a NaN
+    candidate is never above and never tied (brNeumfCatalogRanks)."""
+    U, I, n1, n2, n3, dev = _neumf_catalog_args("neumf_catalog_ranks", pu, pit, tower, dim, hidden, act)
+    n_truth = truth_idx.numel() if isinstance(truth_idx, torch.Tensor) else 0
+    off, idx = _csr((truth_off, truth_idx), U, "truth")
+    xoff, xidx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
+    lib = _lib.load()
+    ws_bytes = int(lib.brNeumfCatalogRanksWorkspaceBytes(U, I, n_truth))
+    if ws_bytes < 0:
+        raise ValueError(f"neumf_catalog_ranks: bad sizes U={U} I={I} truth entries={n_truth}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    above = torch.empty(n_truth, dtype=torch.int32, device=dev)
+    tied = torch.empty(n_truth, dtype=torch.int32, device=dev)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_probs else None
+    check(lib.brNeumfCatalogRanks(*_neumf_operands(pu, pit, U, I, dim, n1, n2, n3, act, tower), off.data_ptr(), idx.data_ptr(), n_truth,
+                                  _p(xoff), _p(xidx), above.data_ptr() if n_truth else ws.data_ptr(), tied.data_ptr() if n_truth else ws.data_ptr(),
+                                  _p(dump), ws.data_ptr(), ws_bytes, _stream()), "brNeumfCatalogRanks")
+    return (above, tied, dump) if dump_probs else (above, tied)
+
+
+def _rank_bins_args(who: str, U: int, list_off, sorted_, pcnt, bins, ties):
+    """the checks the phase entries of the ranks (`who`) make on the users' full lists and their bins -> cap"""
+    _auc_list_args(who, U, list_off, sorted_, pcnt)
+    cap = sorted_.numel() - 1
+    for t, name in ((bins, "bins"), (ties, "ties")):
+        _i32_dev(t, name)
+        if t.dim() != 1 or t.numel() < max(cap + U, 1):
+            raise ValueError(f"{who}: {name} must be 1-D with at least cap + U = {cap + U} entries (has {t.numel()})")
+    return cap
+
+
+def rank_bins(n_users: int, cap: int, device):
+    """-> (bins, ties): the zeroed int32 bins and tie bins of `n_users` users whose lists lie in `cap` floats (n + 1 each per user)"""
+    n = max(int(cap) + int(n_users), 1)
+    return torch.zeros(n, dtype=torch.int32, device=device), torch.zeros(n, dtype=torch.int32, device=device)
+
+
+def neumf_rank_count(pu, pit, tower, dim: int, hidden, act: str, skip_off, skip_idx, list_off, sorted_, pcnt, bins, ties, dump_probs=False):
+    """The catalogue pass of neumf_catalog_ranks over the candidates one owner holds.  The operands of neumf_auc_positives; (skip_off,
+    skip_idx): per user the owner's truth and excluded positions in one ascending list of LOCAL positions; list_off / sorted_ / pcnt of
+    auc_sort_pieces: every user's FULL list; bins / ties of rank_bins: the call ADDS this owner's counts into them (user u's n + 1 bins
+    from list_off[u] + u on) -> None [every pair's probability (U, I_loc)] (brNeumfRankCount)."""
+    U, I, n1, n2, n3, dev = _neumf_catalog_args("neumf_rank_count", pu, pit, tower, dim, hidden, act)
+    off, idx = _csr((skip_off, skip_idx), U, "skip")
+    cap = _rank_bins_args("neumf_rank_count", U, list_off, sorted_, pcnt, bins, ties)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_probs else None
+    check(_lib.load().brNeumfRankCount(*_neumf_operands(pu, pit, U, I, dim, n1, n2, n3, act, tower), off.data_ptr(), idx.data_ptr(),
+                                       list_off.data_ptr(), sorted_.data_ptr(), pcnt.data_ptr() if U else sorted_.data_ptr(), cap,
+                                       bins.data_ptr(), ties.data_ptr(), _p(dump), _stream()), "brNeumfRankCount")
+    return dump
+
+
+def _rank_entry_args(who: str, U: int, entry_off, entry_idx, raw, exclude):
+    off, idx = _csr((entry_off, entry_idx), U, "entries")
+    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.float32 or not raw.is_cuda or not raw.is_contiguous() or raw.dim() != 1:
+        raise TypeError(f"{who}: raw must be a contiguous 1-D float32 device tensor")
+    xoff, xidx = _csr(exclude, U, "exclude") if exclude is not None else (None, None)
+    return off, idx, (raw if raw.numel() else torch.zeros(1, dtype=torch.float32, device=off.device)), xoff, xidx
+
+
+def rank_bins_excluded(entry_off, entry_idx, exclude, raw, list_off, sorted_, pcnt, bins, ties):
+    """(entry_off, entry_idx): the truth entries ranked here, raw: their scores, at least entry_off[-1] of them (neumf_auc_positives,
+    dot_auc_owner_positives; entry_idx may have spare capacity behind them, as csr_split_by_owner leaves it), exclude:
+    (off, idx) CSR in the positions of entry_idx (LOCAL ones at an owner); list_off / sorted_ / pcnt / bins / ties as neumf_rank_count:
+    every entry that is also excluded takes 1 out of its bin and its tie bin, in place (brRankBinsExcluded)."""
+    U = list_off.numel() - 1
+    cap = _rank_bins_args("rank_bins_excluded", U, list_off, sorted_, pcnt, bins, ties)
+    if exclude is None:
+        raise ValueError("rank_bins_excluded: an exclusion CSR is required")
+    off, idx, raw, xoff, xidx = _rank_entry_args("rank_bins_excluded", U, entry_off, entry_idx, raw, exclude)
+    check(_lib.load().brRankBinsExcluded(off.data_ptr(), idx.data_ptr(), xoff.data_ptr(), xidx.data_ptr(), raw.data_ptr(), list_off.data_ptr(),
+                                         sorted_.data_ptr(), pcnt.data_ptr() if U else sorted_.data_ptr(), cap, U, bins.data_ptr(), ties.data_ptr(),
+                                         _stream()), "brRankBinsExcluded")
+
+
+def rank_bins_finalize(entry_off, entry_idx, exclude, raw, list_off, sorted_, pcnt, bins, ties):
+    """The arguments of rank_bins_excluded (exclude may be None) over the bins summed over all owners -> (above, tied) int32, one per
+    entry of entry_idx (its capacity), (-1, -1) for an entry without a rank and past entry_off[-1].  The suffix sums are formed in `bins` IN PLACE: one call per copy of the
+    bins (brRankBinsFinalize)."""
+    U = list_off.numel() - 1
+    cap = _rank_bins_args("rank_bins_finalize", U, list_off, sorted_, pcnt, bins, ties)
+    off, idx, raw, xoff, xidx = _rank_entry_args("rank_bins_finalize", U, entry_off, entry_idx, raw, exclude)
+    n = entry_idx.numel()
+    above = torch.full((max(n, 1),), -1, dtype=torch.int32, device=off.device)
+    tied = torch.full((max(n, 1),), -1, dtype=torch.int32, device=off.device)
+    check(_lib.load().brRankBinsFinalize(off.data_ptr(), idx.data_ptr(), _p(xoff), _p(xidx), raw.data_ptr(), list_off.data_ptr(), sorted_.data_ptr(),
+                                         pcnt.data_ptr() if U else sorted_.data_ptr(), cap, U, bins.data_ptr(), ties.data_ptr(), above.data_ptr(),
+                                         tied.data_ptr(), _stream()), "brRankBinsFinalize")
+    return above[:n], tied[:n]
+
+
 # ------------------------------------------------------------------------------ 8f-1 evaluation: full AUC, MAP@k, hit counts
 def truth_csr(n_users: int, user_rows, item_cols, device):
     """Ground truth of `n_users` rows as the CSR the eval kernels take: (offsets int64 (n_users + 1), column indices int32 ascending

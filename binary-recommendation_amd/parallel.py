@@ -540,6 +540,113 @@ def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_use
     return ops.auc_finalize_lists(recv, W, U, t_off, pcnt[u0:u0 + U], I, list_stride=U)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Exact catalogue ranks counted where the item rows live: auc_at_owners' turn for catalog_ranks.  Steps 1 to 4 are
+# auc_at_owners': every user's full sorted list of positives on every rank.  Then each rank counts the queries of ALL ranks against its
+# own candidates into bins laid out by the GLOBAL truth offsets, the integer bins are summed over the ranks, each rank finalizes the
+# truth entries it owns (it holds their raw scores) and the (above, tied) pairs are put together: integers add exactly, so the result
+# is the single-device one entry for entry.
+# ---------------------------------------------------------------------------------------------------------------------
+def csr_union(a, b, n_cols: int):
+    """two CSRs (off, idx) over the same rows, per row ascending unique positions in [0, n_cols) (idx may have spare capacity behind
+    off[-1], as csr_split_by_owner leaves it) -> the CSR of their union per row, ascending.  Two host syncs (the entry counts)."""
+    n_rows, dev = a[0].shape[0] - 1, a[0].device
+    keys = []
+    for off, idx in (a, b):
+        n = int(off[-1].item())
+        rows = torch.repeat_interleave(torch.arange(n_rows, dtype=torch.int64, device=dev), off[1:] - off[:-1], output_size=n)
+        keys.append(rows * n_cols + idx[:n].to(torch.int64))
+    k = torch.unique(torch.cat(keys))                       # sorted: by row, then by position
+    off = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.bincount(k // n_cols, minlength=n_rows).cumsum(0)
+    return off, (k % n_cols).to(torch.int32).contiguous()
+
+
+def ranks_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, exclude, fetch_user_rows, queries_of, candidates_of, count, positives):
+    """The single-device `catalog_ranks` contract on row-sharded tables.  A collective: every rank calls it with its own `users` (device
+    ids; counts may differ and may be 0), the SAME `items` (None = every item row), the truth CSR (off, idx) over its own users in
+    ascending positions of `items` and optionally an exclusion CSR of the same kind; it gets (above, tied) int32 for its own truth
+    entries, in CSR order.  fetch_user_rows, queries_of and candidates_of as in recommend_at_owners; the model's two scoring phases over
+    this rank's candidates: positives(q, cand, pos_off, pos_idx, out) (ops.neumf_auc_positives) and count(q, cand, skip_off, skip_idx,
+    list_off, sorted_, pcnt, bins, ties) (ops.neumf_rank_count), which adds into the bins."""
+    from . import ops
+    W, r, dev = ctx.world, ctx.rank, users.device
+    if items is None:
+        items = torch.arange(n_item_rows, dtype=users.dtype, device=dev)
+    U, I = users.shape[0], items.shape[0]
+    if I < 1:
+        raise ValueError("catalog_ranks: empty candidate list")
+    n_truth = int(truth[1].numel())
+    t_off, t_idx = ops._csr(truth, U, "truth")
+    t_idx = t_idx[:n_truth]
+    has_ex = exclude is not None
+    if has_ex:
+        ex_off, ex_idx = ops._csr(exclude, U, "exclude")
+        ex_idx = ex_idx[:int(exclude[1].numel())]
+    none = torch.empty(0, dtype=torch.int32, device=dev)
+    # 1. user, truth and exclusion counts, and that the candidate lists agree
+    u_counts, t_counts = _owners_meta(ctx, "catalog_ranks", U, n_truth, items, 0)
+    _u, e_counts = _owners_meta(ctx, "catalog_ranks", U, int(exclude[1].numel()) if has_ex else -1, items, 0)
+    U_all, T_all = sum(u_counts), sum(t_counts)
+    if U_all == 0:
+        return none, none.clone()
+    # 2. the queries, the truth lists and the exclusion lists (global positions) of all ranks on every rank
+    q_all = queries_of(_all_gather_ragged(ctx, fetch_user_rows(users), u_counts))
+    off_all, idx_all = _all_gather_csr(ctx, t_off, t_idx, U, u_counts, t_counts)
+    any_ex = any(c >= 0 for c in e_counts)
+    if any_ex:
+        x_all = _all_gather_csr(ctx, ex_off if has_ex else None, ex_idx if has_ex else none, U, u_counts, e_counts)
+    # 3. this rank's candidates, and its share of every user's positives and excluded positions in its local positions
+    plan = _CandidatePlan(ctx, items)
+    excl = None
+    if plan.n_loc:
+        cand = candidates_of(plan.local_rows)
+        pos_off, pos_idx = plan.split_csr(off_all, idx_all)
+        lens = (pos_off[1:] - pos_off[:-1]).to(torch.int32)
+        if any_ex:
+            excl = plan.split_csr(*x_all)
+    else:                        # no candidate of the list lives here: no positives, no counts - but every collective below is joined
+        lens = torch.zeros(U_all, dtype=torch.int32, device=dev)
+    # 4. every owner's raw scores on every rank, the users' full lists sorted from the receive buffer in place (auc_at_owners step 4)
+    lens_all = ctx.all_gather_rows(lens.view(1, U_all)).to(torch.int64)
+    m = int(lens_all.sum(1).max().item())
+    raw = torch.zeros(1, max(m, 1), dtype=torch.float32, device=dev)
+    if plan.n_loc and m:
+        positives(q_all, cand, pos_off, pos_idx, raw)
+    raw_all = ctx.all_gather_rows(raw) if m else raw.repeat(W, 1)
+    piece_off = torch.zeros(W, U_all + 1, dtype=torch.int64, device=dev)
+    piece_off[:, 1:] = lens_all.cumsum(1)
+    piece_off += (torch.arange(W, dtype=torch.int64, device=dev) * raw.shape[1]).view(W, 1)
+    sorted_, pcnt = ops.auc_sort_pieces(raw_all, piece_off, off_all, T_all)
+    # 5. all queries x the local candidates into zeroed bins over the global lists, then this rank's excluded positives out of them
+    bins, ties = ops.rank_bins(U_all, T_all, dev)
+    if plan.n_loc:
+        skip = csr_union((pos_off, pos_idx), excl, plan.n_loc) if excl is not None else (pos_off, pos_idx)
+        count(q_all, cand, skip[0], skip[1], off_all, sorted_, pcnt, bins, ties)
+        if excl is not None:
+            ops.rank_bins_excluded(pos_off, pos_idx, excl, raw.view(-1), off_all, sorted_, pcnt, bins, ties)
+    # 6. the integer bins of all owners summed on every rank
+    ctx.all_reduce_sum(bins)
+    ctx.all_reduce_sum(ties)
+    # 7. every owner finalizes the entries it holds (entry CSR: its split CSR, raw: its own piece; list CSR: the global one) and puts
+    #    them where they stand in the global truth order: brCsrSplitByOwner keeps the input order, so its entries are the global ones
+    #    with g2l >= 0, in order.  1 + value, 0 where another rank owns the entry: the sum over the ranks is 1 + the owner's value
+    out = torch.zeros(2, max(T_all, 1), dtype=torch.int32, device=dev)
+    if plan.n_loc and T_all:
+        a_loc, t_loc = ops.rank_bins_finalize(pos_off, pos_idx, excl, raw.view(-1), off_all, sorted_, pcnt, bins, ties)
+        g2l = torch.full((I,), -1, dtype=torch.int32, device=dev)
+        g2l[plan.l2g[plan.lo:plan.hi].long()] = torch.arange(plan.n_loc, dtype=torch.int32, device=dev)
+        g = idx_all.long()
+        own = ((g >= 0) & (g < I)) & (g2l[g.clamp(0, I - 1)] >= 0)
+        slot = (own.cumsum(0) - 1).clamp(min=0)
+        out[0, :T_all] = torch.where(own, a_loc[slot] + 1, 0)
+        out[1, :T_all] = torch.where(own, t_loc[slot] + 1, 0)
+    ctx.all_reduce_sum(out)
+    out -= 1                     # an entry no rank owns (a position outside the list) keeps -1
+    t0 = sum(t_counts[:r])
+    return out[0, t0:t0 + n_truth].contiguous(), out[1, t0:t0 + n_truth].contiguous()
+
+
 def make_sharded_engine(base_cls):
     """ShardedNeuMFEngine = NeuMFEngine with its embed / table-optimizer hooks replaced by the
     row-sharded exchange.  (Factory so this module stays importable without the HIP library.)"""
@@ -794,6 +901,21 @@ def make_sharded_engine(base_cls):
                 self.ctx, users, items, self.num_item_rows, truth, fetch, queries_of, candidates_of,
                 positives=lambda q, c, po, pi, out: ops.neumf_auc_positives(q, c, tower, cfg.dim, hidden, cfg.act, po, pi, out=out),
                 count=lambda q, c, so, si, lo, srt, pc: ops.neumf_auc_count(q, c, tower, cfg.dim, hidden, cfg.act, so, si, lo, srt, pc))
+
+        def catalog_ranks(self, users, truth, items=None, exclude=None, dump_probs=False):
+            """NeuMFEngine.catalog_ranks on the row-sharded tables (ranks_at_owners): a collective - every rank calls it with its own
+            users (any number, also none), their truth CSR (and optionally their exclusion CSR) and the same `items`, and gets the
+            single-device integers of ITS truth entries.  Every owner projects, scores and counts only the items whose rows it holds;
+            user rows, the positives' probabilities and the integer bins travel."""
+            if dump_probs:
+                raise NotImplementedError("catalog_ranks(dump_probs=True) on the row-sharded engine is not supported: no rank forms the "
+                                          "probabilities of another owner's items; score with a single-device engine")
+            cfg, hidden = self.cfg, tuple(self.cfg.hidden)
+            users, items, tower, fetch, queries_of, candidates_of = self._owner_catalog(users, items)
+            return ranks_at_owners(
+                self.ctx, users, items, self.num_item_rows, truth, exclude, fetch, queries_of, candidates_of,
+                count=lambda q, c, so, si, lo, srt, pc, b, t: ops.neumf_rank_count(q, c, tower, cfg.dim, hidden, cfg.act, so, si, lo, srt, pc, b, t),
+                positives=lambda q, c, po, pi, out: ops.neumf_auc_positives(q, c, tower, cfg.dim, hidden, cfg.act, po, pi, out=out))
 
         def _embed_backward_apply(self, users, items, B):
             cfg, D = self.cfg, self.cfg.dim

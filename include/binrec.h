@@ -654,6 +654,55 @@ int brNeumfCatalogAuc(const float* pu, int64_t ld_u, int64_t n_users, const floa
                       int n2, int n3, int act, const float* tower, const int64_t* truth_off, const int32_t* truth_idx, float* out_auc,
                       float* dump_probs, void* ws, int64_t ws_bytes, brStream stream);
 
+/* ---- Catalogue ranks for NeuMF: NDCG@k, MRR, recall@k, hit@k over the whole catalogue, single-device and at the item owners: csrc/ranks_neumf.hip ----
+ * The reference ranks NeuMF with HR@k over 1 + 100 sampled items (trainers/topKmetrics.py:74-99) and lists at most the top of
+ * predictForUser (src/models/NeuMFModel.py:133-150); these entries give the exact rank of every positive among ALL candidates over the
+ * same probabilities, without the U x I matrix.  Operands, score and limits as brNeumfCatalogAuc (pu, pit, tower, act; 2*dim <= 256,
+ * n1, n2 <= 128, n3 <= 32, 1 <= n_items < 2^31, ld_u >= n1 + dim, ld_i >= n_items): a pair's probability is bit for bit the one
+ * brNeumfCatalogAuc / brNeumfCatalogTopK dump.  BR_ERR_ARG / BR_ERR_WORKSPACE before any launch; n_users == 0 is BR_OK; no allocation
+ * and no sync inside.
+ * brNeumfCatalogRanks: NeuMFModel.py:133-150 over every pair, then the counts of brDotCatalogRanks, whose contract this is: truth_off
+ *   (n_users + 1) / truth_idx: the CSR of brNeumfCatalogAuc, n_truth = truth_off[n_users] entries; excl_off / excl_idx (optional, both
+ *   or neither): the exclusion CSR of brNeumfCatalogTopK.  Per truth entry e = (u, p), in truth-CSR order, over the candidates i != p
+ *   that are not excluded for u:
+ *     out_above[e] = #{i: prob(u, i) > prob(u, p)},  out_tied[e] = #{i: prob(u, i) == prob(u, p)}.
+ *   The user's other positives are candidates; a position in both CSRs is ranked against the non-excluded others (and is no candidate
+ *   for them); a NaN positive, or a position outside [0, n_items), gets (-1, -1); a NaN candidate is never above and never tied.  All
+ *   counting is in integers (integer atomics only): the result does not depend on the split plan, the user order or the order of
+ *   arrival.  dump_probs (optional, n_users x n_items): every pair's probability (tests).  Limits: those of brNeumfCatalogAuc and
+ *   n_truth + n_users < 2^31.  ws: brNeumfCatalogRanksWorkspaceBytes(n_users, n_items, n_truth) bytes (the positives' raw and sorted
+ *   scores, two int32 bins per truth entry and user, the sort's scratch); -1 for sizes outside the limits.  brRankMetrics turns the
+ *   integers into MRR, NDCG@k, recall@k and hit@k.
+ * brNeumfRankCount: the catalogue pass of brNeumfCatalogRanks alone, over the candidates one owner holds (parallel.py ranks_at_owners):
+ *   (skip_off, skip_idx): per user the owner's truth and excluded positions in ONE ascending list of LOCAL positions, skipped; list_off /
+ *   sorted / pcnt / cap of brAucSortPieces: the user's FULL list of n = pcnt[u] positives.  Every other valid score s adds 1 to the
+ *   user's bin #{v < s} when v_0 <= s <= v_{n-1} (and to the tie bin of the same index when v_lo == s), to bin n when s > v_{n-1}, and
+ *   nothing below v_0 or when NaN.  bins / ties: int32 [cap + n_users] each, user u's n + 1 bins from list_off[u] + u on; the call ADDS
+ *   into them and does not zero them.  Limits: cap + n_users < 2^31.  dump_probs (optional, n_users x n_items).  No workspace.
+ * brRankBinsExcluded / brRankBinsFinalize: the two model-independent kernels around the pass, with two CSRs in two roles: the entry CSR
+ *   (entry_off (n_users + 1), entry_idx) indexes raw, above and tied: the truth entries ranked by this call, positions in the space of
+ *   the exclusion CSR (excl_off, excl_idx) beside it (LOCAL ones at an owner: brCsrSplitByOwner of both); the list CSR list_off indexes
+ *   sorted, pcnt and the bins as in brNeumfRankCount.  raw[e]: the score of entry e (brNeumfAucPositives, brDotAucOwnerPositives).
+ *   brRankBinsExcluded: an entry that is also excluded is no candidate of the user's positives: -1 in its bin and its tie bin (an
+ *   exclusion CSR is required).  brRankBinsFinalize: per user the suffix sums S over the bins IN PLACE (so once per copy of the bins),
+ *   then with lo = #{v < raw[e]}, hi = #{v <= raw[e]}: above[e] = S[hi] + (n - hi), tied[e] = T[lo] + (hi - lo) - 1, without the - 1 for
+ *   an entry that is itself excluded (excl_off / excl_idx optional, both or neither).  A NaN entry, and every entry of a user whose
+ *   list is empty or lies outside cap, is left as it is (the caller presets -1). */
+int64_t brNeumfCatalogRanksWorkspaceBytes(int64_t n_users, int64_t n_items, int64_t n_truth);
+int brNeumfCatalogRanks(const float* pu, int64_t ld_u, int64_t n_users, const float* pit, int64_t ld_i, int64_t n_items, int dim, int n1,
+                        int n2, int n3, int act, const float* tower, const int64_t* truth_off, const int32_t* truth_idx, int64_t n_truth,
+                        const int64_t* excl_off, const int32_t* excl_idx, int32_t* out_above, int32_t* out_tied, float* dump_probs, void* ws,
+                        int64_t ws_bytes, brStream stream);
+int brNeumfRankCount(const float* pu, int64_t ld_u, int64_t n_users, const float* pit, int64_t ld_i, int64_t n_items, int dim, int n1, int n2,
+                     int n3, int act, const float* tower, const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off,
+                     const float* sorted, const int32_t* pcnt, int64_t cap, int32_t* bins, int32_t* ties, float* dump_probs, brStream stream);
+int brRankBinsExcluded(const int64_t* entry_off, const int32_t* entry_idx, const int64_t* excl_off, const int32_t* excl_idx, const float* raw,
+                       const int64_t* list_off, const float* sorted, const int32_t* pcnt, int64_t cap, int64_t n_users, int32_t* bins,
+                       int32_t* ties, brStream stream);
+int brRankBinsFinalize(const int64_t* entry_off, const int32_t* entry_idx, const int64_t* excl_off, const int32_t* excl_idx, const float* raw,
+                       const int64_t* list_off, const float* sorted, const int32_t* pcnt, int64_t cap, int64_t n_users, int32_t* bins,
+                       const int32_t* ties, int32_t* above, int32_t* tied, brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the
