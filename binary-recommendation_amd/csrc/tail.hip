@@ -19,10 +19,8 @@
 
 namespace br {
 
-constexpr int kTailRows = 128;      // rows per workgroup
+constexpr int kTailRows = 128;      // rows per workgroup (= rows per slab)
 constexpr int kTailLpr = 4;         // lanes per row: lane q owns the 8-column chunks q, q+4, q+8, q+12 of its row
-constexpr int kTailThreads = kTailRows * kTailLpr;
-constexpr int kTailWaves = kTailThreads / 64;
 constexpr int kTailRep = BR_STAT_REPLICAS;
 
 struct TailArgs {
@@ -39,43 +37,50 @@ struct TailArgs {
   float* slabs;
 };
 
-// N3P: n3 rounded up to a multiple of 4 (register arrays and the LDS images of W3 / dz3 use it)
-template <int N3P>
-__global__ __launch_bounds__(kTailThreads) void neumf_tail_kernel(TailArgs a) {
+// N3P: n3 rounded up to a multiple of 4 (register arrays and the LDS images of W3 / dz3 use it).
+// ROWS: rows of one LDS tile.  128 = the workgroup's rows in one pass; where two 128-row tiles of n2 columns do not fit the LDS
+// (tail_lds_bytes), 64: a 256-thread workgroup walks its 128 rows in two passes and adds the second pass into its slab.
+template <int N3P, int ROWS>
+__global__ __launch_bounds__(ROWS * kTailLpr) void neumf_tail_kernel(TailArgs a) {
+  constexpr int kTailThreads = ROWS * kTailLpr, kTailWaves = kTailThreads / 64, kPasses = kTailRows / ROWS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int n2 = a.n2, n3 = a.n3, ld = n2 | 1;             // odd row stride
-  float* A = smem;                                          // [128][ld]  raw a2, later gh2
-  float* X = A + kTailRows * ld;                            // [128][ld]  T(a2), later gh2 * xhat
-  float* Ws = X + kTailRows * ld;                           // [n2][N3P]  W3 (zero padded columns)
-  float* DZ = Ws + n2 * N3P;                                // [128][N3P + 1]
-  float* cst = DZ + kTailRows * (N3P + 1);                  // [scale | shift | mean | rstd] (n2 each)
+  float* A = smem;                                          // [ROWS][ld]  raw a2, later gh2
+  float* X = A + ROWS * ld;                                 // [ROWS][ld]  T(a2), later gh2 * xhat
+  float* Ws = X + ROWS * ld;                                // [n2][N3P]  W3 (zero padded columns)
+  float* DZ = Ws + n2 * N3P;                                // [ROWS][N3P + 1]
+  float* cst = DZ + ROWS * (N3P + 1);                       // [scale | shift | mean | rstd] (n2 each)
   float* hw = cst + 4 * n2;                                 // [b3 (N3P) | w4 for a3 (N3P)]
-  float* A3s = hw + 2 * N3P;                                // [128][N3P + 1]  a3 on its way out (coalesced store)
+  float* A3s = hw + 2 * N3P;                                // [ROWS][N3P + 1]  a3 on its way out (coalesced store)
   __shared__ float redf[kTailWaves][N3P + 2];
   __shared__ double redd[kTailWaves][BR_METRIC_SUMS];
   __shared__ double colred[2][128];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int r = t >> 2, q = t & 3;
-  const int64_t base = (int64_t)blockIdx.x * kTailRows;
-  const int nrow = (int)((a.batch - base) < kTailRows ? (a.batch - base) : kTailRows);
   const int moff = a.mf_first ? 1 : 0;
+  const float wdot = a.w4[a.mf_first ? 0 : n3], bias4 = a.b4[0];
+  const int64_t base0 = (int64_t)blockIdx.x * kTailRows;    // (a row of the batch: the grid is ceil(batch / 128))
+#pragma unroll 1
+  for (int pass = 0; pass < kPasses; ++pass) {
+  const int64_t base = base0 + (int64_t)pass * ROWS;
+  const int64_t left = a.batch - base;
+  const int nrow = (int)(left < ROWS ? (left > 0 ? left : 0) : ROWS);
   // per-row scalars of the head: requested before the staging barrier, used long after it
   const bool live = r < nrow;
   const int64_t gr = base + r;
   const float d = live ? a.dot[gr] : 0.f, yv = live ? a.labels[gr] : 0.f;
-  const float wdot = a.w4[a.mf_first ? 0 : n3], bias4 = a.b4[0];
 
   // ---- stage: a2 tile (coalesced), W3, per-column constants ----
   // (rows past the batch are zero-filled: they flow through the arithmetic below with dz = 0)
   {
     // a wave per row (no index division, 4*n2-byte runs); all 16 rows of a wave are loaded before the first
     // LDS write - a rolled load -> write loop costs one memory round trip per row
-    constexpr int RPW = kTailRows / kTailWaves;
+    constexpr int RPW = ROWS / kTailWaves;
     float v[RPW][2];
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
       const int rr = wave + kTailWaves * i;
-      const float* src = a.a2 + (base + (rr < nrow ? rr : 0)) * a.lda2;
+      const float* src = a.a2 + (rr < nrow ? base + rr : base0) * a.lda2;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int k = lane + 64 * h;
@@ -93,11 +98,13 @@ __global__ __launch_bounds__(kTailThreads) void neumf_tail_kernel(TailArgs a) {
       }
     }
   }
-  for (int e = t; e < n2 * N3P; e += kTailThreads) { const int k = e / N3P, n = e - k * N3P; Ws[e] = n < n3 ? a.W3[k * n3 + n] : 0.f; }
-  for (int k = t; k < n2; k += kTailThreads) {
-    cst[k] = a.scale2[k]; cst[n2 + k] = a.shift2[k]; cst[2 * n2 + k] = a.mean2[k]; cst[3 * n2 + k] = a.rstd2[k];
+  if (pass == 0) {
+    for (int e = t; e < n2 * N3P; e += kTailThreads) { const int k = e / N3P, n = e - k * N3P; Ws[e] = n < n3 ? a.W3[k * n3 + n] : 0.f; }
+    for (int k = t; k < n2; k += kTailThreads) {
+      cst[k] = a.scale2[k]; cst[n2 + k] = a.shift2[k]; cst[2 * n2 + k] = a.mean2[k]; cst[3 * n2 + k] = a.rstd2[k];
+    }
+    for (int n = t; n < N3P; n += kTailThreads) { hw[n] = n < n3 ? a.b3[n] : 0.f; hw[N3P + n] = n < n3 ? a.w4[moff + n] : 0.f; }
   }
-  for (int n = t; n < N3P; n += kTailThreads) { hw[n] = n < n3 ? a.b3[n] : 0.f; hw[N3P + n] = n < n3 ? a.w4[moff + n] : 0.f; }
   for (int k = t; k < 256; k += kTailThreads) (&colred[0][0])[k] = 0.0;
   __syncthreads();
 
@@ -194,20 +201,21 @@ __global__ __launch_bounds__(kTailThreads) void neumf_tail_kernel(TailArgs a) {
   for (int o = t; o < n2 * n3; o += kTailThreads) {
     const int k = o / n3, n = o - k * n3;
     float acc = 0.f;
-    for (int rr = 0; rr < kTailRows; ++rr) acc += X[rr * ld + k] * DZ[rr * (N3P + 1) + n];   // dead rows hold dz = 0
-    slab[o] = acc;
+    for (int rr = 0; rr < ROWS; ++rr) acc += X[rr * ld + k] * DZ[rr * (N3P + 1) + n];   // dead rows hold dz = 0
+    slab[o] = pass ? slab[o] + acc : acc;
   }
   if (a.a3)      // rows of the tile are contiguous in a3 (row stride n3)
     for (int e = t; e < nrow * n3; e += kTailThreads) { const int rr = e / n3; a.a3[base * n3 + e] = A3s[rr * (N3P + 1) + (e - rr * n3)]; }
+  auto put = [&](int i, float v) { slab[i] = pass ? slab[i] + v : v; };      // (a slab element belongs to one thread in every pass)
   auto wsum = [&](int i) { float v = 0.f; for (int w = 0; w < kTailWaves; ++w) v += redf[w][i]; return v; };
   if (t < n3) {
     float acc = 0.f;
-    for (int rr = 0; rr < kTailRows; ++rr) acc += DZ[rr * (N3P + 1) + t];
-    slab[n2 * n3 + t] = acc;
-    slab[n2 * n3 + n3 + moff + t] = wsum(t);
+    for (int rr = 0; rr < ROWS; ++rr) acc += DZ[rr * (N3P + 1) + t];
+    put(n2 * n3 + t, acc);
+    put(n2 * n3 + n3 + moff + t, wsum(t));
   }
-  if (t == 64) slab[n2 * n3 + n3 + (a.mf_first ? 0 : n3)] = wsum(N3P);
-  if (t == 65) slab[n2 * n3 + 2 * n3 + 1] = wsum(N3P + 1);
+  if (t == 64) put(n2 * n3 + n3 + (a.mf_first ? 0 : n3), wsum(N3P));
+  if (t == 65) put(n2 * n3 + 2 * n3 + 1, wsum(N3P + 1));
   if (t >= 96 && t < 96 + BR_METRIC_SUMS && a.msums) {
     double v = 0.0;
     for (int w = 0; w < kTailWaves; ++w) v += redd[w][t - 96];
@@ -243,7 +251,7 @@ __global__ __launch_bounds__(kTailThreads) void neumf_tail_kernel(TailArgs a) {
     for (int idx = t; idx < 4 * n2; idx += kTailThreads) {
       const int part = idx / n2, k = idx - part * n2;
       float s1 = 0.f, s2 = 0.f;
-      for (int rr = part * (kTailRows / 4); rr < (part + 1) * (kTailRows / 4); ++rr) { s1 += A[rr * ld + k]; s2 += X[rr * ld + k]; }
+      for (int rr = part * (ROWS / 4); rr < (part + 1) * (ROWS / 4); ++rr) { s1 += A[rr * ld + k]; s2 += X[rr * ld + k]; }
       atomicAdd(&colred[0][k], (double)s1);
       atomicAdd(&colred[1][k], (double)s2);
     }
@@ -260,12 +268,27 @@ __global__ __launch_bounds__(kTailThreads) void neumf_tail_kernel(TailArgs a) {
       atomicAdd(rep + n2 + k, colred[1][k]);
     }
   }
+  if (kPasses > 1) __syncthreads();                          // the next pass restages every tile and zeroes colred
+  }  // pass
 }
 
-static size_t tail_lds_bytes(int n2, int n3p) {
+static size_t tail_lds_bytes(int n2, int n3p, int rows) {
   const int ld = n2 | 1;
-  return sizeof(float) * ((size_t)2 * kTailRows * ld + (size_t)n2 * n3p + (size_t)2 * kTailRows * (n3p + 1) + 4 * (size_t)n2 + 2 * (size_t)n3p);
+  return sizeof(float) * ((size_t)2 * rows * ld + (size_t)n2 * n3p + (size_t)2 * rows * (n3p + 1) + 4 * (size_t)n2 + 2 * (size_t)n3p);
 }
+// the kernel's __shared__ arrays (redf, redd, colred)
+static size_t tail_static_lds_bytes(int n3p, int rows) {
+  const int waves = rows * kTailLpr / 64;
+  return sizeof(float) * waves * (n3p + 2) + sizeof(double) * (waves * BR_METRIC_SUMS + 2 * 128);
+}
+constexpr size_t kTailDynLdsMax = 150 * 1024;     // the dynamic-LDS ceiling requested for the kernel (hipFuncSetAttribute)
+constexpr size_t kTailCuLds = 160 * 1024;         // LDS of a gfx950 CU: dynamic + static of the one workgroup
+static bool tail_fits(int n2, int n3p, int rows) {
+  const size_t dyn = tail_lds_bytes(n2, n3p, rows);
+  return dyn <= kTailDynLdsMax && dyn + tail_static_lds_bytes(n3p, rows) <= kTailCuLds;
+}
+// rows per LDS tile of the VALU form: the workgroup's 128 where they fit (n2 = 128 up to n3 = 8, n3 = 32 up to n2 = 101), else 64
+static int tail_tile_rows(int n2, int n3p) { return tail_fits(n2, n3p, kTailRows) ? kTailRows : kTailRows / 2; }
 
 }  // namespace br
 
@@ -290,6 +313,13 @@ extern "C" int brNeumfTailFused(const float* a2, int64_t lda2, const float* W3, 
   BR_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "brNeumfTailFused: drop_p out of [0,1)");
   BR_CHECK_ARG((drop_p > 0.f) == (keep != nullptr), "brNeumfTailFused: keep bits (brDropoutKeepBits) are required exactly when drop_p > 0");
   BR_CHECK_ARG(loss == BR_LOSS_BCE || loss == BR_LOSS_MSE, "brNeumfTailFused: bad loss");
+  const int n3p = (n3 + 3) & ~3, tile_rows = tail_tile_rows(n2, n3p);
+  if (!tail_fits(n2, n3p, tile_rows)) {      // before any launch (every n2 <= 128, n3 <= 32 fits a 64-row tile: kept as the guard of that arithmetic)
+    set_error("brNeumfTailFused: n2 = %d with n3 = %d needs %zu B of dynamic LDS (+ %zu B static) for %d-row tiles, above the %zu B a workgroup may "
+              "request; the largest supported combination is n2 = 128 with n3 = 32",
+              n2, n3, tail_lds_bytes(n2, n3p, tile_rows), tail_static_lds_bytes(n3p, tile_rows), tile_rows, kTailDynLdsMax);
+    return BR_ERR_UNSUPPORTED;
+  }
   if (batch == 0) return BR_OK;
   BR_CHECK_ARG(n_slabs == brNeumfTailSlabs(batch), "brNeumfTailFused: n_slabs must be brNeumfTailSlabs(batch)");
   hipStream_t s = (hipStream_t)stream;
@@ -325,20 +355,28 @@ extern "C" int brNeumfTailFused(const float* a2, int64_t lda2, const float* W3, 
   a.batch = batch; a.n2 = n2; a.n3 = n3; a.act = act; a.mf_first = mf_first; a.loss = loss; a.inv_batch = inv_batch;
   a.a3 = a3; a.logit = logit; a.prob = prob; a.ddot = ddot; a.gh2 = gh2; a.ldgh2 = ldgh2; a.msums = sums; a.bn_sums = bn_sums;
   a.slabs = slabs;
-  const int n3p = (n3 + 3) & ~3;
-  const size_t lds = tail_lds_bytes(n2, n3p);
+  const size_t lds = tail_lds_bytes(n2, n3p, tile_rows);
   const unsigned grid = (unsigned)n_slabs;
-#define BR_TAIL(NP)                                                                                                       \
-  case NP: {                                                                                                              \
+#define BR_TAIL_LAUNCH(NP, ROWS)                                                                                          \
+  {                                                                                                                       \
     static bool attr = false;                                                                                             \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)neumf_tail_kernel<NP>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = true; } \
-    neumf_tail_kernel<NP><<<grid, kTailThreads, lds, s>>>(a);                                                                \
-  } break;
+    if (!attr) {                                                                                                          \
+      const hipError_t e = hipFuncSetAttribute((const void*)neumf_tail_kernel<NP, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailDynLdsMax); \
+      if (e != hipSuccess) { set_error("brNeumfTailFused: cannot raise the dynamic LDS limit to %zu B: %s", kTailDynLdsMax, hipGetErrorString(e)); return BR_ERR_HIP; } \
+      attr = true;                                                                                                        \
+    }                                                                                                                     \
+    neumf_tail_kernel<NP, ROWS><<<grid, ROWS * kTailLpr, lds, s>>>(a);                                                     \
+  }
+  // (N3P = 4 and 8 fit 128-row tiles at every n2: no 64-row instances of them)
+#define BR_TAIL(NP) case NP: BR_TAIL_LAUNCH(NP, kTailRows) break;
+#define BR_TAIL2(NP) case NP: if (tile_rows == kTailRows) BR_TAIL_LAUNCH(NP, kTailRows) else BR_TAIL_LAUNCH(NP, kTailRows / 2) break;
   switch (n3p) {
-    BR_TAIL(4) BR_TAIL(8) BR_TAIL(12) BR_TAIL(16) BR_TAIL(20) BR_TAIL(24) BR_TAIL(28) BR_TAIL(32)
+    BR_TAIL(4) BR_TAIL(8) BR_TAIL2(12) BR_TAIL2(16) BR_TAIL2(20) BR_TAIL2(24) BR_TAIL2(28) BR_TAIL2(32)
     default: set_error("brNeumfTailFused: unsupported n3"); return BR_ERR_UNSUPPORTED;
   }
 #undef BR_TAIL
+#undef BR_TAIL2
+#undef BR_TAIL_LAUNCH
   BR_CHECK_LAUNCH("brNeumfTailFused");
   return BR_OK;
 }

@@ -523,6 +523,48 @@ def neumf_head(a3, dot, labels, w4, b4, mf_first, loss, inv_batch, logit=None, p
                                   _stream()), "brNeumfHead")
 
 
+def neumf_tail_slabs(batch) -> int:
+    return int(_lib.load().brNeumfTailSlabs(batch))
+
+
+def neumf_tail_slab_elems(n2, n3) -> int:
+    return int(_lib.load().brNeumfTailSlabElems(n2, n3))
+
+
+_BN_FOLD = None
+
+
+def _bn_fold(stats, batch_total, gamma, beta, eps, momentum, moving_mean, moving_var, scale, shift, mean, rstd):
+    """brBnFold (include/binrec.h) from tensors, field order as in the header."""
+    global _BN_FOLD
+    if _BN_FOLD is None:
+        _BN_FOLD = type("brBnFold", (ctypes.Structure,), {"_fields_": _lib.parse_struct("brBnFold")})
+    return _BN_FOLD(stats.data_ptr(), float(batch_total), gamma.data_ptr(), beta.data_ptr(), float(eps), float(momentum), _p(moving_mean) or None,
+                    _p(moving_var) or None, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+
+
+def neumf_tail_fused(a2, W3, b3, w4, b4, dot, labels, act, mf_first, loss, inv_batch, logit, prob, ddot, gh2, scale2=None, shift2=None,
+                     mean2=None, rstd2=None, bn2=None, drop_p=0.0, keep=None, a3=None, sums=None, bn_sums=None, slabs=None, batch=None):
+    """brNeumfTailFused.  a2 / gh2: (B, n2) views whose row strides go in as lda2 / ldgh2.  BatchNorm 2 either as the four vectors
+    scale2/shift2/mean2/rstd2 or as bn2 = (stats, batch_total, gamma, beta, eps, momentum, moving_mean, moving_var, scale, shift, mean,
+    rstd) (the fields of brBnFold; the moving statistics may both be None).  keep: the bit plane of dropout site 2 (dropout_keep_bits),
+    exactly when drop_p > 0.  slabs=None allocates brNeumfTailSlabs(B) x brNeumfTailSlabElems(n2, n3) floats.
+    -> (slabs, n_slabs), to be reduced by reduce_slabs into [dW3 | db3 | dW4 | db4]."""
+    B = dot.shape[0] if batch is None else batch
+    n2, n3 = W3.shape
+    n_slabs = neumf_tail_slabs(B)
+    if slabs is None:
+        slabs = torch.empty(n_slabs * neumf_tail_slab_elems(n2, n3), dtype=torch.float32, device=dot.device)
+    fold = _bn_fold(*bn2) if bn2 is not None else None
+    check(_lib.load().brNeumfTailFused(a2.data_ptr(), a2.stride(0), _f32(W3, "W3").data_ptr(), b3.data_ptr(), w4.data_ptr(), b4.data_ptr(),
+                                       dot.data_ptr(), labels.data_ptr(), _p(scale2), _p(shift2), _p(mean2), _p(rstd2),
+                                       ctypes.byref(fold) if fold is not None else None, float(drop_p), _p(keep) if drop_p > 0 else 0, B, n2, n3,
+                                       ACT[act], int(mf_first), LOSS[loss], float(inv_batch), _p(a3), logit.data_ptr(), prob.data_ptr(), _p(sums),
+                                       ddot.data_ptr(), gh2.data_ptr(), gh2.stride(0), _p(bn_sums), slabs.data_ptr(), n_slabs, _stream()),
+          "brNeumfTailFused")
+    return slabs, n_slabs
+
+
 def bce_logits(z, y, inv_batch, prob=None, dz=None, sums=None):
     check(_lib.load().brBceLogits(z.data_ptr(), y.data_ptr(), z.shape[0], float(inv_batch), _p(prob), _p(dz), _p(sums),
                                   _stream()), "brBceLogits")

@@ -340,8 +340,15 @@ int brDenseFinalize(const float* const* slabs, const int* n_slabs, const int64_t
  * backward of all of it, one launch (trainers/NFC_plain.py:143-155, src/models/NeuMFModel.py:75-93) ----
  * Same results as brDenseForward(layer 3) + brNeumfHead + brDenseBackward(layer 3) (fp32 sums in a different
  * order).  a2: (B x n2) raw output of layer 2; scale2/shift2/mean2/rstd2 from brBnFinalize, or all NULL with bn2 given
- * (BatchNorm 2 finalized inside this launch, brBnFold); n2 <= 64, n3 <= 16 and 16-B aligned rows run on MFMA (csrc/tail_mfma.hip); keep: the bit plane of
- * the dropout in front of layer 3 (brDropoutKeepBits; NULL with drop_p == 0).
+ * (BatchNorm 2 finalized inside this launch, brBnFold); keep: the bit plane of the dropout in front of layer 3
+ * (brDropoutKeepBits; NULL with drop_p == 0).
+ * Two forms.  n2 <= 64, n3 <= 16, lda2 % 4 == ldgh2 % 4 == 0 and 16-B aligned a2 / gh2 run on MFMA (csrc/tail_mfma.hip).  That form
+ * loads a2 in 16-B pieces, so it reads the columns n2 .. lda2-1 of every row and multiplies them by a zero scale: they must hold
+ * FINITE values (Inf or NaN there would turn z3 into NaN); it also stores zeros into the same columns of gh2.  Every other shape
+ * runs on VALU through LDS tiles (csrc/tail.hip), for every n2 <= 128 and n3 <= 32 (BR_ERR_ARG beyond).  With N3P = n3 rounded up to
+ * a multiple of 4, a workgroup's 128 rows are one tile where 4*(2*128*(n2|1) + n2*N3P + 2*128*(N3P+1) + 4*n2 + 2*N3P) bytes of dynamic
+ * LDS stay within 150 KiB (n2 = 128 up to n3 = 8, n3 = 32 up to n2 = 101, n3 <= 16 up to n2 = 123); wider towers run the same rows as
+ * two 64-row tiles.  A size the LDS could not hold is BR_ERR_UNSUPPORTED before any launch.
  * Outputs: a3 (B x n3, may be NULL), logit/prob/ddot (B), gh2 (B x n2) = gradient w.r.t. BN2's output,
  * bn_sums (double[BR_STAT_REPLICAS][2*n2]) += (sum gh2, sum gh2*xhat2), sums as brNeumfHead, and one slab per
  * workgroup [dW3 (n2*n3) | db3 (n3) | dW4 (n3+1, concat order) | db4]: n_slabs = brNeumfTailSlabs(batch),

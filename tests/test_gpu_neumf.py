@@ -54,7 +54,18 @@ def _masks(cfg, spec, step, B, row0=0):
 @pytest.mark.parametrize("variant,dim,B", [("A", 64, 300), ("B", 64, 257), ("A", 10, 64), ("B", 32, 7), ("A", 8, 1000), ("A", 10, 2048),
                                            ("A", 128, 300), ("B", 100, 129)])      # 2*dim > 128: the first layer runs as two K-halves (config 5)
 def test_forward_backward_parity(dev, variant, dim, B):
-    ops, eng, spec, cfg, p, u, i, y = _setup(variant, dim, B, dev)
+    _forward_backward_parity(dev, variant, dim, B)
+
+
+@pytest.mark.parametrize("variant,dim,hidden,B", [("B", 32, (64, 96, 20), 300), ("A", 16, (100, 128, 8), 257), ("A", 16, (64, 128, 16), 300)])
+def test_forward_backward_parity_wide_tail(dev, variant, dim, hidden, B):
+    """towers whose last two layers are wider than 64 x 16: the fused tail runs its VALU form (csrc/tail.hip), at n2 = 128 with the
+    largest n3 its 128-row LDS tiles hold and, at 128 x 16, as two 64-row passes; the same assertions as test_forward_backward_parity."""
+    _forward_backward_parity(dev, variant, dim, B, hidden=hidden)
+
+
+def _forward_backward_parity(dev, variant, dim, B, hidden=None):
+    ops, eng, spec, cfg, p, u, i, y = _setup(variant, dim, B, dev, hidden=hidden)
     td = lambda a, dt: torch.from_numpy(a).to(dev).to(dt)
     eng.train_step(td(u, torch.int32), td(i, torch.int32), td(y, torch.float32))
     torch.cuda.synchronize()
