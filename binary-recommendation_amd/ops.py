@@ -510,6 +510,13 @@ def bn_param_grads(bn_sums, dgamma, dbeta):
           "brBnParamGrads")
 
 
+def bn_param_grads_pair(bn_sums_a, dgamma_a, dbeta_a, bn_sums_b, dgamma_b, dbeta_b):
+    """bn_param_grads of two BatchNorms (the two of a tower) in one launch."""
+    check(_lib.load().brBnParamGradsPair(bn_sums_a.data_ptr(), dgamma_a.data_ptr(), dbeta_a.data_ptr(), dgamma_a.numel(),
+                                         bn_sums_b.data_ptr(), dgamma_b.data_ptr(), dbeta_b.data_ptr(), dgamma_b.numel(), _stream()),
+          "brBnParamGradsPair")
+
+
 def head_slabs(batch) -> int:
     return int(_lib.load().brHeadSlabs(batch))
 
