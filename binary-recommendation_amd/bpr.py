@@ -231,8 +231,8 @@ class BPREngine(RowAdam):
         catalogue and without the U x I matrix (ops.dot_catalog_ranks, csrc/ranks_dot.hip; rows up to 512 features).  truth / items as
         in full_auc; exclude: (off, idx) CSR over `users` of candidate POSITIONS never offered (topk_metrics.seen_csr): an excluded
         truth entry is still ranked, against the others.  -> (above, tied) int32 on the device, (-1, -1) for a positive whose score is
-        NaN.  Ids outside the tables set self.err (check_ids raises).  On the row-sharded engine this is a collective through the
-        gathered rows (every rank calls it and gets the counts of ITS users)."""
+        NaN.  Ids outside the tables set self.err (check_ids raises).  On the row-sharded engine this is a collective (every rank
+        calls it and gets the counts of ITS users), through the gathered rows or counted at the item owners (parallel.py: catalog=)."""
         q, c = self._catalog_rows(users, items)
         return ops.dot_catalog_ranks(q, c, truth[0], truth[1], exclude=exclude, dump_scores=dump_scores)
 

@@ -526,21 +526,29 @@ class BPRModel(RModel):
         ap, _ = ops.map_at_k(ti, off, idx, want_hits=False)
         return float((ap.double().cpu().numpy() * _ap_scale(gt, col, k)).mean())
 
-    def rank_metrics(self, ground_truth, items, ks=(10,), excludeSeen=False) -> dict:
+    def rank_metrics(self, ground_truth, items, ks=(10,), excludeSeen=False, catalog=None) -> dict:
         """MRR and, per cutoff k of ks (at most 8), NDCG@k, recall@k and hit rate@k over all `items`, from the exact rank of every true
         item among them (BPREngine.rank_metrics: one fused pass, no users x items matrix, no limit on the rank): the means over the
         users that have positives, as Python floats {"mrr", "ndcg@k", "recall@k", "hr@k"}.  ground_truth: iterable of (user_id, [true
         item ids]); a true item outside `items` raises, as in full_auc.  excludeSeen: the products a customer has in the training
         split are no candidates (a true item among them is still ranked, against the others).  The rank is pessimistic: r = 1 + the
         candidates scoring above + those scoring EQUAL, so a model that scores everything equal earns nothing.  On a row-sharded
-        engine this is a collective through the gathered rows."""
+        engine (a model compiled under a process group) this is a collective; catalog as in full_auc: "gather" pulls the candidate
+        rows to every rank, "owners" counts where they live (ShardedBPREngine.catalog_ranks) - the same values; None: the engine's
+        default."""
         from .topk_metrics import seen_csr
+        if catalog not in (None, "gather", "owners"):
+            raise ValueError(f"catalog must be None, 'gather' or 'owners', got {catalog!r}")
+        sharded = hasattr(self.model, "ctx")
+        if catalog == "owners" and not sharded:
+            raise ValueError("catalog='owners' needs a row-sharded engine (a model compiled under a process group)")
         gt, _col, truth = _truth_of(ground_truth, items, lambda: self.model.device, strict=True)
         e = self.model
         users = [u for u, _ in gt]
         ex = seen_csr(users, list(items), self.trainDf.CUSTOMER_ID.tolist(), self.trainDf.PRODUCT_ID.tolist(), e.device) if excludeSeen else None
         res = e.rank_metrics(_to_dev(np.asarray(users), e.device, e.id_dtype), truth, ks=ks,
-                             items=_to_dev(np.asarray(items), e.device, e.id_dtype), exclude=ex)
+                             items=_to_dev(np.asarray(items), e.device, e.id_dtype), exclude=ex,
+                             **({"catalog": catalog} if sharded and catalog else {}))
         e.check_ids()
         return _mean_over_users_with_positives(res)
 
@@ -707,7 +715,8 @@ class TwoTowerModel:
         items matrix): the means over the users that have positives, as Python floats {"mrr", "ndcg@k", "recall@k", "hr@k"}.
         positives: iterable of (user, item) pairs as topKMetrics takes them (pairs outside the two lists are ignored); exclude: (off,
         idx) CSR over usersId of candidate positions never offered (topk_metrics.seen_csr).  The rank is pessimistic: r = 1 + the
-        candidates scoring above + those scoring EQUAL, so a model that scores everything equal earns nothing."""
+        candidates scoring above + those scoring EQUAL, so a model that scores everything equal earns nothing.  Under a process group
+        this is a collective: the ranks are counted where the item rows live (ShardedTwoTowerEngine.catalog_ranks), the same values."""
         from .topk_metrics import seen_csr
         pairs = list(positives)
         truth = seen_csr(list(usersId), list(itemsId), [u for u, _i in pairs], [i for _u, i in pairs], self.device)

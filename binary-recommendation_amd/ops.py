@@ -1210,6 +1210,24 @@ def neumf_rank_count(pu, pit, tower, dim: int, hidden, act: str, skip_off, skip_
     return dump
 
 
+def dot_rank_count(Q, C, skip_off, skip_idx, list_off, sorted_, pcnt, bins, ties, dump_scores=False, force_wide=False):
+    """The catalogue pass of dot_catalog_ranks over the candidates one owner holds.  Q (U x dim), C (I_loc x dim): this owner's candidate
+    rows; (skip_off, skip_idx): per user the owner's truth and excluded positions in one ascending list of LOCAL positions; list_off /
+    sorted_ / pcnt of auc_sort_pieces: every user's FULL list; bins / ties of rank_bins: the call ADDS this owner's counts into them
+    (user u's n + 1 bins from list_off[u] + u on); force_wide as in dot_catalog_ranks -> None [every pair's score (U, I_loc)]
+    (brDotRankCount)."""
+    U, I, dim, ld_q, ld_c, dev = _dot_catalog_args("dot_rank_count", Q, C, None, DOT_WIDE_MAX_DIM)
+    off, idx = _csr((skip_off, skip_idx), U, "skip")
+    cap = _rank_bins_args("dot_rank_count", U, list_off, sorted_, pcnt, bins, ties)
+    dump = torch.empty(U, I, dtype=torch.float32, device=dev) if dump_scores else None
+    if U == 0:                     # no user, nothing to add (and no valid pointer for Q)
+        return dump
+    check(_lib.load().brDotRankCount(Q.data_ptr(), ld_q, U, C.data_ptr(), ld_c, I, dim, off.data_ptr(), idx.data_ptr(), list_off.data_ptr(),
+                                     sorted_.data_ptr(), pcnt.data_ptr(), cap, bins.data_ptr(), ties.data_ptr(),
+                                     _p(dump), _wide_flags(force_wide), _stream()), "brDotRankCount")
+    return dump
+
+
 def _rank_entry_args(who: str, U: int, entry_off, entry_idx, raw, exclude):
     off, idx = _csr((entry_off, entry_idx), U, "entries")
     if not isinstance(raw, torch.Tensor) or raw.dtype != torch.float32 or not raw.is_cuda or not raw.is_contiguous() or raw.dim() != 1:

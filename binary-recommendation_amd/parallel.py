@@ -567,8 +567,9 @@ def ranks_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, exclude
     ids; counts may differ and may be 0), the SAME `items` (None = every item row), the truth CSR (off, idx) over its own users in
     ascending positions of `items` and optionally an exclusion CSR of the same kind; it gets (above, tied) int32 for its own truth
     entries, in CSR order.  fetch_user_rows, queries_of and candidates_of as in recommend_at_owners; the model's two scoring phases over
-    this rank's candidates: positives(q, cand, pos_off, pos_idx, out) (ops.neumf_auc_positives) and count(q, cand, skip_off, skip_idx,
-    list_off, sorted_, pcnt, bins, ties) (ops.neumf_rank_count), which adds into the bins."""
+    this rank's candidates: positives(q, cand, pos_off, pos_idx, out) (ops.neumf_auc_positives; the dot-product models:
+    ops.dot_auc_owner_positives) and count(q, cand, skip_off, skip_idx, list_off, sorted_, pcnt, bins, ties) (ops.neumf_rank_count;
+    ops.dot_rank_count), which adds into the bins."""
     from . import ops
     W, r, dev = ctx.world, ctx.rank, users.device
     if items is None:
@@ -1027,9 +1028,26 @@ def make_sharded_two_tower(base_cls):
                 lambda loc: self._tower(ops.gather_rows([self.item_emb], [loc], err_flag=self.err)[0], "item"),
                 lambda q, c, kk, ex: ops.dot_catalog_topk(q, c, kk, exclude=ex))
 
+        def catalog_ranks(self, users, truth, items=None, exclude=None):
+            """TwoTowerEngine.catalog_ranks on the row-sharded tables (ranks_at_owners): a collective - every rank calls it with its own
+            users (any number, also none), their truth CSR (and optionally their exclusion CSR) and the same `items` (None: every row
+            of the item table), and gets the single-device integers of ITS truth entries.  Every owner applies the item tower to the
+            candidates whose rows it holds only, as recommend does, and counts them there (ops.dot_rank_count)."""
+            users = users.contiguous()
+            if items is not None:
+                items = (items if items.dtype == users.dtype else items.to(users.dtype)).contiguous()
+            return ranks_at_owners(
+                self.ctx, users, items, self.item_rows_global, truth, exclude,
+                lambda ids: gather_global_rows(self.ctx, ids, lambda loc: ops.gather_rows([self.user_emb], [loc], err_flag=self.err)[0], self.E),
+                lambda rows: self._tower(rows, "user"),
+                lambda loc: self._tower(ops.gather_rows([self.item_emb], [loc], err_flag=self.err)[0], "item"),
+                count=lambda q, c, so, si, lo, srt, pc, b, t: ops.dot_rank_count(q, c, so, si, lo, srt, pc, b, t),
+                positives=lambda q, c, po, pi, out: ops.dot_auc_owner_positives(q, c, po, pi, out=out))
+
         def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
-            raise NotImplementedError("rank_metrics on the row-sharded TwoTower engine: the exact ranks are counted on one device "
-                                      "(ops.dot_catalog_ranks); counting at the item owners is not built (DESIGN.md 7)")
+            """TwoTowerEngine.rank_metrics as a collective, from the ranks of catalog_ranks: every rank gets the floats of ITS users."""
+            above, tied = self.catalog_ranks(users, truth, items=items, exclude=exclude)
+            return ops.rank_metrics(above, tied, truth[0], ks)
 
         def _softmax(self, q, c, items, B, dq, dc):
             ctx = self.ctx
@@ -1201,6 +1219,33 @@ def make_sharded_bpr(base_cls):
             return auc_at_owners(self.ctx, users, items, self.num_items_global, truth,
                                  lambda ids: gather_global_rows(self.ctx, ids, rows_of("user"), self.dim),
                                  lambda rows: rows, rows_of("item"), self.dim)
+
+        def catalog_ranks(self, users, truth, items=None, exclude=None, dump_scores=False, catalog="gather"):
+            """BPREngine.catalog_ranks as a collective.  catalog="gather" (default): every candidate row is pulled to every rank
+            (_catalog_rows) and each rank ranks its users alone; "owners": every rank counts the users of ALL ranks against the
+            candidates whose rows it holds and the integer bins are summed (ranks_at_owners; the count: ops.dot_rank_count, the whole-row
+            kernels up to 128 features and the block kernels above, as everywhere) - the same integers entry for entry, with U x dim
+            user rows, the truth and exclusion lists, the positives' scores and two int32 bins per truth entry and user on the wire
+            instead of I x dim candidate rows per rank."""
+            if catalog not in ("gather", "owners"):
+                raise ValueError(f"catalog must be 'gather' or 'owners', got {catalog!r}")
+            if catalog == "gather":
+                return super().catalog_ranks(users, truth, items=items, exclude=exclude, dump_scores=dump_scores)
+            if dump_scores:
+                raise NotImplementedError("catalog_ranks(catalog='owners', dump_scores=True): no rank forms the scores of another owner's items")
+            users, items = self._recommend_ids(users, items)
+            self.flush()                         # deferred-Adam rows lag until then
+            rows_of = lambda name: (lambda loc: ops.gather_rows([getattr(self, "_" + name)], [loc], err_flag=self.err)[0])
+            return ranks_at_owners(self.ctx, users, items, self.num_items_global, truth, exclude,
+                                   lambda ids: gather_global_rows(self.ctx, ids, rows_of("user"), self.dim),
+                                   lambda rows: rows, rows_of("item"),
+                                   count=lambda q, c, so, si, lo, srt, pc, b, t: ops.dot_rank_count(q, c, so, si, lo, srt, pc, b, t),
+                                   positives=lambda q, c, po, pi, out: ops.dot_auc_owner_positives(q, c, po, pi, out=out))
+
+        def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None, catalog="gather"):
+            """BPREngine.rank_metrics as a collective, from the ranks of catalog_ranks(catalog=...): the same floats either way."""
+            above, tied = self.catalog_ranks(users, truth, items=items, exclude=exclude, catalog=catalog)
+            return ops.rank_metrics(above, tied, truth[0], ks)
 
         SHARDED_KEYS = ("user", "item", "user_m", "user_v", "item_m", "item_v")
 

@@ -148,16 +148,23 @@ class TwoTowerEngine:
             items = torch.arange(self.item_emb.shape[0], dtype=users.dtype, device=self.device)
         return ops.dot_catalog_topk(self.user_tower(users), self.item_tower(items), k, exclude=exclude)
 
-    def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
-        """Per-user MRR and, for every cutoff of ks (at most 8), NDCG@k, recall@k and hit rate@k of the candidates `items` (None: every row
-        of the item table) by the dot of the tower outputs, as recommend forms them, from the exact ranks of ops.dot_catalog_ranks
-        (csrc/ranks_dot.hip) without the U x I matrix.  truth: (off, idx) CSR over `users` of candidate POSITIONS, ascending
-        (ops.truth_csr); exclude: CSR of positions never offered (topk_metrics.seen_csr).  The rank of a positive is r = 1 + above +
-        tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that scores everything equal earns nothing.
-        -> {"mrr", "ndcg@k", "recall@k", "hr@k"} float32 (U,) on the device, NaN for a user without positives."""
+    def catalog_ranks(self, users, truth, items=None, exclude=None):
+        """Per truth entry, in the order of the CSR, how many of the candidates `items` (None: every row of the item table) score above it
+        and how many tie with it by the dot of the tower outputs, as recommend forms them, without the U x I matrix
+        (ops.dot_catalog_ranks, csrc/ranks_dot.hip).  truth: (off, idx) CSR over `users` of candidate POSITIONS, ascending
+        (ops.truth_csr); exclude: CSR of positions never offered (topk_metrics.seen_csr): an excluded truth entry is still ranked,
+        against the others.  -> (above, tied) int32 on the device, (-1, -1) for a positive whose score is NaN.  The row-sharded
+        engine (parallel.py) overrides this with a collective of the same contract."""
         if items is None:
             items = torch.arange(self.item_emb.shape[0], dtype=users.dtype, device=self.device)
-        above, tied = ops.dot_catalog_ranks(self.user_tower(users), self.item_tower(items), truth[0], truth[1], exclude=exclude)
+        return ops.dot_catalog_ranks(self.user_tower(users), self.item_tower(items), truth[0], truth[1], exclude=exclude)
+
+    def rank_metrics(self, users, truth, ks=(10,), items=None, exclude=None):
+        """Per-user MRR and, for every cutoff of ks (at most 8), NDCG@k, recall@k and hit rate@k of the candidates `items` (None: every row
+        of the item table), from the exact ranks of catalog_ranks.  The rank of a positive is r = 1 + above +
+        tied - pessimistic: a tied candidate is taken to outrank the positive, so a model that scores everything equal earns nothing.
+        -> {"mrr", "ndcg@k", "recall@k", "hr@k"} float32 (U,) on the device, NaN for a user without positives."""
+        above, tied = self.catalog_ranks(users, truth, items=items, exclude=exclude)
         return ops.rank_metrics(above, tied, truth[0], ks)
 
     def enable_graph(self, batch: int | None = None):

@@ -710,6 +710,27 @@ int brRankBinsFinalize(const int64_t* entry_off, const int32_t* entry_idx, const
                        const int64_t* list_off, const float* sorted, const int32_t* pcnt, int64_t cap, int64_t n_users, int32_t* bins,
                        const int32_t* ties, int32_t* above, int32_t* tied, brStream stream);
 
+/* ---- Catalogue ranks at the item owners for dot-product models (BPR, TwoTower on row-sharded engines): csrc/ranks_owner.hip ------------
+ * brDotCatalogRanks (the ranking measures over bpr_predict, src/models/bpr.py:122-133) cut into phases, so that W owners, each holding
+ * a share of the candidates, together compute what one launch over all candidates computes, integer for integer (parallel.py
+ * ranks_at_owners): brDotAucOwnerPositives and brAucSortPieces, this count, brRankBinsExcluded and brRankBinsFinalize.
+ * brDotRankCount: the catalogue pass of brDotCatalogRanks alone (bpr.py:122-133 without the U x I matrix), over the candidates C one
+ *   owner holds: the dot-product counterpart of brNeumfRankCount.  Q, C, dim and BR_DOT_FORCE_WIDE as brDotCatalogRanks: a pair's score
+ *   is bit for bit the one brDotCatalogRanks and brDotAucOwnerPositives form (v_mfma_f32_16x16x4_f32, the same padded width, one
+ *   chain from 0).  Two CSRs in two roles: (skip_off (n_users + 1), skip_idx): per user the owner's truth and excluded positions in ONE
+ *   ascending list of LOCAL positions into C, never counted; list_off / sorted / pcnt / cap of brAucSortPieces: the user's FULL list of
+ *   n = pcnt[u] positives v_0 <= ... <= v_{n-1} at sorted[list_off[u] ...] (`sorted` holds cap + 1 floats).  The counting rule is
+ *   brNeumfRankCount's: every other score s adds 1 to the user's bin #{v < s} when v_0 <= s <= v_{n-1} (and to the tie bin of the same
+ *   index when v_lo == s), to bin n when s > v_{n-1}, and nothing below v_0 or when NaN.  bins / ties: int32 [cap + n_users] each, user
+ *   u's n + 1 bins from list_off[u] + u on; the call ADDS into them and does not zero them (integer atomics only: the sums do not depend
+ *   on the split plan or the order of arrival).  A list with list_off[u] < 0 or ending past cap is left alone (pcnt[u] = -1 of
+ *   brAucSortPieces: n = 0).  dump_scores (optional, n_users x n_items): every pair's score (tests).  Limits: those of
+ *   brDotCatalogRanks (1 <= dim <= 512, 1 <= n_items < 2^31, ld_q, ld_c >= dim) and cap + n_users < 2^31; BR_ERR_ARG before any launch;
+ *   n_users == 0 is BR_OK.  No workspace, no allocation and no sync inside. */
+int brDotRankCount(const float* Q, int64_t ld_q, int64_t n_users, const float* C, int64_t ld_c, int64_t n_items, int dim,
+                   const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off, const float* sorted, const int32_t* pcnt,
+                   int64_t cap, int32_t* bins, int32_t* ties, float* dump_scores, int flags, brStream stream);
+
 /* ---- evaluation of the BPR notebook model and hit counting -------------------
  * Ground truth per user = CSR list of COLUMN indices into the scored item list, ascending: truth_off (n_users + 1), truth_idx.
  * brFullAuc: full_auc (src/models/bpr.py:230-254) = per user sklearn.roc_auc_score(ground truth, scores over all items): the
