@@ -17,6 +17,40 @@ from . import _lib, ops
 from .row_adam import RowAdam
 
 
+class NegativeSampler:
+    """What the per-step negative sampler (BPREngine.sample_negatives, csrc/sampling_step.hip) needs of a training set: the positives'
+    CSR (ops.positives_csr), the candidate item ids (None: 0..n_items-1 with n_items = the largest positive item + 1) and, mode
+    "popularity", Walker's alias table of count(item)^power over the given positives, restricted to the candidates.
+    candidates = M > 1: dynamic negative sampling - every step draws M candidates per triplet and trains on the one the current model
+    scores highest."""
+
+    def __init__(self, users, items, n_users: int, cand_items=None, mode: str = "uniform", candidates: int = 1, power: float = 0.75, seed: int = 0,
+                 max_tries: int = 16, device="cuda", n_items: int | None = None):
+        import numpy as np
+        if mode not in ("uniform", "popularity"):
+            raise ValueError("mode must be 'uniform' or 'popularity'")
+        if not 1 <= int(candidates) <= 32:
+            raise ValueError("candidates must be in [1, 32]")
+        if not 1 <= int(max_tries) <= 256:
+            raise ValueError("max_tries must be in [1, 256]")
+        self.mode, self.candidates, self.power, self.seed, self.max_tries = mode, int(candidates), float(power), int(seed), int(max_tries)
+        self.device = torch.device(device)
+        self.pos_off, self.pos_items = ops.positives_csr(users, items, int(n_users), self.device)
+        it = np.asarray(items.cpu() if torch.is_tensor(items) else items).astype(np.int64)
+        if cand_items is None:
+            self.cand_items = None
+            self.n_cand = int(n_items) if n_items is not None else int(it.max()) + 1
+            cand = np.arange(self.n_cand, dtype=np.int64)
+        else:
+            cand = np.asarray(cand_items.cpu() if torch.is_tensor(cand_items) else cand_items).astype(np.int64)
+            self.cand_items = torch.from_numpy(cand).to(self.device).to(self.pos_items.dtype).contiguous()
+            self.n_cand = int(cand.shape[0])
+        self.alias = None
+        if mode == "popularity":
+            count = np.bincount(it, minlength=int(max(it.max(), cand.max())) + 1).astype(np.float64)
+            self.alias = ops.alias_table(count[cand] ** self.power, device=self.device)
+
+
 class BPREngine(RowAdam):
     """optimizer "adam_dense" = Keras' non-lazy sparse Adam (every row of both tables moves every step [TF-sem]); dense_impl
     "deferred" (default) reaches the untouched rows by per-row replay (include/binrec.h "Deferred dense Adam": the lookup replays a
@@ -191,6 +225,27 @@ class BPREngine(RowAdam):
         self._adam_rows("item", self.item_index, gi, self.dim, replayed=ri)
         self._adam_sweep("user")
         self._adam_sweep("item")
+
+    def sample_negatives(self, users, pos, sampler: NegativeSampler, pos0: int = 0, out=None, dump: bool = False):
+        """The negatives of the NEXT train_step's batch (users, pos), drawn now: negative b is a pure function of (sampler.seed, the
+        completed steps self.t, pos0 + b) and - sampler.candidates > 1 - the hardest of the candidates under the tables as of the last
+        completed step (deferred rows are replayed in registers, nothing is written).  One launch beside the step (outside a captured
+        graph), no host sync.  -> neg (B,), with dump=True also (cands (B, M), scores (B, M)).  `pos` is not read: the positives a
+        negative must avoid are the sampler's CSR."""
+        M = sampler.candidates
+        user = item = None
+        if M > 1:
+            user, item = self._sampler_tables()
+        return ops.bpr_sample_negatives(users, sampler.pos_off, sampler.pos_items, sampler.n_cand, sampler.seed, self.t, pos0=pos0, cand_items=sampler.cand_items,
+                                        alias=sampler.alias, candidates=M, max_tries=sampler.max_tries, user=user, item=item,
+                                        step_state=self.step_state if self.deferred else None, beta1=self.BETA1, beta2=self.BETA2, eps=self.EPS,
+                                        out=out, dump=dump, err_flag=self.err)
+
+    def _sampler_tables(self):
+        """the tables as sample_negatives scores against them (row-sharded engines refuse: parallel.py)"""
+        if self.deferred:
+            return (self._user, self.user_m, self.user_v, self.last["user"]), (self._item, self.item_m, self.item_v, self.last["item"])
+        return (self._user,), (self._item,)
 
     def pop_loss(self) -> float:
         """Host sync: mean triplet loss since the last call."""

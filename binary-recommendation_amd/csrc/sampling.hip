@@ -17,15 +17,12 @@
 #include "common.h"
 #include "rows.h"
 #include "philox.h"
+#include "sampling.h"      // mix32, draw_below, is_positive: shared with sampling_step.hip
 
 #include <hipcub/hipcub.hpp>
 
 namespace br {
 
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {      // murmur3 finaliser
-  x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-  return x;
-}
 struct PermKey { uint32_t k[4]; };
 __host__ __device__ __forceinline__ PermKey perm_key(uint64_t seed, uint32_t stream) {
   PermKey p;
@@ -50,11 +47,6 @@ __host__ __device__ __forceinline__ uint32_t feistel_perm(uint32_t x, uint32_t M
   } while (x >= M);
   return x;
 }
-// uniform integer in [0, n) from one Philox call: floor(u32 * n / 2^32)
-__device__ __forceinline__ uint32_t draw_below(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t stream, uint32_t n) {
-  const Philox4 d = philox4x32_10(c0, c1, stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-  return (uint32_t)(((uint64_t)d.x * (uint64_t)n) >> 32);
-}
 
 template <typename IdT>
 __global__ __launch_bounds__(256) void bootstrap_kernel(const IdT* __restrict__ users, const IdT* __restrict__ items, uint32_t n, uint32_t K, uint64_t seed,
@@ -67,18 +59,6 @@ __global__ __launch_bounds__(256) void bootstrap_kernel(const IdT* __restrict__ 
   const uint32_t a = draw_below(seed, j, 0u, 2u, n);                           // negDf = df.sample(frac=negRatio, replace=True)
   const uint32_t b = draw_below(seed, feistel_perm(j, K, perm_key(seed, 3u)), 0u, 2u, n);   // negDf.PRODUCT_ID.sample(frac=1.).values
   ou[t] = users[a]; oi[t] = items[b]; oy[t] = 0.f;
-}
-
-// membership of `item` in the sorted positive list of `user` (CSR)
-template <typename IdT>
-__device__ __forceinline__ bool is_positive(const int64_t* __restrict__ off, const IdT* __restrict__ pos_items, int64_t user, IdT item) {
-  int64_t lo = off[user], hi = off[user + 1];
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    const IdT v = pos_items[mid];
-    if (v < item) lo = mid + 1; else hi = mid;
-  }
-  return lo < off[user + 1] && pos_items[lo] == item;
 }
 
 template <typename IdT>

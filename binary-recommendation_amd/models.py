@@ -451,13 +451,23 @@ class BPRModel(RModel):
         df = pd.read_csv(path, nrows=rowLimit)
         return int(df.PRODUCT_ID.max()) + 1, int(df.CUSTOMER_ID.max()) + 1, df
 
-    def train(self, path, rowLimit, metricDict: dict = None, distributedConfig=None, negPerPos: int = 4, exhaustive: bool = False, seed: int = 0):
+    def train(self, path, rowLimit, metricDict: dict = None, distributedConfig=None, negPerPos: int = 4, exhaustive: bool = False, seed: int = 0,
+              negSampling: str = "static", hardCandidates: int = 1, popularityPower: float = 0.75):
         """BPRModel.train (src/models/BPRModel.py:76-109): batchSize 64, train/test split, triplets, compileModel, fit for
         `epochs`.  The reference enumerates EVERY (positive, non-interacted product) pair of every customer with Pool(5)
         (O(U*I) rows, :94-98,111-119); here `negPerPos` negatives per positive are sampled on the GPU (brBprSampleTriplets);
         exhaustive=True reproduces the enumeration for small data.  -> {'result': 'completed', 'metrics': [last epoch loss]}
-        in RModel.train's convention (the reference's BPR train returns None)."""
+        in RModel.train's convention (the reference's BPR train returns None).
+        negSampling: "static" (the default) draws the negatives once, before the first epoch, as above; "uniform" / "popularity" draw
+        them again in EVERY step (bpr.NegativeSampler, BPREngine.sample_negatives): uniformly over the training split's products, or
+        with weight count(product)^popularityPower; hardCandidates = M > 1 (dynamic negative sampling, per-step modes only) draws M
+        candidates per triplet and trains on the one the current model scores highest.  The per-step modes train on the positives
+        themselves (one triplet per positive and epoch; negPerPos and exhaustive belong to "static")."""
         from sklearn.model_selection import train_test_split
+        if negSampling not in ("static", "uniform", "popularity"):
+            raise ValueError(f"negSampling must be 'static', 'uniform' or 'popularity', got {negSampling!r}")
+        if int(hardCandidates) < 1 or (negSampling == "static" and int(hardCandidates) > 1):
+            raise ValueError("hardCandidates > 1 (dynamic negative sampling) needs negSampling='uniform' or 'popularity': static negatives are drawn before there is a model")
         self.batchSize = 64
         numItem, numUser, df = self.readData(path, rowLimit)
         self.trainDf, self.testDf = train_test_split(df, test_size=self.testSize, random_state=seed)
@@ -465,6 +475,14 @@ class BPRModel(RModel):
         self.productIds = self.trainDf.PRODUCT_ID.unique().tolist()
         self.compileModel(distributedConfig, max(customerIds) + 1, max(self.productIds) + 1, self.numFactor)
         tu, ti = self.trainDf.CUSTOMER_ID.to_numpy(), self.trainDf.PRODUCT_ID.to_numpy()
+        if negSampling != "static":
+            from .bpr import NegativeSampler
+            e = self.model
+            sampler = NegativeSampler(_to_dev(tu, e.device, e.id_dtype), _to_dev(ti, e.device, e.id_dtype), max(customerIds) + 1,
+                                      cand_items=_to_dev(np.asarray(self.productIds), e.device, e.id_dtype), mode=negSampling,
+                                      candidates=int(hardCandidates), power=popularityPower, seed=seed, device=e.device)
+            hist = self.fit({"customerId_input": tu, "pProduct_input": ti}, None, batch_size=self.batchSize, epochs=self.epochs, seed=seed, sampler=sampler)
+            return {"result": "completed", "metrics": [hist.history["loss"][-1]], "history": hist}
         if exhaustive:
             rows = [r for c in customerIds for r in self.extractPositivesNegatives(self.trainDf, c, self.productIds)]
             X = {"customerId_input": np.array([r["CUSTOMER_ID"] for r in rows], np.float32),
@@ -580,21 +598,27 @@ class BPRModel(RModel):
         """[(item, score)] as strings, best first, for one customer: recommendForUsers([customerId]) (excludeSeen off by default)."""
         return self.recommendForUsers([customerId], numberOfItem, excludeSeen=excludeSeen)[0]
 
-    def fit(self, X: dict, y=None, batch_size=64, epochs=1, seed=0):
-        """model.fit({'customerId_input','pProduct_input','nProduct_input'}, ones, batch_size, epochs) (BPRModel.py:100-109)."""
+    def fit(self, X: dict, y=None, batch_size=64, epochs=1, seed=0, sampler=None):
+        """model.fit({'customerId_input','pProduct_input','nProduct_input'}, ones, batch_size, epochs) (BPRModel.py:100-109).
+        sampler (bpr.NegativeSampler): X needs no 'nProduct_input' - every step's negatives are drawn right before it
+        (BPREngine.sample_negatives) at the global position epoch offset + row of the shuffled epoch, so no (seed, step, position)
+        repeats and the draws do not depend on how many ranks share the batch."""
         e = self.model
         u = _to_dev(X["customerId_input"], e.device, e.id_dtype).view(-1)
         p = _to_dev(X["pProduct_input"], e.device, e.id_dtype).view(-1)
-        n = _to_dev(X["nProduct_input"], e.device, e.id_dtype).view(-1)
+        n = _to_dev(X["nProduct_input"], e.device, e.id_dtype).view(-1) if sampler is None else None
         hist = History()
         g = torch.Generator(device=e.device).manual_seed(seed)
         ctx = getattr(e, "ctx", None)                 # row-sharded engine (compileModel under a process group): this rank's slice of each global batch
         slices = _rank_slices(u.shape[0], batch_size * (ctx.world if ctx is not None else 1), ctx)
+        epoch_offset = 0
         for _ in range(epochs):
             perm = torch.randperm(u.shape[0], device=e.device, generator=g)
-            uu, pp, nn = u[perm], p[perm], n[perm]
+            uu, pp, nn = u[perm], p[perm], (n[perm] if sampler is None else None)
             for lo, hi, _row0, bt in slices:
-                e.train_step(uu[lo:hi], pp[lo:hi], nn[lo:hi], batch_total=bt)
+                neg = nn[lo:hi] if sampler is None else e.sample_negatives(uu[lo:hi], pp[lo:hi], sampler, pos0=epoch_offset + lo)
+                e.train_step(uu[lo:hi], pp[lo:hi], neg, batch_total=bt)
+            epoch_offset += u.shape[0]
             e.check_ids()
             if ctx is not None:
                 ctx.all_reduce_sum(e.loss_slots)      # the epoch's loss over all replicas (a collective)

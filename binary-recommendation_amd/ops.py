@@ -1345,6 +1345,112 @@ def bpr_sample_triplets(users, items, pos_off, pos_items, neg_per_pos: int, seed
     return ou, op, on
 
 
+def alias_table(weights, device=None):
+    """Walker's alias table of `weights` (any non-negative numbers, not all zero) for brBprSampleNegatives -> (thresh uint32, alias
+    int32), n each: a draw takes slot s uniformly and keeps it iff a second uniform u32 is < thresh[s], else alias[s].  Built on the
+    host in numpy float64, deterministically (index plumbing, once per dataset).  thresh = min(floor(p * 2^32), 2^32 - 1) with p the
+    slot's keep probability; where it saturates the slot is its own alias, so the kernel's strict `<` is exact; a zero weight gives
+    thresh 0 (never kept) and is nobody's alias."""
+    import numpy as np
+    w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+    if w.size == 0 or np.isnan(w).any() or (w < 0).any() or not np.isfinite(w).all():
+        raise ValueError("alias_table: weights must be finite and non-negative")
+    tot = w.sum()
+    if not tot > 0:
+        raise ValueError("alias_table: all weights are zero")
+    n = w.size
+    p = w * (n / tot)                          # keep probabilities before pairing: mean 1
+    alias = np.arange(n, dtype=np.int64)
+    small = [i for i in range(n) if p[i] < 1.0]
+    large = [i for i in range(n) if p[i] >= 1.0]
+    keep = np.ones(n, dtype=np.float64)
+    while small and large:
+        s, l = small.pop(), large[-1]
+        keep[s], alias[s] = p[s], l
+        p[l] -= 1.0 - p[s]                     # the large slot gives the small one's remainder
+        if p[l] < 1.0:
+            large.pop()
+            small.append(l)
+    # what is left (rounding) keeps its own slot with probability 1 - except a zero weight stranded among the small ones
+    for s in small:
+        if w[s] == 0.0:
+            keep[s], alias[s] = 0.0, int(np.argmax(w))
+    thresh = np.minimum(np.floor(keep * 4294967296.0), 4294967295.0)
+    sat = thresh >= 4294967295.0
+    alias[sat] = np.arange(n)[sat]
+    dev = device if device is not None else (weights.device if torch.is_tensor(weights) else "cpu")
+    return (torch.from_numpy(thresh.astype(np.uint32)).to(dev), torch.from_numpy(alias.astype(np.int32)).to(dev))
+
+
+def bpr_sample_negatives(users, pos_off, pos_items, n_cand: int, seed: int, draw_step: int, pos0: int = 0, cand_items=None, alias=None, candidates: int = 1,
+                         max_tries: int = 16, user=None, item=None, step_state=None, beta1=0.9, beta2=0.999, eps=1e-7, out=None, dump=False,
+                         err_flag=None):
+    """The negatives of one batch, drawn for this step (brBprSampleNegatives, csrc/sampling_step.hip): negative b is a pure function of
+    (seed, draw_step, pos0 + b) - uniform over the candidates, or by `alias` = ops.alias_table(weights) - and, candidates = M > 1, the
+    hardest of M candidates under the tables as of the last completed step.  user / item: (table,) for current tables (sweep / lazy
+    Adam) or (table, m, v, last) for deferred ones (then step_state is needed); both None for M == 1.  -> out (B,) ids, and with
+    dump=True also (cands (B, M) ids, scores (B, M) float32).  No host sync."""
+    u, ty = _ids(users, "users")
+    _, pt = _ids(pos_items, "pos_items")
+    ty = _same_id_type(ty, pt)
+    M, B, dev = int(candidates), u.shape[0], u.device
+    if not 1 <= M <= 32:
+        raise ValueError("candidates must be in [1, 32]")
+    if not 1 <= int(max_tries) <= 256:
+        raise ValueError("max_tries must be in [1, 256]")
+    if pos_off.dtype != torch.int64 or not pos_off.is_cuda or not pos_off.is_contiguous():
+        raise TypeError("pos_off: expected contiguous int64 device offsets")
+    if cand_items is not None:
+        _, ct = _ids(cand_items, "cand_items")
+        ty = _same_id_type(ty, ct)
+        if cand_items.shape[0] != n_cand:
+            raise ValueError("cand_items must hold n_cand ids")
+    thresh = alias_to = None
+    if alias is not None:
+        thresh, alias_to = alias
+        if thresh.dtype != torch.uint32 or alias_to.dtype != torch.int32 or not (thresh.is_cuda and alias_to.is_cuda and thresh.is_contiguous() and alias_to.is_contiguous()) \
+                or thresh.shape[0] != n_cand or alias_to.shape[0] != n_cand:
+            raise TypeError("alias: (uint32 thresh, int32 alias) contiguous device tensors of n_cand entries (ops.alias_table)")
+    tu = ti = (None, None, None, None)
+    dim = 0
+    if M > 1:
+        if user is None or item is None:
+            raise ValueError("candidates > 1 scores the candidates: the user and item tables are required")
+        if len(user) != len(item) or len(user) not in (1, 4):
+            raise ValueError("user / item: (table,) or (table, m, v, last), the same form for both")
+        user, item = tuple(user), tuple(item)
+        for t in user[:3] + item[:3]:
+            _f32(t, "table / moment")
+        for name, tab in (("user", user), ("item", item)):
+            if tab[0].dim() != 2:
+                raise ValueError(f"{name}: the table must be (rows, dim)")
+            if len(tab) == 4:
+                if tab[1].shape != tab[0].shape or tab[2].shape != tab[0].shape:
+                    raise ValueError(f"{name}: m and v must have the table's shape")
+                last = tab[3]
+                if last.dtype != torch.int32 or not last.is_cuda or not last.is_contiguous() or last.dim() != 1 or last.shape[0] != tab[0].shape[0]:
+                    raise TypeError(f"{name}: last must be a contiguous int32 device tensor with one entry per table row")
+        if user[0].shape[1] != item[0].shape[1]:
+            raise ValueError("the user and the item table must have the same dim")
+        dim = user[0].shape[1]
+        tu, ti = tuple(user) + (None,) * (4 - len(user)), tuple(item) + (None,) * (4 - len(item))
+        if len(user) == 4 and step_state is None:
+            raise ValueError("deferred tables need the step state")
+    if out is None:
+        out = torch.empty(B, dtype=u.dtype, device=dev)
+    elif out.dtype != u.dtype or not out.is_contiguous() or out.shape[0] != B:
+        raise TypeError("out: contiguous ids of the users' dtype, one per row")
+    cands = torch.empty(B, M, dtype=u.dtype, device=dev) if dump else None
+    scores = torch.empty(B, M, dtype=torch.float32, device=dev) if dump else None
+    check(_lib.load().brBprSampleNegatives(u.data_ptr(), ty, B, int(pos0), int(draw_step) & 0xFFFFFFFF, pos_off.data_ptr(), pos_items.data_ptr(), pos_off.shape[0] - 1,
+                                           _p(cand_items), int(n_cand), _p(thresh), _p(alias_to), int(seed), M, int(max_tries),
+                                           _p(tu[0]), _p(tu[1]), _p(tu[2]), _p(tu[3]), 0 if tu[0] is None else tu[0].shape[0],
+                                           _p(ti[0]), _p(ti[1]), _p(ti[2]), _p(ti[3]), 0 if ti[0] is None else ti[0].shape[0], dim,
+                                           _p(step_state) if M > 1 and tu[1] is not None else 0, beta1, beta2, eps, out.data_ptr(), _p(cands), _p(scores),
+                                           _p(err_flag), _stream()), "brBprSampleNegatives")
+    return (out, cands, scores) if dump else out
+
+
 def ncf_negatives(users, items, pos_off, pos_items, num_items: int, size: int, seed: int, oversample: float = 1.3, max_rounds: int = 8):
     """generateNegativeFeedback on the device: `size` DISTINCT (user, item) pairs outside the positives, users and items drawn by
     shuffling the two columns independently.  One host sync per round (the count of distinct valid candidates)."""

@@ -1151,6 +1151,12 @@ def make_sharded_bpr(base_cls):
                 self._adam_sweep(name)
             self.n_seen += B
 
+        def _sampler_tables(self):
+            """sample_negatives with candidates == 1 reads no table and works as on one device (with pos0 = the slice's global row
+            offset the negatives do not depend on the world size); scoring M > 1 candidates does not"""
+            raise NotImplementedError("hard negatives (candidates > 1) on the row-sharded engine: the candidate rows live at their owners "
+                                      "(an id-to-owner exchange of B x M rows, or scoring at the owners: DESIGN.md section 7)")
+
         def _gather_global(self, name, ids):
             """rows `ids` (global ids, any owner) of the row-sharded table `name` -> (len(ids), dim) on this rank."""
             x = ShardExchange(self.ctx).plan(ids)

@@ -758,12 +758,37 @@ int brMapAtK(const int32_t* topk_index, int64_t n_users, int k, const int64_t* t
  *   208-223,237-256): candidates = customer column and product column shuffled independently, round after round (candidate j:
  *   round j / n); keys[j] = user * num_items + item, or ~0 for a positive pair.  Sorted and de-duplicated they are the pool of
  *   distinct negatives (n_unique counts a trailing ~0 if any candidate was invalid); brGatherPermutedPairs takes n_out of the
- *   first n_keys of them in a shuffled order (the reference's head(size)). */
+ *   first n_keys of them in a shuffled order (the reference's head(size)).
+ * brBprSampleNegatives (csrc/sampling_step.hip): the negatives of ONE batch, drawn per step - the per-step form of the site
+ *   brBprSampleTriplets stands in for (src/models/BPRModel.py:94-98,111-119), with the two standard strategies: popularity-weighted
+ *   draws and dynamic negative sampling (n_candidates = M > 1: draw M, score them with the current model, keep the hardest).
+ *   out_neg[b] is a pure function of (seed, draw_step, pos0 + b) and - M > 1 - of the tables:
+ *     candidate j < M, attempt a < max_tries: d = Philox4x32-10(counter (pos0 + b, j * 256 + a, 5, draw_step), key seed) (stream 5;
+ *       1-4 are taken above); slot = (d.x * n_cand) >> 32; with an alias table (alias_thresh uint32 / alias_slot int32, n_cand
+ *       entries each, Walker's method; both NULL = uniform): if d.y >= alias_thresh[slot] then slot = alias_slot[slot];
+ *       id = cand_items ? cand_items[slot] : slot; re-drawn while id is a positive of users[b] and a + 1 < max_tries (the last attempt
+ *       stands: the rule of brBprSampleTriplets).  pos_off (num_users + 1) / pos_items: the positives' CSR, items ascending.
+ *     M > 1: score_j = <user row, candidate j's row> in fp32 (per-lane fused multiply-adds in column order, then a fixed shuffle
+ *       tree: the same bits for the same inputs); out_neg[b] = the first candidate whose score is strictly greater than every earlier
+ *       one (a NaN never wins).  The rows are those of the last completed step: deferred tables (m, v, last of both tables and the
+ *       step state given) are replayed over (last[row], step_state->step] in registers as brGatherRowsDeferred does, nothing is
+ *       written back; current tables (sweep / lazy Adam) pass m = v = last = NULL and are read as stored.
+ *     M == 1 reads no table: the table pointers may be NULL.
+ *   out_neg (batch) and the optional out_cands (batch x M ids) have the id type of `users`; out_scores (batch x M floats, optional;
+ *   0 for M == 1).  Ids outside their table or CSR set BR_ERRFLAG_RANGE in *err_flag and use row 0.
+ *   Limits: 1 <= M <= 32, 1 <= max_tries <= 256, batch < 2^31, n_cand < 2^32; M > 1 needs both tables; BR_ERR_ARG before any launch. */
 int brBootstrapDataset(const void* users, const void* items, int id_type, int64_t n, int64_t n_neg, uint64_t seed, void* out_users,
                        void* out_items, float* out_labels, brStream stream);
 int brBprSampleTriplets(const void* users, const void* items, int id_type, int64_t n, int neg_per_pos, const int64_t* pos_off,
                         const void* pos_items, const void* cand_items, int64_t n_cand, uint64_t seed, int max_tries, void* out_users,
                         void* out_pos, void* out_neg, brStream stream);
+int brBprSampleNegatives(const void* users, int id_type, int64_t batch, int64_t pos0, uint32_t draw_step, const int64_t* pos_off,
+                         const void* pos_items, int64_t num_users, const void* cand_items, int64_t n_cand, const uint32_t* alias_thresh,
+                         const int32_t* alias_slot, uint64_t seed, int n_candidates, int max_tries, const float* user_table,
+                         const float* user_m, const float* user_v, const int32_t* user_last, int64_t user_rows, const float* item_table,
+                         const float* item_m, const float* item_v, const int32_t* item_last, int64_t item_rows, int dim,
+                         const void* step_state, double beta1, double beta2, double eps, void* out_neg, void* out_cands,
+                         float* out_scores, int* err_flag, brStream stream);
 int brNcfNegativeCandidates(const void* users, const void* items, int id_type, int64_t n, int64_t n_cand, const int64_t* pos_off,
                             const void* pos_items, int64_t num_items, uint64_t seed, uint64_t* keys, brStream stream);
 int64_t brSortUniqueWorkspaceBytes(int64_t n);
