@@ -15,40 +15,24 @@ import torch
 
 from . import _lib, ops
 from .row_adam import RowAdam
+from .sampler import CandidatePool
 
 
-class NegativeSampler:
+class NegativeSampler(CandidatePool):
     """What the per-step negative sampler (BPREngine.sample_negatives, csrc/sampling_step.hip) needs of a training set: the positives'
     CSR (ops.positives_csr), the candidate item ids (None: 0..n_items-1 with n_items = the largest positive item + 1) and, mode
-    "popularity", Walker's alias table of count(item)^power over the given positives, restricted to the candidates.
+    "popularity", Walker's alias table of count(item)^power over the given positives, restricted to the candidates (sampler.py).
     candidates = M > 1: dynamic negative sampling - every step draws M candidates per triplet and trains on the one the current model
     scores highest."""
 
     def __init__(self, users, items, n_users: int, cand_items=None, mode: str = "uniform", candidates: int = 1, power: float = 0.75, seed: int = 0,
                  max_tries: int = 16, device="cuda", n_items: int | None = None):
-        import numpy as np
         if mode not in ("uniform", "popularity"):
             raise ValueError("mode must be 'uniform' or 'popularity'")
         if not 1 <= int(candidates) <= 32:
             raise ValueError("candidates must be in [1, 32]")
-        if not 1 <= int(max_tries) <= 256:
-            raise ValueError("max_tries must be in [1, 256]")
-        self.mode, self.candidates, self.power, self.seed, self.max_tries = mode, int(candidates), float(power), int(seed), int(max_tries)
-        self.device = torch.device(device)
-        self.pos_off, self.pos_items = ops.positives_csr(users, items, int(n_users), self.device)
-        it = np.asarray(items.cpu() if torch.is_tensor(items) else items).astype(np.int64)
-        if cand_items is None:
-            self.cand_items = None
-            self.n_cand = int(n_items) if n_items is not None else int(it.max()) + 1
-            cand = np.arange(self.n_cand, dtype=np.int64)
-        else:
-            cand = np.asarray(cand_items.cpu() if torch.is_tensor(cand_items) else cand_items).astype(np.int64)
-            self.cand_items = torch.from_numpy(cand).to(self.device).to(self.pos_items.dtype).contiguous()
-            self.n_cand = int(cand.shape[0])
-        self.alias = None
-        if mode == "popularity":
-            count = np.bincount(it, minlength=int(max(it.max(), cand.max())) + 1).astype(np.float64)
-            self.alias = ops.alias_table(count[cand] ** self.power, device=self.device)
+        self.candidates = int(candidates)
+        super().__init__(users, items, n_users, cand_items=cand_items, mode=mode, power=power, seed=seed, max_tries=max_tries, device=device, n_items=n_items)
 
 
 class BPREngine(RowAdam):

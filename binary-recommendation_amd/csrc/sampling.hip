@@ -17,36 +17,11 @@
 #include "common.h"
 #include "rows.h"
 #include "philox.h"
-#include "sampling.h"      // mix32, draw_below, is_positive: shared with sampling_step.hip
+#include "sampling.h"      // mix32, draw_below, is_positive, perm_key, feistel_perm: shared with sampling_step.hip, sampling_epoch.hip
 
 #include <hipcub/hipcub.hpp>
 
 namespace br {
-
-struct PermKey { uint32_t k[4]; };
-__host__ __device__ __forceinline__ PermKey perm_key(uint64_t seed, uint32_t stream) {
-  PermKey p;
-  for (int r = 0; r < 4; ++r) p.k[r] = mix32((uint32_t)seed + 0x9E3779B9u * (uint32_t)(r + 1)) ^ mix32((uint32_t)(seed >> 32) ^ (stream * 0x85ebca6bu + (uint32_t)r));
-  return p;
-}
-// keyed bijection of [0, M), M >= 1
-__host__ __device__ __forceinline__ uint32_t feistel_perm(uint32_t x, uint32_t M, const PermKey& key) {
-  if (M <= 1) return 0;
-  int b = 1;
-  while (b < 32 && (1ull << b) < (uint64_t)M) ++b;
-  const int hb = (b + 1) >> 1;
-  const uint32_t mask = (1u << hb) - 1u;
-  do {
-    uint32_t L = x >> hb, R = x & mask;
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t F = mix32(R ^ key.k[r]) & mask;
-      const uint32_t t = L ^ F;
-      L = R; R = t;
-    }
-    x = (L << hb) | R;
-  } while (x >= M);
-  return x;
-}
 
 template <typename IdT>
 __global__ __launch_bounds__(256) void bootstrap_kernel(const IdT* __restrict__ users, const IdT* __restrict__ items, uint32_t n, uint32_t K, uint64_t seed,

@@ -41,31 +41,6 @@ struct SampleArgs {
   void* out_neg; void* out_cands; float* out_scores; int* err;
 };
 
-// the positives of one customer for the rejection test: a list of up to 8 items is fetched ONCE, by independent loads (one round trip;
-// the binary search of is_positive is a chain of dependent ones per attempt, and the launch is bound by such chains), a longer one is
-// searched.  The same answer either way.
-template <typename IdT>
-struct Positives {
-  const int64_t* off; const IdT* items; int64_t user; int64_t n; IdT v[8];
-  __device__ __forceinline__ void load(const int64_t* __restrict__ o, const IdT* __restrict__ it, int64_t u) {
-    off = o; items = it; user = u;
-    const int64_t lo = o[u];
-    n = o[u + 1] - lo;
-    if (n >= 1 && n <= 8) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = it[lo + (k < n ? k : n - 1)];
-    }
-  }
-  __device__ __forceinline__ bool has(IdT item) const {
-    if (n <= 0) return false;
-    if (n > 8) return is_positive(off, items, user, item);
-    bool hit = false;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hit |= v[k] == item;      // (entries past n repeat the last one)
-    return hit;
-  }
-};
-
 // candidate j of position c0: attempt a takes Philox(c0, j * 256 + a, stream 5, draw step); the last attempt stands.  last != NULL: also
 // -> seen = last[id] of the candidate that stands (0 and the RANGE flag for an id outside [0, rows)), requested BEFORE the rejection test
 // of its attempt, which it does not depend on.
@@ -77,12 +52,7 @@ __device__ __forceinline__ int64_t draw_candidate(const DrawArgs& a, int64_t use
   int64_t id = 0;
   for (int t = 0; t < a.max_tries; ++t) {
     const Philox4 d = philox4x32_10(c0, j * 256u + (uint32_t)t, 5u, a.step, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    uint32_t slot = (uint32_t)(((uint64_t)d.x * (uint64_t)a.n_cand) >> 32);
-    if (a.thresh && d.y >= a.thresh[slot]) {
-      slot = (uint32_t)a.alias[slot];
-      if (slot >= a.n_cand) { if (err) atomicOr(err, BR_ERRFLAG_RANGE); slot = 0; }      // (a table ops.alias_table did not build)
-    }
-    id = a.cand ? (int64_t)((const IdT*)a.cand)[slot] : (int64_t)slot;
+    id = candidate_of<IdT>(d, a.cand, a.thresh, a.alias, a.n_cand, err);
     if (last) *seen = (uint32_t)last[(uint64_t)id < (uint64_t)rows ? id : 0];
     if (!pos.has((IdT)id)) break;
   }

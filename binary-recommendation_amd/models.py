@@ -145,13 +145,26 @@ class KerasLikeNeuMF:
         yy = None if y is None else _to_dev(y, e.device, torch.float32)
         return u.view(-1), i.view(-1), None if yy is None else yy.view(-1)
 
-    def fit(self, x, y=None, epochs=1, batch_size=None, shuffle=True, verbose=0, callbacks=None, validation_data=None,
-            seed=0, orders=None):
+    def fit(self, x=None, y=None, epochs=1, batch_size=None, shuffle=True, verbose=0, callbacks=None, validation_data=None,
+            seed=0, orders=None, sampler=None):
         """model.fit([users, items], labels, epochs, batch_size, shuffle) (NFC_plain.py:165).  Per epoch the
-        sample order is re-drawn (Keras shuffle=True); metrics are read back once per epoch."""
+        sample order is re-drawn (Keras shuffle=True); metrics are read back once per epoch.
+        sampler = neumf.BatchSampler instead of x and y: the epoch has sampler.rows_per_epoch rows, none of them stored - every slice of
+        _rank_slices is formed by one NeuMFEngine.sample_batch launch at epoch sampler.epoch + ep when its step is due (a rank of the
+        row-sharded engine forms its own slice of the global batch), into the graph's own inputs where the step is a graph replay: the
+        S x B rows of a multi-step graph launch come from ONE launch.  No host shuffle, no host sync inside an epoch; the order and the
+        negatives are the sampler's (shuffle and seed are not read), validation_data stays a static set, and sampler.epoch is advanced
+        by `epochs` at the end, so a second fit repeats no draw."""
         e = self.engine
-        u, i, yy = self._xy(x, y)
-        n = u.shape[0]
+        if sampler is not None:
+            if x is not None or y is not None or orders is not None:
+                raise ValueError("fit: a sampler forms the epoch's rows itself - pass either x and y (and orders) or sampler, not both")
+            n = sampler.rows_per_epoch
+        else:
+            if x is None or y is None:
+                raise ValueError("fit: give the samples x and their labels y, or a sampler (neumf.BatchSampler)")
+            u, i, yy = self._xy(x, y)
+            n = u.shape[0]
         bs = int(batch_size or 32)
         if bs > e.max_batch:
             raise ValueError(f"batch_size {bs} > engine max_batch {e.max_batch}")
@@ -160,27 +173,34 @@ class KerasLikeNeuMF:
         ctx = e.dist if getattr(e, "sharded", False) else None
         slices = _rank_slices(n, bs * (ctx.world if ctx is not None else 1), ctx)
         hist = History()
-        g = torch.Generator(device=e.device).manual_seed(seed)
+        g = torch.Generator(device=e.device).manual_seed(seed) if sampler is None else None
         for ep in range(epochs):
-            if orders is not None:       # caller-supplied sample order per epoch (reproducible comparisons)
-                perm = _to_dev(orders[ep], e.device, torch.int64)
-                uu, ii, ll = u[perm], i[perm], yy[perm]
-            elif shuffle:
-                perm = torch.randperm(n, device=e.device, generator=g)
-                uu, ii, ll = u[perm], i[perm], yy[perm]
+            # rows(lo, hi, into): rows [lo, hi) of this epoch's order; `into` names the graph inputs that will read them (a sampler
+            # forms them there, so nothing is staged; stored rows are slices of the permuted set, as before)
+            if sampler is not None:
+                rows = lambda lo, hi, into, epoch=sampler.epoch + ep: e.sample_batch(sampler, epoch, lo, hi - lo, out=into)
             else:
-                uu, ii, ll = u, i, yy
+                if orders is not None:       # caller-supplied sample order per epoch (reproducible comparisons)
+                    perm = _to_dev(orders[ep], e.device, torch.int64)
+                    uu, ii, ll = u[perm], i[perm], yy[perm]
+                elif shuffle:
+                    perm = torch.randperm(n, device=e.device, generator=g)
+                    uu, ii, ll = u[perm], i[perm], yy[perm]
+                else:
+                    uu, ii, ll = u, i, yy
+                rows = lambda lo, hi, into, uu=uu, ii=ii, ll=ll: (uu[lo:hi], ii[lo:hi], ll[lo:hi])
             gm = getattr(e, "_graph_multi", None) if ctx is None else None
+            g1 = getattr(e, "_graph", None) if ctx is None else None
             k = 0
             while k < len(slices):
                 lo, hi, row0, bt = slices[k]
                 # engine.enable_graph_multi(batch_size, S): S consecutive full batches of the (contiguous) epoch order are one graph launch
                 if gm is not None and gm["batch"] == bs and k + gm["S"] <= len(slices) and slices[k + gm["S"] - 1][1] - lo == gm["S"] * bs:
-                    end = lo + gm["S"] * bs
-                    e.train_steps(uu[lo:end], ii[lo:end], ll[lo:end])
+                    e.train_steps(*rows(lo, lo + gm["S"] * bs, (e.in_users_m, e.in_items_m, e.in_labels_m)))
                     k += gm["S"]
                     continue
-                e.train_step(uu[lo:hi], ii[lo:hi], ll[lo:hi], row0=row0, batch_total=bt)
+                into = (e.in_users, e.in_items, e.in_labels) if g1 is not None and hi - lo == g1["batch"] else None
+                e.train_step(*rows(lo, hi, into), row0=row0, batch_total=bt)
                 k += 1
             e.check_ids()
             if ctx is not None:
@@ -194,6 +214,8 @@ class KerasLikeNeuMF:
                 cb.on_epoch_end(ep, logs)
             if verbose:
                 print(f"Epoch {ep + 1}/{epochs} - " + " - ".join(f"{k}: {v:.6f}" for k, v in logs.items()))
+        if sampler is not None:
+            sampler.epoch += epochs
         return hist
 
     def predict(self, x, batch_size=None, verbose=0):
@@ -303,7 +325,9 @@ class NeuMFModel(RModel):
         u, i, y = _data.bootstrap_dataset(df[self.CUSTOMER_ID].to_numpy(), df[self.PRODUCT_ID].to_numpy(), negRatio, seed, self.device)
         return {"user": u, "item": i, "label": y, "batch_size": batchSize, "shuffle": shuffle}
 
-    def prepareToTrain(self, distributedConfig, path, rowLimit):
+    def prepareToTrain(self, distributedConfig, path, rowLimit, negRatio=3.0, bootstrapTrain=True):
+        """bootstrapTrain=False (train with a per-step sampler): the training split is not bootstrapped - nothing of its n (1 + negRatio)
+        rows is made; trainDs then holds the batch size alone."""
         from sklearn.model_selection import train_test_split
         numItem, numUser, df = self.readData(path, rowLimit)
         trainSplit, testSplit = train_test_split(df, test_size=self.testSize)
@@ -311,17 +335,32 @@ class NeuMFModel(RModel):
         self._products = testSplit.PRODUCT_ID.unique().tolist()
         self._users = testSplit.CUSTOMER_ID.unique().tolist()
         bs = 128 if distributedConfig is None else self.batchSize     # NeuMFModel.py:43-48
-        trainDs, testDs = self.bootstrapDataset(trainSplit, batchSize=bs), self.bootstrapDataset(testSplit, batchSize=bs, shuffle=False)
+        trainDs = self.bootstrapDataset(trainSplit, negRatio=negRatio, batchSize=bs) if bootstrapTrain else {"batch_size": bs}
+        testDs = self.bootstrapDataset(testSplit, batchSize=bs, shuffle=False)
         self.compileModel(distributedConfig, numUser, numItem, self.numFactor)
         return trainDs, testDs, trainSplit
 
-    def train(self, path, rowLimit, metricDict: dict = {}, distributedConfig=None):
-        """RModel.train (RModel.py:115-150) -> {'result': 'completed', 'metrics': [...]}."""
+    def train(self, path, rowLimit, metricDict: dict = {}, distributedConfig=None, negSampling: str = "static", negRatio=3):
+        """RModel.train (RModel.py:115-150) -> {'result': 'completed', 'metrics': [...]}.
+        negSampling "static" (default): the training set is bootstrapDataset's, made once (NeuMFModel.py:102-109).  "uniform" /
+        "popularity": every batch is formed on the device when its step is due (neumf.BatchSampler over the training split):
+        round(negRatio) negatives per positive, drawn again in every epoch - uniformly over the products or by count^0.75 - and never
+        one of the customer's own products.  The test and validation sets stay bootstrapDataset's."""
         from sklearn.model_selection import train_test_split
-        trainDs, testDs, trainSplit = self.prepareToTrain(distributedConfig, path, rowLimit)
-        self.model.fit({"user": trainDs["user"], "item": trainDs["item"]}, trainDs["label"], epochs=self.epochs,
-                       batch_size=trainDs["batch_size"], shuffle=trainDs["shuffle"],
-                       validation_data=({"user": testDs["user"], "item": testDs["item"]}, testDs["label"]))
+        if negSampling not in ("static", "uniform", "popularity"):
+            raise ValueError("negSampling must be 'static', 'uniform' or 'popularity'")
+        trainDs, testDs, trainSplit = self.prepareToTrain(distributedConfig, path, rowLimit, negRatio=float(negRatio), bootstrapTrain=negSampling == "static")
+        val_data = ({"user": testDs["user"], "item": testDs["item"]}, testDs["label"])
+        if negSampling == "static":
+            self.model.fit({"user": trainDs["user"], "item": trainDs["item"]}, trainDs["label"], epochs=self.epochs,
+                           batch_size=trainDs["batch_size"], shuffle=trainDs["shuffle"], validation_data=val_data)
+        else:
+            from .neumf import BatchSampler
+            e = self.model.engine
+            sampler = BatchSampler(_to_dev(trainSplit[self.CUSTOMER_ID].to_numpy(), e.device, e.id_dtype),
+                                   _to_dev(trainSplit[self.PRODUCT_ID].to_numpy(), e.device, e.id_dtype), e.num_user_rows,
+                                   neg_per_pos=int(round(negRatio)), mode=negSampling, n_items=e.num_item_rows, device=e.device)
+            self.model.fit(sampler=sampler, epochs=self.epochs, batch_size=trainDs["batch_size"], validation_data=val_data)
         os.makedirs(os.path.dirname(self.checkpointPath), exist_ok=True)
         self.model.save(self.checkpointPath)
         _, val = train_test_split(trainSplit, test_size=0.2)

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib, ops
 from .row_adam import RowAdam
+from .sampler import CandidatePool
 
 DENSE_ORDER = ("W1", "b1", "g1", "be1", "W2", "b2", "g2", "be2", "W3", "b3", "W4", "b4")
 TABLES = ("user_mlp", "item_mlp", "user_mf", "item_mf")
@@ -95,6 +96,31 @@ class _Flat:
         o0 = self.offsets[k0][0]
         o1, n1, _ = self.offsets[k1]
         return self.buf[o0:o1 + n1]
+
+
+class BatchSampler(CandidatePool):
+    """What the per-step batch sampler (NeuMFEngine.sample_batch, csrc/sampling_epoch.hip) needs of a training set: the positives on the
+    device, their CSR, the candidate items and - mode "popularity" - the alias table, exactly as bpr.NegativeSampler holds them
+    (sampler.py).  An epoch is every positive once (label 1) and neg_per_pos negatives per positive (label 0), drawn again in every
+    epoch: rows_per_epoch = n (1 + neg_per_pos) rows in a keyed order, none of them stored.  `epoch` is the next epoch to draw:
+    KerasLikeNeuMF.fit(sampler=) advances it, so a second fit repeats no draw."""
+
+    def __init__(self, users, items, n_users: int, neg_per_pos: int = 3, cand_items=None, mode: str = "uniform", power: float = 0.75, seed: int = 0,
+                 max_tries: int = 16, n_items: int | None = None, device="cuda"):
+        import numpy as np
+        if int(neg_per_pos) < 0:
+            raise ValueError("neg_per_pos must be >= 0")
+        super().__init__(users, items, n_users, cand_items=cand_items, mode=mode, power=power, seed=seed, max_tries=max_tries, device=device, n_items=n_items)
+        dt = self.pos_items.dtype
+        as_dev = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))).to(self.device).to(dt).contiguous().view(-1)
+        self.users, self.items = as_dev(users), as_dev(items)
+        if self.users.shape != self.items.shape or self.users.shape[0] < 1:
+            raise ValueError("users and items: one id each per positive, at least one")
+        self.neg_per_pos = int(neg_per_pos)
+        self.rows_per_epoch = int(self.users.shape[0]) * (1 + self.neg_per_pos)
+        if self.rows_per_epoch >= 1 << 32:
+            raise ValueError("an epoch of n (1 + neg_per_pos) rows must have fewer than 2^32")
+        self.epoch = 0
 
 
 class NeuMFEngine(RowAdam):
@@ -521,6 +547,17 @@ class NeuMFEngine(RowAdam):
         self.t += S
         gm["graph"].replay()
         self._keep_for = (self.t + 1, 0) if prefetching else None
+
+    def sample_batch(self, sampler: BatchSampler, epoch: int, row0: int, B: int, out=None):
+        """Rows [row0, row0 + B) of epoch `epoch` of `sampler`, formed now for train_step / train_steps: a pure function of
+        (sampler.seed, epoch, global row), so a rank of the row-sharded engine asks for its own slice of the global batch and the ranks'
+        slices are the single-device epoch.  One launch beside the step (outside a captured graph), no host sync.  out: optional
+        (users, items, labels) buffers of B rows.  -> (users, items, labels) in the engine's id dtype and float32."""
+        if sampler.users.dtype != self.id_dtype:
+            raise TypeError(f"the sampler holds {sampler.users.dtype} ids, the engine takes {self.id_dtype}")
+        return ops.neumf_sample_batch(sampler.users, sampler.items, sampler.pos_off, sampler.pos_items, sampler.n_cand, sampler.neg_per_pos, sampler.seed,
+                                      epoch, row0, B, cand_items=sampler.cand_items, alias=sampler.alias, max_tries=sampler.max_tries, out=out,
+                                      err_flag=self.err)
 
     def _snapshot_for_dry_run(self):
         """what enable_graph's dry-run step can change.  Per-step sweep: every table row moves, so the whole (flushed) state.  Deferred /

@@ -1451,6 +1451,60 @@ def bpr_sample_negatives(users, pos_off, pos_items, n_cand: int, seed: int, draw
     return (out, cands, scores) if dump else out
 
 
+def neumf_sample_batch(pos_users, pos_items, pos_off, pos_sorted_items, n_cand: int, neg_per_pos: int, seed: int, epoch: int, row0: int, batch: int,
+                       cand_items=None, alias=None, max_tries: int = 16, out=None, err_flag=None):
+    """Rows [row0, row0 + batch) of epoch `epoch` of the NeuMF fit, formed for this step (brNeumfSampleBatch, csrc/sampling_epoch.hip): a
+    pure function of (seed, epoch, global row) - every positive (pos_users, pos_items) once per epoch with label 1 and neg_per_pos
+    negatives per positive with label 0, uniform over the candidates or by `alias` = ops.alias_table(weights), re-drawn while they are
+    positives of the user (pos_off / pos_sorted_items: ops.positives_csr).  out: optional (users, items, labels) to write into.
+    -> (users, items, labels) of `batch` rows, ids in the positives' dtype, labels float32.  No host sync."""
+    # (the dtypes first: a mismatch is refused wherever the tensors live)
+    _same_id_type(*(t.dtype for t in (pos_users, pos_items, pos_sorted_items, cand_items) if t is not None))
+    pu, ty = _ids(pos_users, "pos_users")
+    pi, it = _ids(pos_items, "pos_items")
+    _, pt = _ids(pos_sorted_items, "pos_sorted_items")
+    ty = _same_id_type(ty, it, pt)
+    if pu.dim() != 1 or pu.shape != pi.shape or pu.shape[0] < 1:
+        raise ValueError("pos_users and pos_items: one id each per positive, at least one")
+    n, r, B, dev = pu.shape[0], int(neg_per_pos), int(batch), pu.device
+    if r < 0:
+        raise ValueError("neg_per_pos must be >= 0")
+    if not 1 <= int(max_tries) <= 256:
+        raise ValueError("max_tries must be in [1, 256]")
+    if pos_off.dtype != torch.int64 or not pos_off.is_cuda or not pos_off.is_contiguous():
+        raise TypeError("pos_off: expected contiguous int64 device offsets")
+    if n * (1 + r) >= 1 << 32:
+        raise ValueError("an epoch of n (1 + neg_per_pos) rows must have fewer than 2^32")
+    if int(row0) < 0 or B < 0 or int(row0) + B > n * (1 + r):
+        raise ValueError("rows [row0, row0 + batch) must lie inside the epoch's n (1 + neg_per_pos) rows")
+    if cand_items is not None:
+        _, ct = _ids(cand_items, "cand_items")
+        ty = _same_id_type(ty, ct)
+        if cand_items.shape[0] != n_cand:
+            raise ValueError("cand_items must hold n_cand ids")
+    thresh = alias_to = None
+    if alias is not None:
+        thresh, alias_to = alias
+        if thresh.dtype != torch.uint32 or alias_to.dtype != torch.int32 or not (thresh.is_cuda and alias_to.is_cuda and thresh.is_contiguous() and alias_to.is_contiguous()) \
+                or thresh.shape[0] != n_cand or alias_to.shape[0] != n_cand:
+            raise TypeError("alias: (uint32 thresh, int32 alias) contiguous device tensors of n_cand entries (ops.alias_table)")
+    if out is None:
+        ou, oi = torch.empty(B, dtype=pu.dtype, device=dev), torch.empty(B, dtype=pu.dtype, device=dev)
+        oy = torch.empty(B, dtype=torch.float32, device=dev)
+    else:
+        ou, oi, oy = out
+        for t in (ou, oi):
+            if t.dtype != pu.dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != B:
+                raise TypeError("out: (users, items) contiguous device ids of the positives' dtype, one per row")
+        _f32(oy, "out labels")
+        if oy.numel() != B:
+            raise TypeError("out: labels, one float32 per row")
+    check(_lib.load().brNeumfSampleBatch(pu.data_ptr(), pi.data_ptr(), ty, n, r, pos_off.data_ptr(), pos_sorted_items.data_ptr(), pos_off.shape[0] - 1,
+                                         _p(cand_items), int(n_cand), _p(thresh), _p(alias_to), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, int(row0), B,
+                                         int(max_tries), ou.data_ptr(), oi.data_ptr(), oy.data_ptr(), _p(err_flag), _stream()), "brNeumfSampleBatch")
+    return ou, oi, oy
+
+
 def ncf_negatives(users, items, pos_off, pos_items, num_items: int, size: int, seed: int, oversample: float = 1.3, max_rounds: int = 8):
     """generateNegativeFeedback on the device: `size` DISTINCT (user, item) pairs outside the positives, users and items drawn by
     shuffling the two columns independently.  One host sync per round (the count of distinct valid candidates)."""

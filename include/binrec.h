@@ -776,7 +776,22 @@ int brMapAtK(const int32_t* topk_index, int64_t n_users, int k, const int64_t* t
  *     M == 1 reads no table: the table pointers may be NULL.
  *   out_neg (batch) and the optional out_cands (batch x M ids) have the id type of `users`; out_scores (batch x M floats, optional;
  *   0 for M == 1).  Ids outside their table or CSR set BR_ERRFLAG_RANGE in *err_flag and use row 0.
- *   Limits: 1 <= M <= 32, 1 <= max_tries <= 256, batch < 2^31, n_cand < 2^32; M > 1 needs both tables; BR_ERR_ARG before any launch. */
+ *   Limits: 1 <= M <= 32, 1 <= max_tries <= 256, batch < 2^31, n_cand < 2^32; M > 1 needs both tables; BR_ERR_ARG before any launch.
+ * brNeumfSampleBatch (csrc/sampling_epoch.hip): rows [row0, row0 + batch) of epoch `epoch` of the NeuMF fit, formed per step - the
+ *   per-step form of the site brBootstrapDataset stands in for (src/models/NeuMFModel.py:102-123): every positive once with label 1
+ *   and, per positive, r = neg_per_pos negatives with label 0, drawn again in every epoch and rejected while they are positives of
+ *   the customer.  An epoch has N = n (1 + r) rows; a row is a pure function of (seed, epoch, global row g):
+ *     d = Philox4x32-10(counter (epoch, 0, 7, 0), key seed); seed_e = d.y << 32 | d.x; src = feistel_perm(g, N, perm_key(seed_e, 6)).
+ *     src < n: the row is (pos_users[src], pos_items[src], 1.0f).  Otherwise j = src - n, p = j / r: the user is pos_users[p], the
+ *     label 0.0f and the item the draw of brBprSampleNegatives keyed on j: attempt a < max_tries takes
+ *     d = Philox4x32-10(counter (j, a, 6, epoch), key seed) (streams 6 and 7; 1-5 are taken above); slot = (d.x * n_cand) >> 32; with an
+ *     alias table: if d.y >= alias_thresh[slot] then slot = alias_slot[slot]; id = cand_items ? cand_items[slot] : slot; re-drawn
+ *     while id is a positive of the user and a + 1 < max_tries (the last attempt stands).
+ *   So every positive gets exactly r negatives per epoch, and they depend neither on the epoch's order nor on the batch size or the
+ *   number of ranks (a rank asks for its own slice of the global batch).  pos_users / pos_items (n) and the outputs (batch each) have
+ *   one id type; pos_off (num_users + 1) / pos_sorted_items: the positives' CSR, items ascending.  A user outside the CSR sets
+ *   BR_ERRFLAG_RANGE in *err_flag and is treated as user 0 for the rejection test.  Limits: neg_per_pos >= 0, N < 2^32,
+ *   1 <= max_tries <= 256, n_cand < 2^32, 0 <= row0, row0 + batch <= N; BR_ERR_ARG before any launch; batch == 0 is BR_OK. */
 int brBootstrapDataset(const void* users, const void* items, int id_type, int64_t n, int64_t n_neg, uint64_t seed, void* out_users,
                        void* out_items, float* out_labels, brStream stream);
 int brBprSampleTriplets(const void* users, const void* items, int id_type, int64_t n, int neg_per_pos, const int64_t* pos_off,
@@ -789,6 +804,10 @@ int brBprSampleNegatives(const void* users, int id_type, int64_t batch, int64_t 
                          const float* item_m, const float* item_v, const int32_t* item_last, int64_t item_rows, int dim,
                          const void* step_state, double beta1, double beta2, double eps, void* out_neg, void* out_cands,
                          float* out_scores, int* err_flag, brStream stream);
+int brNeumfSampleBatch(const void* pos_users, const void* pos_items, int id_type, int64_t n, int neg_per_pos, const int64_t* pos_off,
+                       const void* pos_sorted_items, int64_t num_users, const void* cand_items, int64_t n_cand, const uint32_t* alias_thresh,
+                       const int32_t* alias_slot, uint64_t seed, uint32_t epoch, int64_t row0, int64_t batch, int max_tries, void* out_users,
+                       void* out_items, float* out_labels, int* err_flag, brStream stream);
 int brNcfNegativeCandidates(const void* users, const void* items, int id_type, int64_t n, int64_t n_cand, const int64_t* pos_off,
                             const void* pos_items, int64_t num_items, uint64_t seed, uint64_t* keys, brStream stream);
 int64_t brSortUniqueWorkspaceBytes(int64_t n);
