@@ -99,16 +99,59 @@ __device__ __forceinline__ void adam_replay(V& th, V& m, V& v, uint32_t from, ui
   for (uint32_t j = from + 1; j <= upto; ++j) adam_decay(th, m, v, ring[j & (BR_ALPHA_RING - 1)], h);
 }
 
+// ---- what a one-row-per-wave kernel reads from the step state -------------------------------------------------------------------------
+// The step state is the same for every wave of a launch and NOTHING inside a launch that replays rows writes it: the advance (step + 1,
+// the new ring entry) runs in a launch of its own or as an extra workgroup of the chunk-rank launch BEHIND the lookup / gather
+// (neumf_step.cpp defer_advance, LookupArgs::step_add).  So the wave kernels read it through the constant address space: a uniform
+// address there is a scalar load wherever in the program it stands - through the plain pointer every load behind the wave's first store
+// (the out-of-range flag) became a vector load with a full wait of its own, once per replayed row.
+typedef const StepStateDev __attribute__((address_space(4)))* StepStateK;
+__device__ __forceinline__ StepStateK step_state_k(const StepStateDev* ss) { return (StepStateK)ss; }
+
+// the replay's constants, read ONCE at the top of the wave (replay_k), in the same batch of scalar loads as the wave's ids, and handed
+// down: none of the helpers below dereferences ss->step / fast / trunc / sqrt_b2 / eps_c again
+struct ReplayK {
+  uint32_t step, fast, trunc;
+  float sqrt_b2, eps_c;
+};
+__device__ __forceinline__ ReplayK replay_k(const StepStateDev* ss) {
+  const StepStateK k = step_state_k(ss);
+  return ReplayK{k->step, k->fast, k->trunc, k->sqrt_b2, k->eps_c};
+}
+// "these are needed HERE": ONE pin (rows.h) for the five constants and up to two ids, placed behind the wave's id loads.  It keeps the
+// compiler from sinking the loads to their first uses and from consuming one id before it has asked for the other (a wait of its
+// own each): every load is issued, then the wave waits once, for the ids and the constants together.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BR_PIN_K(k) asm volatile("" : "+s"((k).step), "+s"((k).fast), "+s"((k).trunc), "+s"((k).sqrt_b2), "+s"((k).eps_c))
+#define BR_PIN_K1(k, x) asm volatile("" : "+s"((k).step), "+s"((k).fast), "+s"((k).trunc), "+s"((k).sqrt_b2), "+s"((k).eps_c), "+s"(x))
+#define BR_PIN_K2(k, x, y) asm volatile("" : "+s"((k).step), "+s"((k).fast), "+s"((k).trunc), "+s"((k).sqrt_b2), "+s"((k).eps_c), "+s"(x), "+s"(y))
+#else
+#define BR_PIN_K(k) (void)(k)
+#define BR_PIN_K1(k, x) (void)(k), (void)(x)
+#define BR_PIN_K2(k, x, y) (void)(k), (void)(x), (void)(y)
+#endif
+__device__ __forceinline__ void replay_k_pin(ReplayK& k) { BR_PIN_K(k); }
+// the alphas of steps j .. j + 7 in one scalar load (s_load_dwordx8; the ring's mirror makes eight entries from ANY index contiguous).
+// Entries past the row's last step are stale ring contents: loaded, never used.
+struct Alpha8 { float a[8]; };
+__device__ __forceinline__ Alpha8 alpha8(const StepStateDev* ss, uint32_t j) {
+  const float __attribute__((address_space(4)))* rp = step_state_k(ss)->alpha_hist + (j & (BR_ALPHA_RING - 1));
+  Alpha8 r;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) r.a[q] = rp[q];
+  return r;
+}
+
 // the same replay when `from` / `upto` are WAVE-UNIFORM (one row per wave): alpha comes through scalar loads from the ring in global
 // memory, requested one step ahead (no LDS image per workgroup), and a row nobody has touched yet (m == v == 0 in every lane) is
 // skipped by a scalar branch.  No per-lane skip: a lane with m == v == 0 runs theta = fma(-0, 1/eps, theta) = theta, the same bits.
 template <typename V>
-__device__ __forceinline__ void adam_replay_uniform(V& th, V& m, V& v, uint32_t from, uint32_t upto, const StepStateDev* __restrict__ ss,
-                                                    const AdamHp& h) {
+__device__ __forceinline__ void adam_replay_uniform(V& th, V& m, V& v, uint32_t from, uint32_t upto, const StepStateDev* ss, const AdamHp& h) {
   if (__builtin_amdgcn_ballot_w64(!(all_zero(m) && all_zero(v))) == 0) return;
-  float a = ss->alpha_hist[(from + 1) & (BR_ALPHA_RING - 1)];
+  const StepStateK k = step_state_k(ss);
+  float a = k->alpha_hist[(from + 1) & (BR_ALPHA_RING - 1)];
   for (uint32_t j = from + 1; j <= upto; ++j) {
-    const float an = ss->alpha_hist[(j + 1) & (BR_ALPHA_RING - 1)];
+    const float an = k->alpha_hist[(j + 1) & (BR_ALPHA_RING - 1)];
     adam_decay(th, m, v, a, h);
     a = an;
   }
@@ -127,7 +170,8 @@ struct FastRp {
   float c, eps_c;
   uint32_t trunc;
 };
-__device__ __forceinline__ FastRp fast_rp(const StepStateDev* __restrict__ ss) { return FastRp{ss->sqrt_b2, ss->eps_c, ss->trunc}; }
+__device__ __forceinline__ FastRp fast_rp(const StepStateDev* __restrict__ ss) { return FastRp{ss->sqrt_b2, ss->eps_c, ss->trunc}; }   // (row-group kernels)
+__device__ __forceinline__ FastRp fast_rp(const ReplayK& k) { return FastRp{k.sqrt_b2, k.eps_c, k.trunc}; }
 
 __device__ __forceinline__ void fast_open(pk2 v, float eps, pk2& d, pk2& r) {
   d = (pk2){__builtin_amdgcn_sqrtf(v.x), __builtin_amdgcn_sqrtf(v.y)} + eps;
@@ -184,27 +228,38 @@ __device__ __forceinline__ void fast_moments(V& m, V& v, uint32_t lag, const Ste
 }
 
 // fast form of adam_replay_uniform: steps (from, upto] of theta; m, v are left as stored (fast_moments brings them up).  Eight steps'
-// alphas per scalar load (s_load_dwordx8 from the mirrored ring): with one load per step the loop waits for a scalar-cache round trip
-// in every iteration.
-template <typename V>
-__device__ __forceinline__ void adam_replay_fast_uniform(V& th, const V& m, const V& v, uint32_t from, uint32_t upto, const StepStateDev* __restrict__ ss,
-                                                         const AdamHp& h) {
-  if (__builtin_amdgcn_ballot_w64(!(all_zero(m) && all_zero(v))) == 0) return;
-  const FastRp f = fast_rp(ss);
+// alphas per scalar load, and every load is requested AHEAD of its use: `first` = alpha8(ss, from + 1) comes from the caller, who asks
+// for it beside the row's m / v loads (fast_first), group g + 1 is requested before the eight steps of group g run, and the last
+// lag % 8 steps take the leading entries of one more group - the loop never waits for the scalar cache with nothing to do (one load
+// per step put a round trip into every step; one load per group, requested where it is used, one into every group and one into
+// every step of the remainder).  The same st.step(alpha_j, ..) calls in the same order: the same bits.
+__device__ __forceinline__ uint32_t fast_end(uint32_t from, uint32_t upto, const ReplayK& k) {      // last step theta is replayed for
   const uint32_t lag = upto - from;
-  const uint32_t end = from + (lag < f.trunc ? lag : f.trunc);           // last step theta is replayed for
+  return from + (lag < k.trunc ? lag : k.trunc);
+}
+__device__ __forceinline__ Alpha8 fast_first(const StepStateDev* ss, uint32_t from) { return alpha8(ss, from + 1); }
+template <typename V>
+__device__ __forceinline__ void adam_replay_fast_uniform(V& th, const V& m, const V& v, uint32_t from, uint32_t upto, const ReplayK& k, const Alpha8& first,
+                                                         const StepStateDev* ss, const AdamHp& h) {
+  if (__builtin_amdgcn_ballot_w64(!(all_zero(m) && all_zero(v))) == 0) return;
+  const FastRp f = fast_rp(k);
+  const uint32_t end = fast_end(from, upto, k);
   FastSt<V> st;
   st.open(th, m, v, h.eps);
   uint32_t j = from + 1;
+  Alpha8 cur = first;
   for (; j + 7 <= end; j += 8) {
-    const float* __restrict__ rp = ss->alpha_hist + (j & (BR_ALPHA_RING - 1));
-    float a8[8];
+    const Alpha8 nxt = alpha8(ss, j + 8);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) a8[k] = rp[k];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st.step(a8[k], h.b1, f);
+    for (int q = 0; q < 8; ++q) st.step(cur.a[q], h.b1, f);
+    cur = nxt;
   }
-  for (; j <= end; ++j) st.step(ss->alpha_hist[j & (BR_ALPHA_RING - 1)], h.b1, f);
+  const uint32_t rem = end + 1 - j;            // 0 .. 7 live steps, their alphas lead `cur`
+#pragma unroll
+  for (int q = 0; q < 7; ++q) {
+    if ((uint32_t)q >= rem) break;
+    st.step(cur.a[q], h.b1, f);
+  }
   th = st.theta();
 }
 // per-lane form (row-group kernels: several rows with different lags per wave; alphas from the ring image in LDS)
@@ -223,12 +278,59 @@ __device__ __forceinline__ void adam_replay_fast(V& th, const V& m, const V& v, 
 // Replay of steps (from, upto] in the form the step state asks for.  MOMENTS: m and v are brought to step `upto` too (the optimizer
 // and the flush store them; a lookup only needs theta).
 template <bool MOMENTS, typename V>
-__device__ __forceinline__ void adam_catch_up_uniform(V& th, V& m, V& v, uint32_t from, uint32_t upto, const StepStateDev* __restrict__ ss, const AdamHp& h) {
-  if (ss->fast) {
-    adam_replay_fast_uniform(th, m, v, from, upto, ss, h);
+__device__ __forceinline__ void adam_catch_up_uniform(V& th, V& m, V& v, uint32_t from, uint32_t upto, const ReplayK& k, const Alpha8& first,
+                                                      const StepStateDev* ss, const AdamHp& h) {
+  if (k.fast) {
+    adam_replay_fast_uniform(th, m, v, from, upto, k, first, ss, h);
     if (MOMENTS) fast_moments(m, v, upto - from, ss);
   } else {
     adam_replay_uniform(th, m, v, from, upto, ss, h);
+  }
+}
+// The per-call form, for a wave that replays several rows behind work of its own and keeps no ReplayK (the per-step samplers,
+// sampling_step.hip: a replay there runs beside the candidates' row loads, not on a chain of waits): the step state is read where it
+// is used, and the alphas are one scalar load per group of eight steps and one per step of the remainder.  Same st.step / adam_decay
+// calls in the same order as the forms above: the same bits.  Kept apart so that the samplers' code does not move with the lookups'.
+template <typename V>
+__device__ __forceinline__ void adam_replay_uniform_percall(V& th, V& m, V& v, uint32_t from, uint32_t upto, const StepStateDev* __restrict__ ss,
+                                                            const AdamHp& h) {
+  if (__builtin_amdgcn_ballot_w64(!(all_zero(m) && all_zero(v))) == 0) return;
+  float a = ss->alpha_hist[(from + 1) & (BR_ALPHA_RING - 1)];
+  for (uint32_t j = from + 1; j <= upto; ++j) {
+    const float an = ss->alpha_hist[(j + 1) & (BR_ALPHA_RING - 1)];
+    adam_decay(th, m, v, a, h);
+    a = an;
+  }
+}
+template <typename V>
+__device__ __forceinline__ void adam_replay_fast_uniform_percall(V& th, const V& m, const V& v, uint32_t from, uint32_t upto,
+                                                                 const StepStateDev* __restrict__ ss, const AdamHp& h) {
+  if (__builtin_amdgcn_ballot_w64(!(all_zero(m) && all_zero(v))) == 0) return;
+  const FastRp f = fast_rp(ss);
+  const uint32_t lag = upto - from;
+  const uint32_t end = from + (lag < f.trunc ? lag : f.trunc);           // last step theta is replayed for
+  FastSt<V> st;
+  st.open(th, m, v, h.eps);
+  uint32_t j = from + 1;
+  for (; j + 7 <= end; j += 8) {
+    const float* __restrict__ rp = ss->alpha_hist + (j & (BR_ALPHA_RING - 1));
+    float a8[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a8[k] = rp[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) st.step(a8[k], h.b1, f);
+  }
+  for (; j <= end; ++j) st.step(ss->alpha_hist[j & (BR_ALPHA_RING - 1)], h.b1, f);
+  th = st.theta();
+}
+template <bool MOMENTS, typename V>
+__device__ __forceinline__ void adam_catch_up_uniform_percall(V& th, V& m, V& v, uint32_t from, uint32_t upto, const StepStateDev* __restrict__ ss,
+                                                              const AdamHp& h) {
+  if (ss->fast) {
+    adam_replay_fast_uniform_percall(th, m, v, from, upto, ss, h);
+    if (MOMENTS) fast_moments(m, v, upto - from, ss);
+  } else {
+    adam_replay_uniform_percall(th, m, v, from, upto, ss, h);
   }
 }
 template <bool MOMENTS, typename V>

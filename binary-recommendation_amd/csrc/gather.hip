@@ -256,16 +256,20 @@ __global__ __launch_bounds__(256) void gather_rows_deferred_wave_kernel(
   const int64_t b = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (b >= n) return;
   const int lane = (int)(threadIdx.x & 63);
+  ReplayK k = replay_k(ss);                           // the step state once per wave, in one batch of scalar loads with the id
   int64_t r = load_id(ids, b);
+  BR_PIN_K1(k, r);
   const bool ok = (uint64_t)r < (uint64_t)rows;
-  if (!ok) { if (err && lane == 0) *err = 1; r = 0; }
-  const uint32_t t = ss->step, seen = (uint32_t)last[r];
+  if (!ok) r = 0;
+  const uint32_t t = k.step, seen = (uint32_t)last[r];
   const int64_t off = r * dim + lane * VEC;
   V th = vload<VEC>(table + off);
   if (seen + 1 < t) {
     V m = vload<VEC>(M + off), v = vload<VEC>(Vv + off);
-    adam_catch_up_uniform<false>(th, m, v, seen, t - 1, ss, h);
+    const Alpha8 first = fast_first(ss, seen);        // beside m / v
+    adam_catch_up_uniform<false>(th, m, v, seen, t - 1, k, first, ss, h);
   }
+  flag_range(err, ok, lane == 0);                     // behind the loads (lookup_wave.h)
   vstore<VEC>(out + b * ld_out + lane * VEC, ok ? th : vzero<VEC>());
 }
 

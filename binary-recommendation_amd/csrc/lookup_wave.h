@@ -22,11 +22,42 @@ struct LookupArgs {
   uint32_t spec = 0;
 };
 // which streams of the deferred lookup load m / v speculatively: BR_LOOKUP_SPEC = 0 (default) | 1 (users) | 2 (items) | 3 (both).  Measured at
-// config 2 (94 % of the user rows lag): 69-70 us with and without - like two pairs per wave (BR_LOOKUP_PAIRS=2), it does not move the launch:
-// neither the dependent round trips nor the bytes in flight per wave bound it.
+// config 2 (94 % of the user rows lag): 69-70 us with and without, like two pairs per wave (BR_LOOKUP_PAIRS=2).  Both experiments were run
+// while a pair still waited about fifteen times (the step state and the alphas fetched per row and per group, see LOOKUP WAITS below):
+// the first removed one of those waits, the second doubled the per-row ones along with the bytes, so they say little about what
+// bounds the launch.
+//
+// LOOKUP WAITS.  Every form below reads the step state once per wave (adam_math.h ReplayK) in the batch of scalar loads that fetches
+// its ids, raises the out-of-range flag BEHIND its loads (a store in front of them turns every later uniform load into a vector load
+// with a full wait), and requests each row's first eight alphas beside the row's m / v.  What a pair then waits for: ids + step state;
+// last[] of both rows; theta, m, v and the first alphas; and inside a replay loop the next group's alphas, requested eight steps earlier.
+// (gather_deferred_group4 is the exception: four rows' alpha groups are 32 SGPRs, a second set in flight costs the fused gather + sort
+// launch a workgroup per CU, and the rest of the treatment alone measured no gain on the BPR step - it keeps the parent's form, see there.)
+// Measured at config 2 (profiles/lookup_chain/): the fused lookup + sort launch 66.2 -> 58.2 us, the step 0.311-0.313 -> 0.300 ms, same bits.
 static inline uint32_t lookup_spec(int64_t, int64_t, int64_t) {
   static const int forced = [] { const char* e = getenv("BR_LOOKUP_SPEC"); return e ? atoi(e) : 0; }();
   return (uint32_t)forced & 3u;
+}
+
+// the step state's constants and both ids of pair b in ONE batch of scalar loads with one wait (BR_PIN_K2), branch-free (load_id
+// branches on the id pointer: two calls are two branches, each load with a wait of its own): a null id array (ids = positions) reads
+// the step state's first bytes instead and drops the value.  Through the constant address space, like the step state (adam_math.h
+// StepStateK): the launch only reads its ids, and the loads stay scalar.  The dummy read is sizeof(IdT) <= 8 bytes AT ss: it relies on the
+// step state being a live allocation of at least 8 bytes aligned to 8 (StepStateDev is far larger, and it is a device allocation of its own, aligned to 256 B or more).
+template <typename IdT>
+__device__ __forceinline__ ReplayK load_k_id_pair(const StepStateDev* ss, const IdT* users, const IdT* items, int64_t b, int64_t& u, int64_t& i) {
+  typedef const IdT __attribute__((address_space(4)))* IdK;
+  ReplayK k = replay_k(ss);
+  IdT uu = *(users ? (IdK)users + b : (IdK)ss), ii = *(items ? (IdK)items + b : (IdK)ss);
+  BR_PIN_K2(k, uu, ii);
+  u = users ? (int64_t)uu : b;
+  i = items ? (int64_t)ii : b;
+  return k;
+}
+// an id outside its table: OR the range bit into the step's error flag (a capacity bit raised earlier stays).  Called BEHIND the
+// wave's loads.
+__device__ __forceinline__ void flag_range(int* err, bool ok, bool writer) {
+  if (!ok && err && writer) atomicOr(err, BR_ERRFLAG_RANGE);
 }
 
 // pair b (wave-uniform) of embed_dim = 32 * VEC: a lane owns VEC columns of the fused user row and the same columns of the item row
@@ -36,22 +67,24 @@ __device__ __forceinline__ void lookup_wave_pair(const LookupArgs& a, int64_t b,
   constexpr int dim = 32 * VEC;
   constexpr int64_t ld = 2 * dim;
   const float* __restrict__ user_tab = a.user_tab; const float* __restrict__ item_tab = a.item_tab;
-  const StepStateDev* __restrict__ ss = a.ss;
+  const StepStateDev* ss = a.ss;
   const int col = lane * VEC;                         // column of the fused row: [0, dim) MLP, [dim, 2 dim) MF
-  int64_t u = load_id((const IdT*)a.users, b), i = load_id((const IdT*)a.items, b);
+  int64_t u, i;
+  const ReplayK k = load_k_id_pair(ss, (const IdT*)a.users, (const IdT*)a.items, b, u, i);
   const bool uok = (uint64_t)u < (uint64_t)a.user_rows, iok = (uint64_t)i < (uint64_t)a.item_rows;
-  if ((!uok || !iok) && a.err && lane == 0) *a.err = 1;
   if (!uok) u = 0;
   if (!iok) i = 0;
-  const uint32_t t = ss->step + a.step_add;           // the step being computed: rows must include steps <= t-1
+  const uint32_t t = k.step + a.step_add;             // the step being computed: rows must include steps <= t-1
   const uint32_t lu = (uint32_t)a.user_last[u], li = (uint32_t)a.item_last[i];
   const int64_t uo = u * ld + col, io = i * ld + col;
   V ur = vload<VEC>(user_tab + uo), ir = vload<VEC>(item_tab + io);
   V um = vzero<VEC>(), uv = vzero<VEC>(), im = vzero<VEC>(), iv = vzero<VEC>();
   if ((a.spec & 1u) || lu + 1 < t) { um = vload<VEC>(a.user_m + uo); uv = vload<VEC>(a.user_v + uo); }
   if ((a.spec & 2u) || li + 1 < t) { im = vload<VEC>(a.item_m + io); iv = vload<VEC>(a.item_v + io); }
-  if (li + 1 < t) adam_catch_up_uniform<false>(ir, im, iv, li, t - 1, ss, a.h);
-  if (lu + 1 < t) adam_catch_up_uniform<false>(ur, um, uv, lu, t - 1, ss, a.h);
+  const Alpha8 ia = fast_first(ss, li), ua = fast_first(ss, lu);      // beside m / v: there when the rows arrive
+  if (li + 1 < t) adam_catch_up_uniform<false>(ir, im, iv, li, t - 1, k, ia, ss, a.h);
+  if (lu + 1 < t) adam_catch_up_uniform<false>(ur, um, uv, lu, t - 1, k, ua, ss, a.h);
+  flag_range(a.err, uok && iok, lane == 0);
   if (!uok) ur = vzero<VEC>();
   if (!iok) ir = vzero<VEC>();
   const bool mlp = lane < 32;
@@ -87,22 +120,23 @@ template <typename IdT>
 __device__ __forceinline__ void lookup_half_pair(const LookupArgs& a, int64_t b, int lane) {
   constexpr int dim = 64;
   constexpr int64_t ld = 2 * dim;
-  const StepStateDev* __restrict__ ss = a.ss;
+  const StepStateDev* ss = a.ss;
   const bool it = lane >= 32;                          // this lane's row: the item's
   const int col = (lane & 31) * 4;                     // column of the fused row: [0, dim) MLP, [dim, 2 dim) MF
-  int64_t u = load_id((const IdT*)a.users, b), i = load_id((const IdT*)a.items, b);
+  int64_t u, i;
+  const ReplayK rk = load_k_id_pair(ss, (const IdT*)a.users, (const IdT*)a.items, b, u, i);
   const bool uok = (uint64_t)u < (uint64_t)a.user_rows, iok = (uint64_t)i < (uint64_t)a.item_rows;
-  if ((!uok || !iok) && a.err && lane == 0) *a.err = 1;
   if (!uok) u = 0;
   if (!iok) i = 0;
-  const uint32_t t = ss->step + a.step_add;
+  const uint32_t t = rk.step + a.step_add;
   const uint32_t lu = (uint32_t)a.user_last[u], li = (uint32_t)a.item_last[i];
-  const FastRp f = fast_rp(ss);
+  const FastRp f = fast_rp(rk);
   uint32_t lag_u = lu + 1 < t ? t - 1 - lu : 0u, lag_i = li + 1 < t ? t - 1 - li : 0u;
   const int64_t off = (it ? i : u) * ld + col;
   const float4 th = vload<4>((it ? a.item_tab : a.user_tab) + off);
   float4 m = vzero<4>(), v = vzero<4>();
   if (it ? lag_i > 0 : lag_u > 0) { m = vload<4>((it ? a.item_m : a.user_m) + off); v = vload<4>((it ? a.item_v : a.user_v) + off); }
+  Alpha8 au = fast_first(ss, lu), ai = fast_first(ss, li);      // beside m / v: there when the rows arrive
   float4 out = th;
   lag_u = lag_u < f.trunc ? lag_u : f.trunc; lag_i = lag_i < f.trunc ? lag_i : f.trunc;      // theta is replayed over min(lag, trunc) steps
   const uint32_t steps = lag_u > lag_i ? lag_u : lag_i, mine = it ? lag_i : lag_u;
@@ -110,21 +144,20 @@ __device__ __forceinline__ void lookup_half_pair(const LookupArgs& a, int64_t b,
     FastSt<float4> st;
     st.open(th, m, v, a.h.eps);
     uint32_t k = 1;
-    for (; k + 7 <= steps; k += 8) {      // eight alphas of each row per scalar load (the ring's first eight entries are mirrored behind its end)
-      const float* __restrict__ ru = ss->alpha_hist + ((lu + k) & (BR_ALPHA_RING - 1));
-      const float* __restrict__ ri = ss->alpha_hist + ((li + k) & (BR_ALPHA_RING - 1));
-      float au[8], ai[8];
+    for (; k + 7 <= steps; k += 8) {      // eight alphas of each row per scalar load, the next group requested before this one's steps
+      const Alpha8 nu = alpha8(ss, lu + k + 8), ni = alpha8(ss, li + k + 8);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) { au[q] = ru[q]; ai[q] = ri[q]; }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) st.step(k + q <= mine ? (it ? ai[q] : au[q]) : 0.f, a.h.b1, f);
+      for (int q = 0; q < 8; ++q) st.step(k + q <= mine ? (it ? ai.a[q] : au.a[q]) : 0.f, a.h.b1, f);
+      au = nu; ai = ni;
     }
-    for (; k <= steps; ++k) {
-      const float au = ss->alpha_hist[(lu + k) & (BR_ALPHA_RING - 1)], ai = ss->alpha_hist[(li + k) & (BR_ALPHA_RING - 1)];
-      st.step(k <= mine ? (it ? ai : au) : 0.f, a.h.b1, f);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {         // the last steps % 8 steps: their alphas lead the group already here
+      if (k + q > steps) break;
+      st.step(k + q <= mine ? (it ? ai.a[q] : au.a[q]) : 0.f, a.h.b1, f);
     }
     out = st.theta();
   }
+  flag_range(a.err, uok && iok, lane == 0);
   if (it ? !iok : !uok) out = vzero<4>();
   const bool mlp = col < dim;
   const int uoff = a.item_first ? dim : 0, ioff = a.item_first ? 0 : dim;
@@ -149,22 +182,33 @@ __device__ __forceinline__ void lookup_wave_pairs(const LookupArgs& a, int64_t b
   constexpr int dim = 32 * VEC;
   constexpr int64_t ld = 2 * dim;
   const float* __restrict__ user_tab = a.user_tab; const float* __restrict__ item_tab = a.item_tab;
-  const StepStateDev* __restrict__ ss = a.ss;
+  const StepStateDev* ss = a.ss;
   const int col = lane * VEC;
-  const uint32_t t = ss->step + a.step_add;
+  ReplayK k = replay_k(ss);
   int64_t u[R], i[R], bq[R];
   bool live[R], uok[R], iok[R];
 #pragma unroll
   for (int q = 0; q < R; ++q) {
     live[q] = b0 + q < a.batch;
     bq[q] = live[q] ? b0 + q : a.batch - 1;
-    u[q] = load_id((const IdT*)a.users, bq[q]); i[q] = load_id((const IdT*)a.items, bq[q]);
   }
+  {      // every id and the constants: one batch of loads, one wait
+    typedef const IdT __attribute__((address_space(4)))* IdK;
+    IdT uu[R], ii[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) { uu[q] = *(a.users ? (IdK)a.users + bq[q] : (IdK)ss); ii[q] = *(a.items ? (IdK)a.items + bq[q] : (IdK)ss); }
+#pragma unroll
+    for (int q = 0; q < R; ++q) { BR_PIN_K2(k, uu[q], ii[q]); }
+#pragma unroll
+    for (int q = 0; q < R; ++q) { u[q] = a.users ? (int64_t)uu[q] : bq[q]; i[q] = a.items ? (int64_t)ii[q] : bq[q]; }
+  }
+  const uint32_t t = k.step + a.step_add;
   uint32_t lu[R], li[R];
+  bool all_ok = true;
 #pragma unroll
   for (int q = 0; q < R; ++q) {
     uok[q] = (uint64_t)u[q] < (uint64_t)a.user_rows; iok[q] = (uint64_t)i[q] < (uint64_t)a.item_rows;
-    if ((!uok[q] || !iok[q]) && a.err && lane == 0 && live[q]) *a.err = 1;
+    all_ok = all_ok && ((uok[q] && iok[q]) || !live[q]);
     if (!uok[q]) u[q] = 0;
     if (!iok[q]) i[q] = 0;
     lu[q] = (uint32_t)a.user_last[u[q]]; li[q] = (uint32_t)a.item_last[i[q]];
@@ -180,10 +224,13 @@ __device__ __forceinline__ void lookup_wave_pairs(const LookupArgs& a, int64_t b
   }
   const bool mlp = lane < 32;
   const int uoff = a.item_first ? dim : 0, ioff = a.item_first ? 0 : dim;
+  Alpha8 ia = fast_first(ss, li[0]), ua = fast_first(ss, lu[0]);      // beside the row loads; the next pair's before this pair's replay
 #pragma unroll
   for (int q = 0; q < R; ++q) {
-    if (li[q] + 1 < t) adam_catch_up_uniform<false>(ir[q], im[q], iv[q], li[q], t - 1, ss, a.h);
-    if (lu[q] + 1 < t) adam_catch_up_uniform<false>(ur[q], um[q], uv[q], lu[q], t - 1, ss, a.h);
+    const Alpha8 ic = ia, uc = ua;
+    if (q + 1 < R) { ia = fast_first(ss, li[q + 1]); ua = fast_first(ss, lu[q + 1]); }
+    if (li[q] + 1 < t) adam_catch_up_uniform<false>(ir[q], im[q], iv[q], li[q], t - 1, k, ic, ss, a.h);
+    if (lu[q] + 1 < t) adam_catch_up_uniform<false>(ur[q], um[q], uv[q], lu[q], t - 1, k, uc, ss, a.h);
     if (!uok[q]) ur[q] = vzero<VEC>();
     if (!iok[q]) ir[q] = vzero<VEC>();
     if (!live[q]) continue;
@@ -207,6 +254,7 @@ __device__ __forceinline__ void lookup_wave_pairs(const LookupArgs& a, int64_t b
     if constexpr (VEC == 4) s += __shfl_xor(s, 1, 64);
     if (lane == 63) a.dot[b] = s;
   }
+  flag_range(a.err, all_ok, lane == 0);
 }
 
 // one row of a deferred table by one wave (rows of 64 * VEC floats): out[p] = row ids[p] as of step - 1, p = the physical position of
@@ -218,21 +266,25 @@ struct GatherDefJobs {
   uint32_t step_add = 0;      // 1: the step state is advanced BEHIND this launch (by the chunk-rank launch): the step being computed is ss->step + 1
 };
 template <typename IdT, int VEC>
-__device__ __forceinline__ void gather_deferred_wave_row(const GatherDefJobs& jobs, const GatherDefJob& jb, int64_t b, int lane, const StepStateDev* __restrict__ ss,
+__device__ __forceinline__ void gather_deferred_wave_row(const GatherDefJobs& jobs, const GatherDefJob& jb, int64_t b, int lane, const StepStateDev* ss,
                                                          const AdamHp& h, int64_t ld_out, int* err) {
   using V = typename VecT<VEC>::type;
   constexpr int dim = 64 * VEC;
   b = seg_phys(b, jobs.seg_len, jobs.seg_stride, jb.seg_off);
+  ReplayK k = replay_k(ss);                           // one batch of scalar loads with the id, one wait
   int64_t r = load_id((const IdT*)jb.ids, b);
+  BR_PIN_K1(k, r);
   const bool ok = (uint64_t)r < (uint64_t)jb.rows;
-  if (!ok) { if (err && lane == 0) *err = 1; r = 0; }
-  const uint32_t t = ss->step + jobs.step_add, seen = (uint32_t)jb.last[r];
+  if (!ok) r = 0;
+  const uint32_t t = k.step + jobs.step_add, seen = (uint32_t)jb.last[r];
   const int64_t off = r * dim + lane * VEC;
   V th = vload<VEC>(jb.table + off);
   if (seen + 1 < t) {
     V m = vload<VEC>(jb.M + off), v = vload<VEC>(jb.Vv + off);
-    adam_catch_up_uniform<false>(th, m, v, seen, t - 1, ss, h);
+    const Alpha8 first = fast_first(ss, seen);        // beside m / v
+    adam_catch_up_uniform<false>(th, m, v, seen, t - 1, k, first, ss, h);
   }
+  flag_range(err, ok, lane == 0);
   vstore<VEC>(jb.out + b * ld_out + lane * VEC, ok ? th : vzero<VEC>());
 }
 
@@ -241,12 +293,12 @@ __device__ __forceinline__ void gather_deferred_wave_row(const GatherDefJobs& jo
 // of what the CU's share of HBM needs (the BPR gather ran at 0.48 of its memory time); control flow stays scalar per row (a wave replays
 // one row at a time).  Rows [0, n_a) belong to job 0, the rest to job 1; rows past the end are skipped.
 template <typename IdT, int VEC, int R>
-__device__ __forceinline__ void gather_deferred_wave_rows(const GatherDefJobs& jobs, int64_t b0, int lane, const StepStateDev* __restrict__ ss, const AdamHp& h,
+__device__ __forceinline__ void gather_deferred_wave_rows(const GatherDefJobs& jobs, int64_t b0, int lane, const StepStateDev* ss, const AdamHp& h,
                                                           int64_t ld_out, int* err) {
   using V = typename VecT<VEC>::type;
   constexpr int dim = 64 * VEC;
   const int64_t n_a = jobs.j[0].n, n_all = n_a + jobs.j[1].n;
-  const uint32_t t = ss->step + jobs.step_add;
+  ReplayK k = replay_k(ss);
   int which[R];
   int64_t pos[R], row[R];
   bool live[R], ok[R];
@@ -260,12 +312,16 @@ __device__ __forceinline__ void gather_deferred_wave_rows(const GatherDefJobs& j
     pos[q] = seg_phys(which[q] ? bc - n_a : bc, jobs.seg_len, jobs.seg_stride, jb.seg_off);
     row[q] = load_id((const IdT*)jb.ids, pos[q]);
   }
+  replay_k_pin(k);
+  const uint32_t t = k.step + jobs.step_add;
   uint32_t seen[R];
+  bool all_ok = true;
 #pragma unroll
   for (int q = 0; q < R; ++q) {
     const GatherDefJob& jb = jobs.j[which[q]];
     ok[q] = (uint64_t)row[q] < (uint64_t)jb.rows;
-    if (!ok[q]) { if (err && lane == 0 && live[q]) *err = 1; row[q] = 0; }
+    all_ok = all_ok && (ok[q] || !live[q]);
+    if (!ok[q]) row[q] = 0;
     seen[q] = (uint32_t)jb.last[row[q]];
   }
   V th[R], m[R], v[R];
@@ -277,11 +333,15 @@ __device__ __forceinline__ void gather_deferred_wave_rows(const GatherDefJobs& j
     m[q] = vzero<VEC>(); v[q] = vzero<VEC>();
     if (seen[q] + 1 < t) { m[q] = vload<VEC>(jb.M + off); v[q] = vload<VEC>(jb.Vv + off); }
   }
+  Alpha8 first = fast_first(ss, seen[0]);              // beside the row loads; the next row's before this row's replay
 #pragma unroll
   for (int q = 0; q < R; ++q) {
-    if (seen[q] + 1 < t) adam_catch_up_uniform<false>(th[q], m[q], v[q], seen[q], t - 1, ss, h);
+    const Alpha8 cur = first;
+    if (q + 1 < R) first = fast_first(ss, seen[q + 1]);
+    if (seen[q] + 1 < t) adam_catch_up_uniform<false>(th[q], m[q], v[q], seen[q], t - 1, k, cur, ss, h);
     if (live[q]) vstore<VEC>(jobs.j[which[q]].out + pos[q] * ld_out + lane * VEC, ok[q] ? th[q] : vzero<VEC>());
   }
+  flag_range(err, all_ok, lane == 0);
 }
 
 // 256-B rows (64 floats), fast replay: FOUR rows per wave side by side - lane group q = lane >> 4 holds row q, 16 B per lane - so theta,
@@ -290,6 +350,11 @@ __device__ __forceinline__ void gather_deferred_wave_rows(const GatherDefJobs& j
 // run together over max(lag) iterations; each group takes ITS alpha (ring index last + k: the four `last` values are read back as scalars,
 // four s_load_dwordx8 per eight steps) and alpha = 0 once its lag is used up, which leaves theta as it is.  Per element the operations of
 // the one-wave-per-row form in the same order: same bits.
+// NOT given the ReplayK / alphas-ahead treatment of the forms above (LOOKUP WAITS); only its range flag became an atomicOr.  Four rows'
+// alpha groups are 32 SGPRs: with a second set in flight gather_sort_kernel<IdT,1> went from 91 to 106 SGPRs, 8 to 7 waves per SIMD, and
+// since its 1024-thread workgroups take four waves per SIMD each, from two workgroups per CU to one.  With the alphas requested where
+// they are used but the step state from ReplayK and the last lag % 8 steps from one eight-wide load per row (99 SGPRs, 8 waves) the BPR
+// step at 64 factors measured 0.1730-0.1737 ms against the parent's 0.1719-0.1731, alternated three times: no gain, so the parent's text.
 template <typename IdT>
 __device__ __forceinline__ void gather_deferred_group4(const GatherDefJobs& jobs, int64_t b0, int lane, const StepStateDev* __restrict__ ss, const AdamHp& h,
                                                        int64_t ld_out, int* err) {
@@ -307,7 +372,7 @@ __device__ __forceinline__ void gather_deferred_group4(const GatherDefJobs& jobs
   int64_t row = which ? load_id((const IdT*)jb.ids, pos) : load_id((const IdT*)ja.ids, pos);
   const int64_t rows = which ? jb.rows : ja.rows;
   const bool ok = (uint64_t)row < (uint64_t)rows;
-  if (!ok) { if (err && live && (lane & 15) == 0) *err = 1; row = 0; }
+  if (!ok) { if (err && live && (lane & 15) == 0) atomicOr(err, BR_ERRFLAG_RANGE); row = 0; }
   const uint32_t seen = (uint32_t)(which ? jb.last : ja.last)[row];
   const FastRp f = fast_rp(ss);
   uint32_t lag = seen + 1 < t ? t - 1 - seen : 0u;

@@ -129,7 +129,8 @@ __global__ __launch_bounds__(kThreadsL, 8) void lookup_sort_kernel(const LookupA
 // form of the fused lookup at embed_dim 64: BR_LOOKUP_PAIRS = 1 (default: one pair per wave, lookup_wave_pair) | 2 (two pairs per wave) |
 // 0 (lookup_half_pair: both rows of the pair side by side, 16 B per lane).  Measured at config 2, same bits in all three: 68-69 us | 70.5 us |
 // 86-88 us - the half-wave form halves the load instructions but replays four elements per lane over max(lag_u, lag_i) steps with a
-// per-lane alpha select: the launch follows its VALU work, not its instruction count.
+// per-lane alpha select.  (Taken while every form still fetched the step state per row and the alphas per group where they were used,
+// lookup_wave.h LOOKUP WAITS: they rank the three forms, they do not show what bounds the launch.)
 static int lookup_pairs_per_wave() {
   static const int r = [] { const char* e = getenv("BR_LOOKUP_PAIRS"); const int v = e ? atoi(e) : 1; return (v == 0 || v == 2) ? v : 1; }();
   return r;
@@ -406,7 +407,12 @@ extern "C" int brRowIndexMergePairSeg(const void* ids_a, int64_t upper_a, void* 
 // lookup's shapes, the large-chunk sort's range, BR_FUSED_SORT != 0.
 bool br::lookup_with_index_supported(int dim, int64_t n, int64_t upper_a, int64_t upper_b, int64_t ld_stash, const void* x0, const void* stash_a,
                                      const void* stash_b) {
-  static const bool on = [] { const char* e = getenv("BR_FUSED_SORT"); return !(e && e[0] == '0'); }();
+  // DELIBERATELY not cached in a static, unlike BR_LOOKUP_PAIRS, BR_LOOKUP_SPEC and BR_GATHER_GROUP4: it is read on every call (eager steps
+  // and captures only: a replayed graph does not come here), so that one process can run the same engine both ways
+  // (tests/test_gpu_lookup_chain.py, as tests/test_gpu_twotower_bpr.py does with the BPR step).  A change of the variable takes effect at
+  // the next eager step or capture.
+  const char* e = getenv("BR_FUSED_SORT");
+  const bool on = !(e && e[0] == '0');
   const int wvec = wave_pair_vec(dim);      // (units of 32 floats: a lane owns the same columns of the user row and the item row)
   return on && wave_rows_enabled() && wvec && ld_stash % wvec == 0 &&
          ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(stash_a) | reinterpret_cast<uintptr_t>(stash_b)) & (4 * wvec - 1)) == 0 &&

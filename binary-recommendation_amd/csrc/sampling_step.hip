@@ -151,10 +151,10 @@ __global__ __launch_bounds__(256) void bpr_sample_hard_kernel(const SampleArgs a
         if (seen[q] < done && in) { m[q] = vload<VEC>(a.item.m + off); v[q] = vload<VEC>(a.item.v + off); }
       }
       // the customer's row (its chunk) is replayed behind the group's requests: they are in flight meanwhile
-      if (u_lag && (CHUNKED || g == 0)) adam_catch_up_uniform<false>(ur, um, uv, u_seen, done, ss, a.h);
+      if (u_lag && (CHUNKED || g == 0)) adam_catch_up_uniform_percall<false>(ur, um, uv, u_seen, done, ss, a.h);
 #pragma unroll
       for (int q = 0; q < R; ++q) {
-        if (seen[q] < done) adam_catch_up_uniform<false>(th[q], m[q], v[q], seen[q], done, ss, a.h);
+        if (seen[q] < done) adam_catch_up_uniform_percall<false>(th[q], m[q], v[q], seen[q], done, ss, a.h);
         acc[q] = fma_chain(acc[q], ur, th[q]);
       }
     }
