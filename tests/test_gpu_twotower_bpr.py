@@ -44,25 +44,26 @@ def test_inbatch_softmax_kernels(dev, Bq, dim):
 @pytest.mark.parametrize("Bq,Bc,dim,idt", [(1, 1, 1, torch.int32), (3, 130, 7, torch.int64), (129, 63, 33, torch.int32), (260, 2, 100, torch.int32),
                                            (1, 700, 128, torch.int64), (513, 257, 104, torch.int32), (64, 64, 57, torch.int32)])
 @pytest.mark.parametrize("with_ws", [True, False])
-def test_inbatch_softmax_ragged_shapes_and_workspace(dev, Bq, Bc, dim, idt, with_ws):
+def test_inbatch_softmax_ragged_shapes_and_workspace(dev, Bq, Bc, dim, idt, with_ws, diag_offset=0):
     """rectangular / ragged (rows not multiples of 128 / 64, features not multiples of 4 / 8 / 32, one row, one column), int64 ids,
     a diagonal that leaves the matrix for some queries, with the split workspace and through the C-ABI without one (ws = NULL:
     one workgroup per 128 rows writes its results directly); no ids = no accidental-hit mask."""
     ops, lib = _m("ops"), _m("_lib").load()
     rng = np.random.default_rng(Bq * 1000 + Bc + dim)
     q = rng.normal(0, 0.5, (Bq, dim)).astype(np.float32); c = rng.normal(0, 0.5, (Bc, dim)).astype(np.float32)
-    off = 0 if Bq <= Bc else 0                               # query i's positive is candidate i (+ off); queries past Bc have none
-    cid = rng.integers(0, 9, Bc); qid = np.where(np.arange(Bq) < Bc, cid[np.minimum(np.arange(Bq), Bc - 1)], rng.integers(0, 9, Bq))
+    off = diag_offset                                        # query i's positive is candidate i + off; queries whose i + off leaves [0, Bc) have none
+    pj = np.arange(Bq) + off
+    cid = rng.integers(0, 9, Bc); qid = np.where((pj >= 0) & (pj < Bc), cid[np.clip(pj, 0, Bc - 1)], rng.integers(0, 9, Bq))
     td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     qd, cd, qi, ci = td(q), td(c), td(qid).to(idt), td(cid).to(idt)
     # float64 reference with the same rule: S_ij += float32.min / 100 where cand id == query's id and j is not the diagonal
     S = q.astype(np.float64) @ c.astype(np.float64).T
-    diag = np.zeros((Bq, Bc), bool); ii = np.arange(Bq); ok = ii + off < Bc; diag[ii[ok], ii[ok] + off] = True
+    diag = np.zeros((Bq, Bc), bool); ii = np.arange(Bq); ok = (ii + off >= 0) & (ii + off < Bc); diag[ii[ok], ii[ok] + off] = True
     S = S + np.where((qid[:, None] == cid[None, :]) & ~diag, float(np.finfo(np.float32).min) / 100, 0.0)
     m = S.max(1, keepdims=True); lse_ref = (m + np.log(np.exp(S - m).sum(1, keepdims=True)))[:, 0]
     P = np.exp(S - lse_ref[:, None]) - diag
     rdq, rdc = P @ c.astype(np.float64), P.T @ q.astype(np.float64)
-    loss_ref = float((lse_ref - np.where(ok, S[ii, np.minimum(ii + off, Bc - 1)], 0.0)).sum())
+    loss_ref = float((lse_ref - np.where(ok, S[ii, np.clip(ii + off, 0, Bc - 1)], 0.0)).sum())
     lse = torch.empty(Bq, device=dev); ls = torch.zeros(64, dtype=torch.float64, device=dev)
     dq, dc = torch.full((Bq, dim), 7.0, device=dev), torch.full((Bc, dim), 7.0, device=dev)
     if with_ws:
@@ -91,6 +92,16 @@ def test_inbatch_softmax_ragged_shapes_and_workspace(dev, Bq, Bc, dim, idt, with
     np.testing.assert_allclose(lse2.cpu().numpy(), lse_ref, rtol=1e-5, atol=1e-5)
     assert abs(ls2.sum().item() - loss_ref) <= 1e-5 * max(1.0, abs(loss_ref))
     np.testing.assert_allclose(dq2.cpu().numpy(), rdq, rtol=1e-4, atol=1e-5 * max(1e-3, np.abs(rdq).max()))
+
+
+@pytest.mark.parametrize("Bq,Bc,dim,idt", [(1, 1, 1, torch.int32), (3, 130, 7, torch.int64), (129, 63, 33, torch.int32), (260, 2, 100, torch.int32),
+                                           (1, 700, 128, torch.int64), (513, 257, 104, torch.int32), (64, 64, 57, torch.int32)])
+@pytest.mark.parametrize("with_ws", [True, False])
+@pytest.mark.parametrize("diag_offset", [5, -3])
+def test_inbatch_softmax_ragged_shapes_diag_offset(dev, Bq, Bc, dim, idt, with_ws, diag_offset):
+    """the same shapes and assertions with the diagonal moved: the partner of query i is candidate i + diag_offset, the queries at either
+    end have none (the 0 case is the test above)"""
+    test_inbatch_softmax_ragged_shapes_and_workspace(dev, Bq, Bc, dim, idt, with_ws, diag_offset)
 
 
 def test_inbatch_softmax_sharded_columns(dev):
