@@ -1,12 +1,12 @@
-// The catalogue pass of the dot-product AUC with its two CSRs in two separate roles, for the owner-side count of a row-sharded engine
-// (auc_owner.hip).  The two passes are dot_auc_kernel's and dot_auc_wide_kernel's bodies (auc_dot.hip), statement for statement, kept the
-// same by hand as those two are among themselves (DESIGN.md 4e "One copy of the tile loop", 4i), except that
-//   - (off, idx) is only what the cursor and the window mask skip: this owner's positives, ascending LOCAL positions into C;
+// The catalogue pass of the dot-product AUC, written twice: dot_auc_pass for whole rows (dim <= 128) and dot_auc_wide_pass for 128-feature
+// blocks (dim <= 512).  Both serve the single-device kernels (auc_dot.hip) and the owner-side count of a row-sharded engine
+// (auc_owner.hip); the two widths are copies of each other behind the scores, kept the same by hand, as their tile streams are copies of
+// the top-k and rank kernels' (DESIGN.md 4e "One copy of the tile loop", 4i).  A pass has its two CSRs in two separate roles:
+//   - (off, idx) is only what the cursor (dot_tile.h RowCursor) and the window mask skip: on an owner its own positives, ascending LOCAL
+//     positions into C;
 //   - loff says where a user's sorted list lies in `sorted` (loff[u], pcnt[u] entries): ALL the user's positives, of every owner.
-// With loff == off they are the single-device kernels.  Those keep their own text: as wrappers of these bodies they compile to the same
-// register, LDS and occupancy budgets (profiles/recommend/auc_one_body_resources.json) but not to the same instructions, and the
-// alternating measurement that has to decide it has not been taken yet.  The kernels own the LDS arrays (tile, pos_s,
-// xm_s) and hand them in.  Here too, once for every kernel that runs a pass: the tile shape, the LDS cap and the split plan.
+// The single-device kernels pass loff = off: the truth CSR in both roles.  The kernels own the LDS arrays (tile, pos_s, xm_s) and hand
+// them in.  Here too, once for every kernel that runs a pass: the tile shape, the LDS cap and the split plan.
 #pragma once
 #include <math.h>
 
@@ -91,18 +91,9 @@ __device__ __forceinline__ void dot_auc_pass(const float* __restrict__ Q, int64_
   int step0 = 0;                                                      // highest power of two <= top (wave-uniform)
   if (top > 0) step0 = 1 << (31 - __builtin_clz((unsigned)top));
 
-  // truth cursor of user u0 + lane: the first entry of its list at or after p0, and that entry's position
-  int64_t ex_cur = 0, ex_end = 0, ex_nxt = INT64_MAX;
-  if (lane < UW && u0 + lane < n_users) {
-    int64_t lo = off[u0 + lane], hi = off[u0 + lane + 1];
-    ex_end = hi;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)idx[mid] < p0) lo = mid + 1; else hi = mid;
-    }
-    ex_cur = lo;
-    if (ex_cur < ex_end) ex_nxt = idx[ex_cur];
-  }
+  // skip cursor of user u0 + lane: the first entry of its (off, idx) row at or after p0, and that entry's position
+  RowCursor xc;
+  if (lane < UW && u0 + lane < n_users) xc = cursor_at(off, idx, u0 + lane, p0);
 
   float4 pre[CPT];
   auto load_tile = [&](int64_t start) {
@@ -140,12 +131,7 @@ __device__ __forceinline__ void dot_auc_pass(const float* __restrict__ Q, int64_
     if (!active) continue;
 
     // this window's positive mask of user u0 + lane (lanes < UW), handed to the lanes that hold the user's scores through LDS
-    uint64_t xm = 0;
-    while (ex_nxt < base + NT) {
-      if (ex_nxt >= base) xm |= 1ull << (ex_nxt - base);
-      ++ex_cur;
-      ex_nxt = ex_cur < ex_end ? (int64_t)idx[ex_cur] : INT64_MAX;
-    }
+    const uint64_t xm = cursor_window(xc, idx, base, NT);
     const bool any_ex = __ballot(xm != 0) != 0;
     if (any_ex) {
       if (lane < UW) XM[lane] = xm;
@@ -319,18 +305,9 @@ __device__ __forceinline__ void dot_auc_wide_pass(const float* __restrict__ Q, i
   int step0 = 0;                                                      // highest power of two <= top (wave-uniform)
   if (top > 0) step0 = 1 << (31 - __builtin_clz((unsigned)top));
 
-  // truth cursor of user u0 + lane: the first entry of its list at or after p0, and that entry's position
-  int64_t ex_cur = 0, ex_end = 0, ex_nxt = INT64_MAX;
-  if (lane < UW && u0 + lane < n_users) {
-    int64_t lo = off[u0 + lane], hi = off[u0 + lane + 1];
-    ex_end = hi;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)idx[mid] < p0) lo = mid + 1; else hi = mid;
-    }
-    ex_cur = lo;
-    if (ex_cur < ex_end) ex_nxt = idx[ex_cur];
-  }
+  // skip cursor of user u0 + lane: the first entry of its (off, idx) row at or after p0, and that entry's position
+  RowCursor xc;
+  if (lane < UW && u0 + lane < n_users) xc = cursor_at(off, idx, u0 + lane, p0);
 
   // features [f0, f0 + 128) of the items [start, start + NT) -> pre
   float4 pre[CPT];
@@ -386,12 +363,7 @@ __device__ __forceinline__ void dot_auc_wide_pass(const float* __restrict__ Q, i
     if (!active) continue;
 
     // this window's positive mask of user u0 + lane (lanes < UW), handed to the lanes that hold the user's scores through LDS
-    uint64_t xm = 0;
-    while (ex_nxt < base + NT) {
-      if (ex_nxt >= base) xm |= 1ull << (ex_nxt - base);
-      ++ex_cur;
-      ex_nxt = ex_cur < ex_end ? (int64_t)idx[ex_cur] : INT64_MAX;
-    }
+    const uint64_t xm = cursor_window(xc, idx, base, NT);
     const bool any_ex = __ballot(xm != 0) != 0;
     uint64_t m[4] = {0, 0, 0, 0};
     if (any_ex) {

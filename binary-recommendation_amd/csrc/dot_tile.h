@@ -1,7 +1,7 @@
 // What the dot-product catalogue kernels (recommend_dot.hip / recommend_dot_wide.hip: top-k, auc_count.h: AUC, ranks_dot.hip: ranks)
-// share outside their tile loops: the split plan (recommend.hip's too), wave_lds_order, the CSR row cursor (RowCursor: the rank kernels use
-// it, the AUC bodies still spell it inline) and what the entry points check and choose alike.  The tile loop itself is still written out
-// in every kernel and kept the same by hand: see DESIGN.md 4e "One copy of the tile loop".
+// share outside their tile loops: the split plan (recommend.hip's too), wave_lds_order, the CSR row cursor (RowCursor: the AUC and the
+// rank passes) and what the entry points check and choose alike.  The tile loop itself is still written out once per family and width
+// (top-k, AUC pass, rank pass) and kept the same by hand: see DESIGN.md 4e "One copy of the tile loop".
 #pragma once
 #include <type_traits>
 

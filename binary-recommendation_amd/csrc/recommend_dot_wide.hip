@@ -11,7 +11,7 @@
 //   - the next block (the next step's first block after a step's last) is in flight while the current one is scored;
 //   - a wave owns 16 users (one row tile), their A fragments in registers for the whole launch: 32 NB VGPRs;
 //   - everything after the scores - threshold compare, candidate queue, LDS lists, exclusion cursor, split plan, merge - is
-//     recommend_dot.hip's (topk_list.h, dot_tile.h); that part of the tile loop is a copy kept the same by hand, as auc_dot.hip's is
+//     recommend_dot.hip's (topk_list.h, dot_tile.h); that part of the tile loop is a copy kept the same by hand, as the AUC passes' (auc_count.h) is
 //     (DESIGN.md 4e "One copy of the tile loop", 4h).
 #include <math.h>
 

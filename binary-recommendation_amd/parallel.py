@@ -465,6 +465,34 @@ def recommend_at_owners(ctx: DistCtx, users, items, n_item_rows: int, k: int, ex
     return ops.topk_lists_merge(recv.view(torch.float32), recv[:, k:], W, U, k, plan.l2g, plan.l2g_off, list_stride=U * 2 * k, user_stride=2 * k)
 
 
+def _sorted_positives_at_owners(ctx: DistCtx, plan: "_CandidatePlan", q_all, off_all, idx_all, T_all: int, candidates_of, positives):
+    """What auc_at_owners and ranks_at_owners share behind the gathered queries and truth lists: this rank's candidates, its share
+    of every user's positives in its local positions, and every user's full sorted list of positives on every rank.  Every owner's
+    per-user counts, then its raw scores, go to every rank: each piece padded to the longest (one host sync to learn it), and the
+    lists are sorted from the receive buffer in place.  A rank that owns no candidate of the list has no positives but joins both
+    all-gathers.  -> (cand, pos_off, pos_idx: None on such a rank; raw: this rank's piece (1, max(longest, 1)); sorted_, pcnt)."""
+    from . import ops
+    W, dev, U_all = ctx.world, q_all.device, off_all.shape[0] - 1
+    cand = pos_off = pos_idx = None
+    if plan.n_loc:
+        cand = candidates_of(plan.local_rows)
+        pos_off, pos_idx = plan.split_csr(off_all, idx_all)
+        lens = (pos_off[1:] - pos_off[:-1]).to(torch.int32)
+    else:
+        lens = torch.zeros(U_all, dtype=torch.int32, device=dev)
+    lens_all = ctx.all_gather_rows(lens.view(1, U_all)).to(torch.int64)
+    m = int(lens_all.sum(1).max().item())
+    raw = torch.zeros(1, max(m, 1), dtype=torch.float32, device=dev)
+    if plan.n_loc and m:
+        positives(q_all, cand, pos_off, pos_idx, raw)
+    raw_all = ctx.all_gather_rows(raw) if m else raw.repeat(W, 1)
+    piece_off = torch.zeros(W, U_all + 1, dtype=torch.int64, device=dev)
+    piece_off[:, 1:] = lens_all.cumsum(1)
+    piece_off += (torch.arange(W, dtype=torch.int64, device=dev) * raw.shape[1]).view(W, 1)
+    sorted_, pcnt = ops.auc_sort_pieces(raw_all, piece_off, off_all, T_all)
+    return cand, pos_off, pos_idx, raw, sorted_, pcnt
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Full-catalogue AUC counted where the item rows live (DESIGN.md 4i): recommend_at_owners' turn for full_auc.  Every rank scores the
 # positives it owns, the raw scores of all owners are sorted into every user's full list on every rank, each rank counts the queries
@@ -505,26 +533,9 @@ def auc_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, fetch_use
         raise ValueError(f"full_auc: the query rows have {q_all.shape[1]} features, dim = {dim}")
     off_all, idx_all = _all_gather_csr(ctx, t_off, t_idx, U, u_counts, t_counts)
     T_all = sum(t_counts)
-    # 3. this rank's candidates, and its share of every user's positives in its local positions
+    # 3, 4. this rank's candidates and its share of every user's positives; every user's full sorted list on every rank
     plan = _CandidatePlan(ctx, items)
-    if plan.n_loc:
-        cand = candidates_of(plan.local_rows)
-        pos_off, pos_idx = plan.split_csr(off_all, idx_all)
-        lens = (pos_off[1:] - pos_off[:-1]).to(torch.int32)
-    else:                        # no candidate of the list lives here: no positives, no counts - but every collective below is joined
-        lens = torch.zeros(U_all, dtype=torch.int32, device=dev)
-    # 4. every owner's per-user counts, then its raw scores, on every rank: each piece padded to the longest (one host sync to learn
-    #    it), and the users' full lists sorted from the receive buffer in place
-    lens_all = ctx.all_gather_rows(lens.view(1, U_all)).to(torch.int64)
-    m = int(lens_all.sum(1).max().item())
-    raw = torch.zeros(1, max(m, 1), dtype=torch.float32, device=dev)
-    if plan.n_loc and m:
-        positives(q_all, cand, pos_off, pos_idx, raw)
-    raw_all = ctx.all_gather_rows(raw) if m else raw.repeat(W, 1)
-    piece_off = torch.zeros(W, U_all + 1, dtype=torch.int64, device=dev)
-    piece_off[:, 1:] = lens_all.cumsum(1)
-    piece_off += (torch.arange(W, dtype=torch.int64, device=dev) * raw.shape[1]).view(W, 1)
-    sorted_, pcnt = ops.auc_sort_pieces(raw_all, piece_off, off_all, T_all)
+    cand, pos_off, pos_idx, _raw, sorted_, pcnt = _sorted_positives_at_owners(ctx, plan, q_all, off_all, idx_all, T_all, candidates_of, positives)
     # 5. all queries x the local candidates: one integer 2W per user
     if plan.n_loc:
         w2 = count(q_all, cand, pos_off, pos_idx, off_all, sorted_, pcnt)
@@ -571,7 +582,7 @@ def ranks_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, exclude
     ops.dot_auc_owner_positives) and count(q, cand, skip_off, skip_idx, list_off, sorted_, pcnt, bins, ties) (ops.neumf_rank_count;
     ops.dot_rank_count), which adds into the bins."""
     from . import ops
-    W, r, dev = ctx.world, ctx.rank, users.device
+    r, dev = ctx.rank, users.device
     if items is None:
         items = torch.arange(n_item_rows, dtype=users.dtype, device=dev)
     U, I = users.shape[0], items.shape[0]
@@ -597,28 +608,11 @@ def ranks_at_owners(ctx: DistCtx, users, items, n_item_rows: int, truth, exclude
     any_ex = any(c >= 0 for c in e_counts)
     if any_ex:
         x_all = _all_gather_csr(ctx, ex_off if has_ex else None, ex_idx if has_ex else none, U, u_counts, e_counts)
-    # 3. this rank's candidates, and its share of every user's positives and excluded positions in its local positions
+    # 3, 4. this rank's candidates, its share of every user's excluded positions and positives in its local positions; every user's
+    #    full sorted list of positives on every rank
     plan = _CandidatePlan(ctx, items)
-    excl = None
-    if plan.n_loc:
-        cand = candidates_of(plan.local_rows)
-        pos_off, pos_idx = plan.split_csr(off_all, idx_all)
-        lens = (pos_off[1:] - pos_off[:-1]).to(torch.int32)
-        if any_ex:
-            excl = plan.split_csr(*x_all)
-    else:                        # no candidate of the list lives here: no positives, no counts - but every collective below is joined
-        lens = torch.zeros(U_all, dtype=torch.int32, device=dev)
-    # 4. every owner's raw scores on every rank, the users' full lists sorted from the receive buffer in place (auc_at_owners step 4)
-    lens_all = ctx.all_gather_rows(lens.view(1, U_all)).to(torch.int64)
-    m = int(lens_all.sum(1).max().item())
-    raw = torch.zeros(1, max(m, 1), dtype=torch.float32, device=dev)
-    if plan.n_loc and m:
-        positives(q_all, cand, pos_off, pos_idx, raw)
-    raw_all = ctx.all_gather_rows(raw) if m else raw.repeat(W, 1)
-    piece_off = torch.zeros(W, U_all + 1, dtype=torch.int64, device=dev)
-    piece_off[:, 1:] = lens_all.cumsum(1)
-    piece_off += (torch.arange(W, dtype=torch.int64, device=dev) * raw.shape[1]).view(W, 1)
-    sorted_, pcnt = ops.auc_sort_pieces(raw_all, piece_off, off_all, T_all)
+    excl = plan.split_csr(*x_all) if plan.n_loc and any_ex else None
+    cand, pos_off, pos_idx, raw, sorted_, pcnt = _sorted_positives_at_owners(ctx, plan, q_all, off_all, idx_all, T_all, candidates_of, positives)
     # 5. all queries x the local candidates into zeroed bins over the global lists, then this rank's excluded positives out of them
     bins, ties = ops.rank_bins(U_all, T_all, dev)
     if plan.n_loc:

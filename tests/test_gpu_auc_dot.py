@@ -124,6 +124,40 @@ def test_non_finite_scores(dev):
     assert float(auc[5]) == 0.0                                        # NaN user: no pair counts
 
 
+@pytest.mark.parametrize("dim, U, force_wide", [(33, 70, False), (33, 40, True), (350, 40, False)])
+def test_lists_past_the_workspace(dev, dim, U, force_wide):
+    """the C ABI with a workspace sized for fewer truth entries than the call brings (brDotCatalogAuc[Wide]WorkspaceBytes(n_truth)
+    bounds the entries a call can take): a user whose list ends inside the capacity keeps brFullAuc's bits, a user past it gets NaN and
+    nothing else moves.  The whole-row and the block kernels, 5 item splits (I = 300), a partial last wave and idle waves in the one
+    workgroup, rows that are not 16-B aligned.  A workspace of ws_bytes holds fewer than ws_bytes / 8 entries (two float halves)."""
+    ops, L = _m("ops"), _m("_lib")
+    lib, I, n_fit = L.load(), 300, 255
+    g = torch.Generator(device="cpu").manual_seed(dim + U)
+    Q = torch.randn(U, dim, generator=g).to(dev)
+    C = torch.randn(I, dim, generator=g).to(dev)
+    off, idx = _truth(np.random.default_rng(U).integers(20, 40, U), I, dev, seed=U)
+    wide = force_wide or dim > 128
+    ws_bytes = int(lib.brDotCatalogAucWideWorkspaceBytes(U, I, dim, n_fit) if wide else lib.brDotCatalogAucWorkspaceBytes(U, I, n_fit))
+    ends = off[1:]
+    fits, past = ends <= n_fit, ends > ws_bytes // 8
+    assert fits.any() and past.any()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    auc = torch.full((U,), -1.0, device=dev)
+    dump = torch.empty(U, I, device=dev)
+    head = (Q.data_ptr(), dim, U, C.data_ptr(), dim, I, dim, off.data_ptr(), idx.data_ptr(), auc.data_ptr(), dump.data_ptr())
+    tail = (ws.data_ptr(), ws_bytes, ops._stream())
+    if wide:
+        L.check(lib.brDotCatalogAucWide(*head, ops._wide_flags(force_wide), *tail), "brDotCatalogAucWide")
+    else:
+        L.check(lib.brDotCatalogAuc(*head, *tail), "brDotCatalogAuc")
+    ref = ops.full_auc(dump, off, idx)
+    assert not torch.isnan(ref).any()
+    assert torch.equal(auc[fits], ref[fits]) and torch.isnan(auc[past]).all()
+    assert (torch.isnan(auc) | (auc == ref)).all()
+    want = (ops.dot_catalog_auc_wide(Q, C, off, idx, force_wide=force_wide) if wide else ops.dot_catalog_auc(Q, C, off, idx))
+    assert torch.equal(want, ref)                                      # the same call with room for every entry
+
+
 def test_strides_and_alignment(dev):
     """a column slice of a wider table (16-B aligned rows and not: the scalar-load path) gives the contiguous result"""
     ops = _m("ops")
