@@ -517,6 +517,37 @@ def bn_param_grads_pair(bn_sums_a, dgamma_a, dbeta_a, bn_sums_b, dgamma_b, dbeta
           "brBnParamGradsPair")
 
 
+def dense_finalize(regions, bn_blocks, grad, theta=None, m=None, v=None, alpha_t=0.0, beta1=0.9, beta2=0.999, eps=1e-7):
+    """End of the dense backward in one launch (brDenseFinalize): reduce_slabs of three regions, bn_param_grads of two BatchNorms and
+    adam_flat on the flat vector.  regions: three (slabs, n_slabs, elems, grad_off); bn_blocks: two (bn_sums, N, dgamma_off, dbeta_off),
+    bn_sums = double [STAT_REPLICAS][2N]; together they cover grad[0:n] exactly once.  theta, m, v: all three (Adam with the new
+    gradient) or none (gradients only: the data-parallel host all-reduces `grad` before its optimizer)."""
+    if len(regions) != 3 or len(bn_blocks) != 2:
+        raise ValueError("dense_finalize: three slab regions and two BatchNorm blocks")
+    if len({theta is None, m is None, v is None}) != 1:
+        raise ValueError("dense_finalize: theta, m and v go together (all three or none)")
+    n = _f32(grad, "grad").numel()
+    for name, t in (("theta", theta), ("m", m), ("v", v)):
+        if t is not None and _f32(t, name).numel() != n:
+            raise ValueError(f"dense_finalize: {name} has {t.numel()} elements, grad {n}")
+    for s, ns, el, _ in regions:
+        if _f32(s, "slabs").numel() < int(ns) * int(el):
+            raise ValueError("dense_finalize: a slab buffer is shorter than n_slabs x elems")
+    for s, N, _, _ in bn_blocks:
+        if s.dtype != torch.float64 or not s.is_cuda or not s.is_contiguous() or s.numel() < STAT_REPLICAS * 2 * int(N):
+            raise TypeError("dense_finalize: bn_sums is a contiguous float64 device tensor [STAT_REPLICAS][2N]")
+    SP = (ctypes.c_void_p * 3)(*[r[0].data_ptr() for r in regions])
+    NS = (ctypes.c_int * 3)(*[int(r[1]) for r in regions])
+    EL = (ctypes.c_int64 * 3)(*[int(r[2]) for r in regions])
+    GO = (ctypes.c_int64 * 3)(*[int(r[3]) for r in regions])
+    BS = (ctypes.c_void_p * 2)(*[b[0].data_ptr() for b in bn_blocks])
+    BN = (ctypes.c_int * 2)(*[int(b[1]) for b in bn_blocks])
+    DG = (ctypes.c_int64 * 2)(*[int(b[2]) for b in bn_blocks])
+    DB = (ctypes.c_int64 * 2)(*[int(b[3]) for b in bn_blocks])
+    check(_lib.load().brDenseFinalize(SP, NS, EL, GO, BS, BN, DG, DB, _p(theta), _p(m), _p(v), grad.data_ptr(), n, float(alpha_t), float(beta1),
+                                      float(beta2), float(eps), _stream()), "brDenseFinalize")
+
+
 def head_slabs(batch) -> int:
     return int(_lib.load().brHeadSlabs(batch))
 

@@ -71,6 +71,46 @@ def test_argument_errors_are_reported_not_crashed(built):
     assert h.brProbeGraphNodes() == 0 and h.brProbeGraphArm(None, 0) == -1 and h.brProbeGraphRead(0, None) == -1
 
 
+def test_dense_finalize_argument_errors(built):
+    """brDenseFinalize checks its layout on the host before any launch: the three slab regions and the two BatchNorm blocks must cover
+    the n parameters exactly, lie inside them, hold at least one slab each, and theta comes with m and v or not at all.  The pointers
+    are never dereferenced on these paths (0x1000 stands for device memory)."""
+    lib = import_module("binary-recommendation_amd._lib")
+    h = lib.load()
+    P = 0x1000
+
+    def call(n_slabs=(3, 2, 1), elems=(130, 65, 7), grad_off=(40, 204, 0), bn_n=(33, 1), dgamma=(7, 269), dbeta=(171, 170), n=270,
+             theta=P, m=P, v=P, slabs=(P, P, P), sums=(P, P), grad=P):
+        SP = (ctypes.c_void_p * 3)(*slabs)
+        BS = (ctypes.c_void_p * 2)(*sums)
+        return h.brDenseFinalize(SP, (ctypes.c_int * 3)(*n_slabs), (ctypes.c_int64 * 3)(*elems), (ctypes.c_int64 * 3)(*grad_off), BS,
+                                 (ctypes.c_int * 2)(*bn_n), (ctypes.c_int64 * 2)(*dgamma), (ctypes.c_int64 * 2)(*dbeta), theta, m, v, grad, n,
+                                 1e-3, 0.9, 0.999, 1e-7, None)
+
+    ERR_ARG = lib.parse_enums()["BR_ERR_ARG"]
+    bad = {
+        "covers fewer than n": dict(elems=(130, 65, 6)),
+        "covers more than n": dict(elems=(130, 65, 7), bn_n=(33, 2)),
+        "covers more than n (region)": dict(elems=(131, 65, 7)),
+        "region past n": dict(grad_off=(40, 206, 0)),
+        "BatchNorm range past n": dict(dgamma=(7, 270)),
+        "negative offset": dict(grad_off=(40, 204, -1)),
+        "theta without m": dict(m=None),
+        "theta without v": dict(v=None),
+        "theta without m and v": dict(m=None, v=None),
+        "n_slabs = 0": dict(n_slabs=(3, 0, 1)),
+        "elems = 0": dict(elems=(137, 65, 0)),
+        "null slab pointer": dict(slabs=(P, None, P)),
+        "null sums pointer": dict(sums=(None, P)),
+        "null grad": dict(grad=None),
+        "n = 0": dict(n=0),
+    }
+    for what, kw in bad.items():
+        assert call(**kw) == ERR_ARG, what
+        assert b"brDenseFinalize" in h.brGetLastError(), what
+    assert h.brDenseFinalize(None, None, None, None, None, None, None, None, None, None, None, P, 270, 1e-3, 0.9, 0.999, 1e-7, None) == ERR_ARG
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     lib = import_module("binary-recommendation_amd._lib")
     monkeypatch.setattr(lib, "_lib", None)

@@ -69,8 +69,15 @@ def _forward_backward_parity(dev, variant, dim, B, hidden=None):
     td = lambda a, dt: torch.from_numpy(a).to(dev).to(dt)
     eng.train_step(td(u, torch.int32), td(i, torch.int32), td(y, torch.float32))
     torch.cuda.synchronize()
+    _assert_step_parity(eng, spec, cfg, p, u, i, y)
+
+
+def _assert_step_parity(eng, spec, cfg, p, u, i, y, step=1):
+    """what training step `step` on (u, i, y) left in `eng` against the oracle started from the parameters p (also the anchor of
+    tests/test_gpu_dense_finalize.py)"""
+    B = len(u)
     eng.check_ids()
-    masks = _masks(cfg, spec, 1, B)
+    masks = _masks(cfg, spec, step, B)
     loss, c, g, rg, ns = O.neumf_step_grads(spec, p, u, i, y, masks, dt=np.float64)
     # BatchNorm over a handful of rows divides by a tiny batch variance: fp32 rounding of the
     # activations is amplified by rstd, so small-batch cases get 4x the bound (inherent to fp32 BN,
@@ -108,7 +115,8 @@ def test_three_optimizer_steps(dev, variant, dim, optimizer, impl):
     is 1e-5 relative + 2 % (dense) / 0.5 % (tables) of the distance Adam can travel in 3 steps
     (a ReLU unit sitting at 0 can also flip between fp32 and fp64); the tight checks are the
     single-step gradients above and the optimizer kernels on identical inputs
-    (test_gpu_sparse_optim.py)."""
+    (tables: test_gpu_sparse_optim.py; dense parameters: the finalize against adam_flat and float64,
+    test_gpu_dense_finalize.py)."""
     B = 200
     ops, eng, spec, cfg, p, u, i, y = _setup(variant, dim, B, dev, optimizer=optimizer, dense_impl=impl)
     td = lambda a, dt: torch.from_numpy(a).to(dev).to(dt)
