@@ -4,11 +4,12 @@
 //
 //   AUC(u) = W / (P N),  2W = sum over positives p and the other items i of 2 [s_i < s_p] + [s_i == s_p]
 //
-// The scoring loop of catalog_topk_kernel<W, ACT> is restated in neumf_score.h (neumf_score: acc = b2', the fmaf chain over n1 with
-// act(urow[i] + x), the W3'^T chain, the head with w4mf . dot, sigmoidf_acc), statement for statement, so a pair's probability depends on
-// its user row, its item column and the folded tower only - not on the lane, the split or the kernel that forms it.  The two copies are
-// held equal by a test that compares their dumps bit for bit (tests/test_gpu_neumf_auc.py); recommend.hip keeps its own text because it
-// is the measured kernel; the ranks (ranks_neumf.hip) include the same header.  Four phases, the two in the middle and at the end shared with the dot-product models (auc_owner.hip):
+// The scoring loop is neumf_score.h's (neumf_logit: acc = b2', the fmaf chain over n1 with act(urow[i] + x), the W3'^T chain, the head
+// with w4mf . dot; neumf_score: sigmoidf_acc of it), the one text catalog_topk_kernel and the ranks (ranks_neumf.hip) call too, so a
+// pair's probability depends on its user row, its item column and the folded tower only - not on the lane, the split or the kernel that
+// forms it; a test compares the kernels' dumps bit for bit (tests/test_gpu_neumf_auc.py).  This unit also owns the positives' kernel
+// and its launch (neumf_positives, declared in neumf_score.h), which the ranks call: its instantiations are compiled here only.  Four
+// phases, the two in the middle and at the end shared with the dot-product models (auc_owner.hip):
 //   - neumf_auc_pos_kernel: one wave per user, lane = one of the user's truth entries, 64 at a time: raw[pos_off[u] + j];
 //   - brAucSortPieces: per user one ascending list, NaN dropped, the count P' beside;
 //   - neumf_auc_count_kernel: catalog_topk_kernel's grid and split plan (4 users per workgroup, lane = item, 64 items per step).  The
@@ -33,6 +34,32 @@ namespace {
 // of a compute unit - more than the eight (32 waves) it can hold at all: LDS never bounds the occupancy
 constexpr int kNeumfAucLdsCap = 1024;
 
+// one wave per user: raw[off[u] + j] = the probability of (u, the user's j-th entry) (neumf_score.h neumf_positives)
+template <int W, int ACT>
+__global__ __launch_bounds__(256) void neumf_auc_pos_kernel(const float* __restrict__ pu, int64_t ld_u, const float* __restrict__ pit,
+                                                             int64_t ld_i, int64_t n_users, int64_t n_items, int dim, int n1, int n3,
+                                                             const float* __restrict__ tower, TowerLayout L,
+                                                             const int64_t* __restrict__ off, const int32_t* __restrict__ idx,
+                                                             float* __restrict__ raw, int64_t cap) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t u = (int64_t)blockIdx.x * kRecWaves + wave;
+  if (u >= n_users) return;
+  const int64_t o0 = off[u], o1 = off[u + 1], P = o1 - o0;
+  if (P <= 0 || o0 < 0 || o1 > cap) return;
+
+  const float* __restrict__ urow = pu + u * ld_u;            // [Pu (b1 included) | user mf]
+  const TowerView t = tower_view(tower, L);
+  for (int64_t j0 = 0; j0 < P; j0 += 64) {
+    const int64_t j = j0 + lane;
+    const int64_t p = j < P ? (int64_t)idx[o0 + j] : -1;
+    const bool ok = p >= 0 && p < n_items;
+    const int64_t pc = ok ? p : 0;                           // (a lane without an entry scores item 0: every load stays in bounds)
+    const float prob = neumf_score<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, t);
+    if (j < P) raw[o0 + j] = ok ? prob : __builtin_nanf("");
+  }
+}
+
 template <int W, int ACT>
 __global__ __launch_bounds__(256) void neumf_auc_count_kernel(const float* __restrict__ pu, int64_t ld_u, const float* __restrict__ pit,
                                                                int64_t ld_i, int64_t n_users, int64_t n_items, int dim, int n1, int n3,
@@ -48,17 +75,9 @@ __global__ __launch_bounds__(256) void neumf_auc_count_kernel(const float* __res
   const int64_t u = (int64_t)blockIdx.x * kRecWaves + wave;
   if (u >= n_users) return;                                  // (no workgroup barrier below: a wave may leave alone)
   const int64_t split = blockIdx.y;
-  const int64_t p0 = split * chunks_per_split * 64;
-  int64_t p1 = p0 + chunks_per_split * 64;
-  if (p1 > n_items) p1 = n_items;
-
+  const auto [p0, p1] = split_items(split, chunks_per_split, n_items);
   const float* __restrict__ urow = pu + u * ld_u;            // [Pu (b1 included) | user mf]
-  const float* __restrict__ W2 = tower + L.w2;
-  const float* __restrict__ b2 = tower + L.b2;
-  const float* __restrict__ W3t = tower + L.w3t;
-  const float* __restrict__ b3 = tower + L.b3;
-  const float* __restrict__ w4 = tower + L.w4;
-  const float w4mf = tower[L.w4mf], b4 = tower[L.b4];
+  const TowerView t = tower_view(tower, L);
 
   // the user's sorted positives (wave-uniform): P' entries from lb, in LDS when they fit, else read from `sorted`.  A list that does
   // not lie inside sorted's `cap` floats counts as empty (its user gets NaN from the finalize: pcnt < 0)
@@ -76,17 +95,7 @@ __global__ __launch_bounds__(256) void neumf_auc_count_kernel(const float* __res
   int step0 = 0;                                             // highest power of two <= P'
   if (np > 0) step0 = 1 << (31 - __builtin_clz((unsigned)np));
 
-  // skip cursor: first entry of the user's list at or after p0
-  int64_t ex_cur, ex_end;
-  {
-    int64_t lo = ex_off[u], hi = ex_off[u + 1];
-    ex_end = hi;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)ex_idx[mid] < p0) lo = mid + 1; else hi = mid;
-    }
-    ex_cur = lo;
-  }
+  WaveCursor ex = wave_cursor_at(ex_off, ex_idx, u, p0);     // skip cursor: first entry of the user's list at or after p0
 
   uint64_t w2 = 0;
   for (int64_t base = p0; base < p1; base += 64) {
@@ -94,19 +103,9 @@ __global__ __launch_bounds__(256) void neumf_auc_count_kernel(const float* __res
     const bool valid = p < p1;
     const int64_t pc = valid ? p : p1 - 1;                   // tail lanes recompute the last item (never read past the list)
 
-    uint64_t m = 0;
-    for (;;) {                                               // the entries inside [base, base + 64) are a prefix of the rest
-      const int64_t q = ex_cur + lane;
-      const int64_t e = q < ex_end ? (int64_t)ex_idx[q] : INT64_MAX;
-      const bool in = e < base + 64;
-      if (in && e >= base) m |= 1ull << (e - base);
-      const int n_in = __popcll(__ballot(in));
-      ex_cur += n_in;
-      if (n_in < 64) break;
-    }
-    const bool skipped = (wave_or64(m) >> lane) & 1;
+    const bool skipped = (wave_or64(wave_cursor_window(ex, ex_idx, base, lane)) >> lane) & 1;
 
-    const float s = neumf_score<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, W2, b2, W3t, b3, w4, w4mf, b4);
+    const float s = neumf_score<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, t);
     if (valid && dump_probs) dump_probs[u * n_items + p] = s;
 
     // fast paths first (a NaN score fails every compare: 0); the scores inside [min, max] search the list
@@ -149,14 +148,6 @@ __global__ __launch_bounds__(256) void neumf_auc_sum_splits_kernel(const uint64_
   out[u] = w2;
 }
 
-template <int W, int ACT>
-void launch_count(hipStream_t st, const Operands& a, const int64_t* ex_off, const int32_t* ex_idx, const int64_t* loff, const float* sorted,
-                  const int32_t* pcnt, int64_t cap, int64_t cps, int64_t S, uint64_t* part, float* dump) {
-  const dim3 grid((unsigned)ceil_div(a.U, kRecWaves), (unsigned)S);
-  neumf_auc_count_kernel<W, ACT><<<grid, 256, 0, st>>>(a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3, a.tower, a.L, ex_off, ex_idx,
-                                                       loff, sorted, pcnt, cap, cps, S, part, dump);
-}
-
 int64_t count_part_bytes(int64_t n_users, int64_t n_items) {
   int64_t S, cps;
   catalog_plan(n_users, n_items, &S, &cps);
@@ -168,17 +159,18 @@ int64_t auc_fixed_bytes(int64_t n_users, int64_t n_items) {
   return count_part_bytes(n_users, n_items) + align256(n_users * 8) + align256(n_users * 4);
 }
 
-int count(const char* name, const Operands& a, int n2, int act, const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off,
+int count(const char* name, const Operands& a, const int64_t* skip_off, const int32_t* skip_idx, const int64_t* list_off,
           const float* sorted, const int32_t* pcnt, int64_t cap, uint64_t* part, uint64_t* out_w2, float* dump, hipStream_t st) {
   int64_t S, cps;
   catalog_plan(a.U, a.I, &S, &cps);
   if (cap > INT32_MAX) cap = INT32_MAX;
-  if (!dispatch_tower(n2, act, [&](auto w, auto ac) {
-        launch_count<decltype(w)::value, decltype(ac)::value>(st, a, skip_off, skip_idx, list_off, sorted, pcnt, cap, cps, S, part, dump);
-      })) {
-    br::set_error("%s: no kernel for n2 = %d", name, n2);
-    return BR_ERR_UNSUPPORTED;
-  }
+  const dim3 grid((unsigned)ceil_div(a.U, kRecWaves), (unsigned)S);
+  if (const int rc = dispatch_tower(name, a.n2, a.act, [&](auto w, auto ac) {
+        neumf_auc_count_kernel<decltype(w)::value, decltype(ac)::value><<<grid, 256, 0, st>>>(
+            a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3, a.tower, tower_layout(a.n1, a.n2, a.n3), skip_off, skip_idx, list_off,
+            sorted, pcnt, cap, cps, S, part, dump);
+      }))
+    return rc;
   BR_CHECK_LAUNCH(name);
   neumf_auc_sum_splits_kernel<<<(unsigned)ceil_div(a.U, 256), 256, 0, st>>>(part, S, a.U, out_w2);
   BR_CHECK_LAUNCH(name);
@@ -186,6 +178,17 @@ int count(const char* name, const Operands& a, int n2, int act, const int64_t* s
 }
 
 }  // namespace
+
+int neumf_positives(const char* name, const Operands& a, const int64_t* off, const int32_t* idx, float* raw, int64_t cap, hipStream_t st) {
+  if (const int rc = dispatch_tower(name, a.n2, a.act, [&](auto w, auto ac) {
+        neumf_auc_pos_kernel<decltype(w)::value, decltype(ac)::value><<<(unsigned)ceil_div(a.U, kRecWaves), 256, 0, st>>>(
+            a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3, a.tower, tower_layout(a.n1, a.n2, a.n3), off, idx, raw, cap);
+      }))
+    return rc;
+  BR_CHECK_LAUNCH(name);
+  return BR_OK;
+}
+
 }  // namespace br
 
 using namespace br;
@@ -196,8 +199,8 @@ extern "C" int brNeumfAucPositives(const float* pu, int64_t ld_u, int64_t n_user
   BR_CHECK_ARG(pu && pit && tower && pos_off && pos_idx && raw, "brNeumfAucPositives: null pointer");
   if (const int rc = catalog_check_args("brNeumfAucPositives", ld_u, n_users, ld_i, n_items, dim, n1, n2, n3, act)) return rc;
   if (n_users == 0) return BR_OK;
-  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, tower, tower_layout(n1, n2, n3)};
-  return positives("brNeumfAucPositives", a, n2, act, pos_off, pos_idx, raw, INT64_MAX, (hipStream_t)stream);
+  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n2, n3, act, tower};
+  return neumf_positives("brNeumfAucPositives", a, pos_off, pos_idx, raw, INT64_MAX, (hipStream_t)stream);
 }
 
 extern "C" int64_t brNeumfAucCountWorkspaceBytes(int64_t n_users, int64_t n_items) {
@@ -218,8 +221,8 @@ extern "C" int brNeumfAucCount(const float* pu, int64_t ld_u, int64_t n_users, c
     return BR_ERR_WORKSPACE;
   }
   if (n_users == 0) return BR_OK;
-  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, tower, tower_layout(n1, n2, n3)};
-  return count("brNeumfAucCount", a, n2, act, skip_off, skip_idx, list_off, sorted, pcnt, cap, (uint64_t*)ws, out_w2, dump_probs,
+  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n2, n3, act, tower};
+  return count("brNeumfAucCount", a, skip_off, skip_idx, list_off, sorted, pcnt, cap, (uint64_t*)ws, out_w2, dump_probs,
                (hipStream_t)stream);
 }
 
@@ -251,11 +254,11 @@ extern "C" int brNeumfCatalogAuc(const float* pu, int64_t ld_u, int64_t n_users,
   int64_t cap = third / 4 - 1;                                       // truth entries [0, cap) fit; a user past them gets NaN
   if (cap > INT32_MAX) cap = INT32_MAX;
   hipStream_t st = (hipStream_t)stream;
-  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, tower, tower_layout(n1, n2, n3)};
-  if (const int rc = positives("brNeumfCatalogAuc positives", a, n2, act, truth_off, truth_idx, raw, cap, st)) return rc;
+  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n2, n3, act, tower};
+  if (const int rc = neumf_positives("brNeumfCatalogAuc positives", a, truth_off, truth_idx, raw, cap, st)) return rc;
   // one piece per user, where the positives' kernel wrote it: piece_off = list_off = truth_off
   if (const int rc = brAucSortPieces(raw, cap, truth_off, 1, n_users, truth_off, sorted, cap, pcnt, tmp, third, stream)) return rc;
-  if (const int rc = count("brNeumfCatalogAuc count", a, n2, act, truth_off, truth_idx, truth_off, sorted, pcnt, cap, part, w2, dump_probs, st))
+  if (const int rc = count("brNeumfCatalogAuc count", a, truth_off, truth_idx, truth_off, sorted, pcnt, cap, part, w2, dump_probs, st))
     return rc;
   return brAucFinalizeLists(w2, n_users, 1, truth_off, pcnt, n_users, n_items, out_auc, stream);
 }

@@ -1,6 +1,6 @@
-// What the NeuMF catalogue kernels (recommend.hip: top-k, auc_neumf.hip: AUC) share on the host: the folded tower's layout, the padded
-// width their kernels are instantiated at, the limits and the split plan.  The scoring loop itself is written out in both files and
-// kept the same by a bit-equality test.
+// What the NeuMF catalogue kernels (recommend.hip: top-k, auc_neumf.hip: AUC, ranks_neumf.hip: ranks) share on the host: the folded
+// tower's layout, the padded width their kernels are instantiated at, the limits and the split plan.  What they share on the device
+// (the scoring loop, the tower view, the wave cursor) and the dispatch over the instantiations: neumf_score.h.
 #pragma once
 #include "common.h"
 #include "dot_tile.h"

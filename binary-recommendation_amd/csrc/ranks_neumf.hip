@@ -7,10 +7,10 @@
 // without the U x I matrix; brRankMetrics (ranks_dot.hip) turns the integers into MRR, NDCG@k, recall@k and hit@k.  The contract is
 // brDotCatalogRanks' (DESIGN.md 4k).  The launches of brNeumfCatalogRanks:
 //   - rank_init_kernel (rank_bins.h): the bins zeroed, the outputs -1;
-//   - neumf_auc_pos_kernel (neumf_score.h) and brAucSortPieces with one piece, as brNeumfCatalogAuc: the user's non-NaN positives
-//     ascending v_0 <= ... <= v_{n-1}, their number n in pcnt;
+//   - neumf_positives (auc_neumf.hip's neumf_auc_pos_kernel) and brAucSortPieces with one piece, as brNeumfCatalogAuc: the user's
+//     non-NaN positives ascending v_0 <= ... <= v_{n-1}, their number n in pcnt;
 //   - neumf_rank_count_kernel: neumf_auc_count_kernel's grid and split plan (4 users per workgroup, one wave per user, lane = item, 64
-//     items per step); the window mask is the union of two cursors (truth and exclusion).  Per valid unmasked score s: below v_0 or NaN
+//     items per step); the window mask is the union of two WaveCursors (truth and exclusion).  Per valid unmasked score s: below v_0 or NaN
 //     touches nothing; above v_{n-1} bumps a per-lane register counter (wave-reduced into bin n at the end of the split); inside,
 //     lo = #{v < s} by binary lifting and bin lo gets +1 (the candidate outranks the positives 0 .. lo - 1), and where v_lo == s tie bin
 //     lo too.  The list is wave-uniform: it sits in LDS up to kNeumfRankLdsCap entries with the wave's n + 1 bins beside it (LDS integer
@@ -51,10 +51,7 @@ __global__ __launch_bounds__(256) void neumf_rank_count_kernel(const float* __re
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t u = (int64_t)blockIdx.x * kRecWaves + wave;
   if (u >= n_users) return;                                  // (no workgroup barrier below: a wave may leave alone)
-  const int64_t split = blockIdx.y;
-  const int64_t p0 = split * chunks_per_split * 64;
-  int64_t p1 = p0 + chunks_per_split * 64;
-  if (p1 > n_items) p1 = n_items;
+  const auto [p0, p1] = split_items(blockIdx.y, chunks_per_split, n_items);
 
   // the user's sorted positives (wave-uniform): n entries from lb, in LDS with their bins when they fit, else read from `sorted`.  A
   // list that does not lie inside sorted's `cap` floats counts as empty (its entries keep (-1, -1): pcnt < 0)
@@ -78,40 +75,11 @@ __global__ __launch_bounds__(256) void neumf_rank_count_kernel(const float* __re
   if (np > 0) step0 = 1 << (31 - __builtin_clz((unsigned)np));
 
   const float* __restrict__ urow = pu + u * ld_u;            // [Pu (b1 included) | user mf]
-  const float* __restrict__ W2 = tower + L.w2;
-  const float* __restrict__ b2 = tower + L.b2;
-  const float* __restrict__ W3t = tower + L.w3t;
-  const float* __restrict__ b3 = tower + L.b3;
-  const float* __restrict__ w4 = tower + L.w4;
-  const float w4mf = tower[L.w4mf], b4 = tower[L.b4];
+  const TowerView t = tower_view(tower, L);
 
   // the two cursors: first entry of the user's truth row and of its exclusion row at or after p0 (no exclusion CSR: an empty row)
-  auto row_from = [&](const int64_t* __restrict__ off, const int32_t* __restrict__ idx, int64_t* end) {
-    int64_t lo = off[u], hi = off[u + 1];
-    *end = hi;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)idx[mid] < p0) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-  };
-  int64_t t_end, x_end = 0;
-  int64_t t_cur = row_from(t_off, t_idx, &t_end), x_cur = 0;
-  if (x_off) x_cur = row_from(x_off, x_idx, &x_end);
-  // the row's entries inside [base, base + 64) as this lane's share of the window mask; they are a prefix of the rest
-  auto window = [&](const int32_t* __restrict__ idx, int64_t& cur, int64_t end, int64_t base) __attribute__((always_inline)) {
-    uint64_t m = 0;
-    for (;;) {
-      const int64_t q = cur + lane;
-      const int64_t e = q < end ? (int64_t)idx[q] : INT64_MAX;
-      const bool in = e < base + 64;
-      if (in && e >= base) m |= 1ull << (e - base);
-      const int n_in = __popcll(__ballot(in));
-      cur += n_in;
-      if (n_in < 64) break;
-    }
-    return m;
-  };
+  WaveCursor tc = wave_cursor_at(t_off, t_idx, u, p0), xc;
+  if (x_off) xc = wave_cursor_at(x_off, x_idx, u, p0);
 
   int over = 0;                                              // this lane's candidates above the user's largest positive
   for (int64_t base = p0; base < p1; base += 64) {
@@ -119,11 +87,11 @@ __global__ __launch_bounds__(256) void neumf_rank_count_kernel(const float* __re
     const bool valid = p < p1;
     const int64_t pc = valid ? p : p1 - 1;                   // tail lanes recompute the last item (never read past the list)
 
-    uint64_t m = window(t_idx, t_cur, t_end, base);
-    if (x_cur < x_end) m |= window(x_idx, x_cur, x_end, base);         // (wave-uniform)
+    uint64_t m = wave_cursor_window(tc, t_idx, base, lane);
+    if (xc.cur < xc.end) m |= wave_cursor_window(xc, x_idx, base, lane);         // (wave-uniform)
     const bool skipped = (wave_or64(m) >> lane) & 1;
 
-    const float s = neumf_score<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, W2, b2, W3t, b3, w4, w4mf, b4);
+    const float s = neumf_score<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, t);
     if (valid && dump_probs) dump_probs[u * n_items + p] = s;
 
     // fast paths first (a NaN score fails every compare: nothing); the scores inside [min, max] search the list
@@ -171,27 +139,18 @@ __global__ __launch_bounds__(256) void neumf_rank_count_kernel(const float* __re
   }
 }
 
-template <int W, int ACT>
-void launch_rank_count(hipStream_t st, const Operands& a, const int64_t* t_off, const int32_t* t_idx, const int64_t* x_off, const int32_t* x_idx,
-                       const int64_t* loff, const float* sorted, const int32_t* pcnt, int64_t cap, int64_t cps, int64_t S, int32_t* bins,
-                       int32_t* ties, float* dump) {
-  const dim3 grid((unsigned)ceil_div(a.U, kRecWaves), (unsigned)S);
-  neumf_rank_count_kernel<W, ACT><<<grid, 256, 0, st>>>(a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3, a.tower, a.L, t_off, t_idx, x_off,
-                                                        x_idx, loff, sorted, pcnt, cap, cps, bins, ties, dump);
-}
-
-int rank_count(const char* name, const Operands& a, int n2, int act, const int64_t* t_off, const int32_t* t_idx, const int64_t* x_off,
-               const int32_t* x_idx, const int64_t* list_off, const float* sorted, const int32_t* pcnt, int64_t cap, int32_t* bins, int32_t* ties,
-               float* dump, hipStream_t st) {
+int rank_count(const char* name, const Operands& a, const int64_t* t_off, const int32_t* t_idx, const int64_t* x_off, const int32_t* x_idx,
+               const int64_t* list_off, const float* sorted, const int32_t* pcnt, int64_t cap, int32_t* bins, int32_t* ties, float* dump,
+               hipStream_t st) {
   int64_t S, cps;
   catalog_plan(a.U, a.I, &S, &cps);
-  if (!dispatch_tower(n2, act, [&](auto w, auto ac) {
-        launch_rank_count<decltype(w)::value, decltype(ac)::value>(st, a, t_off, t_idx, x_off, x_idx, list_off, sorted, pcnt, cap, cps, S, bins, ties,
-                                                                    dump);
-      })) {
-    br::set_error("%s: no kernel for n2 = %d", name, n2);
-    return BR_ERR_UNSUPPORTED;
-  }
+  const dim3 grid((unsigned)ceil_div(a.U, kRecWaves), (unsigned)S);
+  if (const int rc = dispatch_tower(name, a.n2, a.act, [&](auto w, auto ac) {
+        neumf_rank_count_kernel<decltype(w)::value, decltype(ac)::value><<<grid, 256, 0, st>>>(
+            a.pu, a.ld_u, a.pit, a.ld_i, a.U, a.I, a.dim, a.n1, a.n3, a.tower, tower_layout(a.n1, a.n2, a.n3), t_off, t_idx, x_off, x_idx,
+            list_off, sorted, pcnt, cap, cps, bins, ties, dump);
+      }))
+    return rc;
   BR_CHECK_LAUNCH(name);
   return BR_OK;
 }
@@ -234,11 +193,11 @@ extern "C" int brNeumfCatalogRanks(const float* pu, int64_t ld_u, int64_t n_user
   hipStream_t st = (hipStream_t)stream;
   launch_rank_init(st, w, ws, out_above, out_tied, n_truth);
   BR_CHECK_LAUNCH("brNeumfCatalogRanks init");
-  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, tower, tower_layout(n1, n2, n3)};
-  if (const int rc = positives("brNeumfCatalogRanks positives", a, n2, act, truth_off, truth_idx, raw, cap, st)) return rc;
+  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n2, n3, act, tower};
+  if (const int rc = neumf_positives("brNeumfCatalogRanks positives", a, truth_off, truth_idx, raw, cap, st)) return rc;
   // one piece per user, where the positives' kernel wrote it: piece_off = list_off = truth_off
   if (const int rc = brAucSortPieces(raw, cap, truth_off, 1, n_users, truth_off, sorted, cap, pcnt, tmp, tmp_bytes, stream)) return rc;
-  if (const int rc = rank_count("brNeumfCatalogRanks count", a, n2, act, truth_off, truth_idx, excl_off, excl_idx, truth_off, sorted, pcnt, cap,
+  if (const int rc = rank_count("brNeumfCatalogRanks count", a, truth_off, truth_idx, excl_off, excl_idx, truth_off, sorted, pcnt, cap,
                                 bins, ties, dump_probs, st))
     return rc;
   const unsigned per_user = (unsigned)ceil_div(n_users, 4);
@@ -261,8 +220,8 @@ extern "C" int brNeumfRankCount(const float* pu, int64_t ld_u, int64_t n_users, 
   if (const int rc = catalog_check_args("brNeumfRankCount", ld_u, n_users, ld_i, n_items, dim, n1, n2, n3, act)) return rc;
   BR_CHECK_ARG(ranks_sizes_ok(n_users, cap), "brNeumfRankCount: cap = %lld: 0 <= cap, cap + n_users < 2^31", (long long)cap);
   if (n_users == 0) return BR_OK;
-  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, tower, tower_layout(n1, n2, n3)};
-  return rank_count("brNeumfRankCount", a, n2, act, skip_off, skip_idx, nullptr, nullptr, list_off, sorted, pcnt, cap, bins, ties, dump_probs,
+  const Operands a{pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n2, n3, act, tower};
+  return rank_count("brNeumfRankCount", a, skip_off, skip_idx, nullptr, nullptr, list_off, sorted, pcnt, cap, bins, ties, dump_probs,
                     (hipStream_t)stream);
 }
 

@@ -13,12 +13,15 @@
 //   - each wave keeps its user's running top-k of its split in registers (entry e = slot e / 64 of lane e % 64, sorted by (score desc,
 //     position asc)); a pair enters only if it beats the k-th entry (one compare); the exclusion list of the user is walked with a
 //     cursor as the item window advances (it is ascending), one 64-bit mask per window;
+//   - the score, the tower view, the cursor and the dispatch over (tower width, activation) are neumf_score.h's, the one text the AUC
+//     (auc_neumf.hip) and the ranks (ranks_neumf.hip) use too: this kernel calls neumf_logit and dumps z and sigmoidf_acc(z);
 //   - a merge launch combines the splits' lists with the same order (ties keep the lower position, as brTopKRows) and pads with
 //     (-inf, -1) where fewer than k candidates remain.
 #include <math.h>
 
 #include "common.h"
 #include "dot_tile.h"
+#include "neumf_score.h"
 #include "neumf_tower.h"
 #include "topk_list.h"
 
@@ -110,29 +113,11 @@ __global__ __launch_bounds__(256) void catalog_topk_kernel(const float* __restri
   const int64_t u = (int64_t)blockIdx.x * kRecWaves + wave;
   if (u >= n_users) return;
   const int64_t split = blockIdx.y;
-  const int64_t p0 = split * chunks_per_split * 64;
-  int64_t p1 = p0 + chunks_per_split * 64;
-  if (p1 > n_items) p1 = n_items;
-
+  const auto [p0, p1] = split_items(split, chunks_per_split, n_items);
   const float* __restrict__ urow = pu + u * ld_u;            // [Pu (b1 included) | user mf]
-  const float* __restrict__ W2 = tower + L.w2;
-  const float* __restrict__ b2 = tower + L.b2;
-  const float* __restrict__ W3t = tower + L.w3t;
-  const float* __restrict__ b3 = tower + L.b3;
-  const float* __restrict__ w4 = tower + L.w4;
-  const float w4mf = tower[L.w4mf], b4 = tower[L.b4];
-
-  // exclusion cursor: first entry of the user's list at or after p0
-  int64_t ex_cur = 0, ex_end = 0;
-  if (ex_off) {
-    int64_t lo = ex_off[u], hi = ex_off[u + 1];
-    ex_end = hi;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)ex_idx[mid] < p0) lo = mid + 1; else hi = mid;
-    }
-    ex_cur = lo;
-  }
+  const TowerView t = tower_view(tower, L);
+  WaveCursor ex;                                             // exclusion cursor: first entry of the user's list at or after p0
+  if (ex_off) ex = wave_cursor_at(ex_off, ex_idx, u, p0);
 
   WaveList list;
   list.init();
@@ -142,47 +127,9 @@ __global__ __launch_bounds__(256) void catalog_topk_kernel(const float* __restri
     const int64_t pc = valid ? p : p1 - 1;                   // tail lanes recompute the last item (never read past the list)
 
     bool excluded = false;
-    if (ex_off) {
-      uint64_t m = 0;
-      for (;;) {                                             // the entries inside [base, base + 64) are a prefix of the rest
-        const int64_t q = ex_cur + lane;
-        const int64_t e = q < ex_end ? (int64_t)ex_idx[q] : INT64_MAX;
-        const bool in = e < base + 64;
-        if (in && e >= base) m |= 1ull << (e - base);
-        const int n_in = __popcll(__ballot(in));
-        ex_cur += n_in;
-        if (n_in < 64) break;
-      }
-      excluded = (wave_or64(m) >> lane) & 1;
-    }
+    if (ex_off) excluded = (wave_or64(wave_cursor_window(ex, ex_idx, base, lane)) >> lane) & 1;
 
-    float acc[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] = b2[j];
-    const float* __restrict__ pcol = pit + pc;
-    float xn = pcol[0];
-#pragma unroll 1
-    for (int i = 0; i < n1; ++i) {                           // the next feature's load is in flight while this one is consumed
-      const float x = xn;
-      xn = pcol[(int64_t)(i + 1 < n1 ? i + 1 : i) * ld_i];
-      const float h = act_apply(urow[i] + x, ACT);
-      const float* __restrict__ w = W2 + (int64_t)i * W;
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc[j] = fmaf(h, w[j], acc[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] = act_apply(acc[j], ACT);   // padded columns: W3' rows are zero there
-    float z = b4;
-    for (int m = 0; m < n3; ++m) {
-      const float* __restrict__ w = W3t + (int64_t)m * W;
-      float s = b3[m];
-#pragma unroll
-      for (int j = 0; j < W; ++j) s = fmaf(acc[j], w[j], s);
-      z = fmaf(act_apply(s, ACT), w4[m], z);
-    }
-    float dot = 0.f;
-    for (int d = 0; d < dim; ++d) dot = fmaf(urow[n1 + d], pcol[(int64_t)(n1 + d) * ld_i], dot);
-    z = fmaf(w4mf, dot, z);
+    const float z = neumf_logit<W, ACT>(urow, pit + pc, ld_i, dim, n1, n3, t);
     const float prob = sigmoidf_acc(z);                      // the engine's head probability (predict)
     if (valid) {
       if (dump_logits) dump_logits[u * n_items + p] = z;
@@ -240,18 +187,6 @@ __global__ __launch_bounds__(256) void topk_rows_exclude_kernel(const float* __r
     prev_s = sel_s; prev_i = sel_i;
     __syncthreads();
   }
-}
-
-template <int W>
-void launch_catalog_topk(dim3 grid, hipStream_t st, const float* pu, int64_t ld_u, const float* pit, int64_t ld_i, int64_t U, int64_t I,
-                         int dim, int n1, int n3, int act, const float* tower, const TowerLayout& L, const int64_t* ex_off,
-                         const int32_t* ex_idx, int k, int64_t cps, int64_t S, float* ps, int32_t* pp, float* dl, float* dp) {
-  if (act == BR_ACT_SIGMOID)
-    catalog_topk_kernel<W, BR_ACT_SIGMOID><<<grid, 256, 0, st>>>(pu, ld_u, pit, ld_i, U, I, dim, n1, n3, tower, L, ex_off, ex_idx, k, cps, S, ps, pp, dl, dp);
-  else if (act == BR_ACT_RELU)
-    catalog_topk_kernel<W, BR_ACT_RELU><<<grid, 256, 0, st>>>(pu, ld_u, pit, ld_i, U, I, dim, n1, n3, tower, L, ex_off, ex_idx, k, cps, S, ps, pp, dl, dp);
-  else
-    catalog_topk_kernel<W, BR_ACT_LINEAR><<<grid, 256, 0, st>>>(pu, ld_u, pit, ld_i, U, I, dim, n1, n3, tower, L, ex_off, ex_idx, k, cps, S, ps, pp, dl, dp);
 }
 
 }  // namespace
@@ -329,14 +264,11 @@ extern "C" int brNeumfCatalogTopK(const float* pu, int64_t ld_u, const float* pi
   const TowerLayout L = tower_layout(n1, n2, n3);
   const dim3 grid((unsigned)ceil_div(n_users, kRecWaves), (unsigned)S);
   hipStream_t st = (hipStream_t)stream;
-#define BR_CATALOG_W(WW) \
-  case WW: launch_catalog_topk<WW>(grid, st, pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, act, tower, L, excl_off, excl_idx, k, cps, S, ps, pp, dump_logits, dump_probs); break;
-  switch (tower_width(n2)) {
-    BR_CATALOG_W(8) BR_CATALOG_W(16) BR_CATALOG_W(24) BR_CATALOG_W(32) BR_CATALOG_W(40) BR_CATALOG_W(48) BR_CATALOG_W(56)
-    BR_CATALOG_W(64) BR_CATALOG_W(96) BR_CATALOG_W(128)
-    default: br::set_error("brNeumfCatalogTopK: no kernel for n2 = %d", n2); return BR_ERR_UNSUPPORTED;
-  }
-#undef BR_CATALOG_W
+  if (const int rc = dispatch_tower("brNeumfCatalogTopK", n2, act, [&](auto w, auto ac) {
+        catalog_topk_kernel<decltype(w)::value, decltype(ac)::value><<<grid, 256, 0, st>>>(
+            pu, ld_u, pit, ld_i, n_users, n_items, dim, n1, n3, tower, L, excl_off, excl_idx, k, cps, S, ps, pp, dump_logits, dump_probs);
+      }))
+    return rc;
   BR_CHECK_LAUNCH("brNeumfCatalogTopK");
   catalog_merge_kernel<<<(unsigned)ceil_div(n_users, kRecWaves), 256, 0, st>>>(ps, pp, n_users, S, k, out_scores, out_index);
   BR_CHECK_LAUNCH("brNeumfCatalogTopK merge");

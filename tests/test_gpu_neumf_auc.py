@@ -2,7 +2,7 @@
 NeuMFModel.full_auc / mean_average_precision_k).
 
 The kernel-level tests allow no tolerance: the per-user AUC equals brFullAuc of the dumped probabilities BIT FOR BIT with NaN in the
-same places, the dump equals brNeumfCatalogTopK's dump_probs bit for bit (what keeps the two copies of the scoring loop the same), and W
+same places, the dump equals brNeumfCatalogTopK's dump_probs bit for bit (one scoring function, csrc/neumf_score.h, reached from both kernels), and W
 owners over parts of the candidates give the single launch's floats.  Where another summation order enters (float64, the pair path) the
 allowed difference per user is derived in the test from the scores themselves (_flip_bound).
 
@@ -156,7 +156,7 @@ def test_bit_exact_against_full_auc_of_the_dump(dev, variant, dim, hidden, idt):
     assert _equal(auc, ops.full_auc(dump, toff, tidx))
     assert _equal(auc, ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx))
     probs = ops.neumf_catalog_topk(pu, pit, tower, tail[0], tail[1], tail[2], 10, dump_probs=True)[2]
-    assert _same_bits(dump, probs)                                    # the two copies of the scoring loop are one function
+    assert _same_bits(dump, probs)                                    # one scoring function (neumf_logit) reached from two kernels
     assert R.same_bits(auc.cpu().numpy(), R.oracle_auc(dump.cpu().numpy(), off, idx, np.arange(I)))
     # the engine surface returns the same
     e_auc, e_dump = eng.full_auc(users, (toff, tidx), items=torch.as_tensor(items, dtype=idt, device=dev), dump_probs=True)

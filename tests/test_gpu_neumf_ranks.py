@@ -187,6 +187,44 @@ def test_plan_independence(dev):
     assert _same(part, (full[0][sel], full[1][sel]))
 
 
+# --------------------------------------------------------------------------------------------------------------- 4b: the wave cursor
+def test_rows_that_fill_or_straddle_a_window(dev):
+    """the one cursor of the three catalogue kernels (neumf_score.h WaveCursor) on rows that are empty, sit at either end, fill the
+    64-item window [64, 128), cross a window boundary or name every item, each as the truth row and as the exclusion row; 200 items are
+    three full windows and a tail of 8, and the plan gives every window its own split, so all cursors but the first start inside a row"""
+    ops = _m("ops")
+    I, k = 200, 64
+    rows = [np.empty(0, np.int64), np.array([0]), np.array([I - 1]), np.arange(64, 128), np.arange(60, 71), np.arange(I)]
+    U = len(rows)
+    assert U % 4
+    ws = int(ops._lib.load().brNeumfCatalogTopKWorkspaceBytes(U, I, k))       # 2 x (U x splits x k) entries of 4 bytes, a multiple of 256
+    assert ws // (2 * U * k * 4) == 4 and ws % (2 * U * k * 4) == 0              # 4 splits
+    spec, p, eng = N._engine(dev, "A", 10, 50, I, seed=21)
+    users = torch.arange(U, dtype=torch.int32, device=dev)
+    pu, pit, tower, tail = N._operands(eng, users, torch.arange(I, dtype=torch.int32, device=dev))
+
+    def csr(shift):
+        r = rows[shift:] + rows[:shift]
+        return N._dev_csr(np.concatenate([[0], np.cumsum([len(x) for x in r])]), np.concatenate(r), dev)
+
+    toff, tidx = csr(0)
+    auc, dump = ops.neumf_catalog_auc(pu, pit, tower, *tail, toff, tidx, dump_probs=True)
+    assert N._equal(auc, ops.full_auc(dump, toff, tidx))
+    assert torch.equal(torch.isnan(auc).cpu(), torch.tensor([True, False, False, False, False, True]))
+    for shift in (0, 3):                                                       # the rows excluded for their own user, and for another
+        ex = csr(shift)
+        ts, ti, probs = ops.neumf_catalog_topk(pu, pit, tower, *tail, k, exclude=ex, dump_probs=True)
+        assert N._same_bits(probs, dump)
+        assert _same((ts, ti), ops.topk_rows(probs, k, exclude=ex)), shift
+        full = (U - 1 - shift) % U                                             # the user whose exclusion row names every item
+        assert (ts[full] == -float("inf")).all() and (ti[full] == -1).all()
+        for x in (None, ex):
+            above, tied, d = ops.neumf_catalog_ranks(pu, pit, tower, *tail, toff, tidx, exclude=x, dump_probs=True)
+            assert N._same_bits(d, dump)
+            assert _same((above, tied), D._count(dump, toff, tidx, x)), (shift, x is not None)
+    eng.check_ids()
+
+
 # --------------------------------------------------------------------------------------------------------------- 5: the phase entries
 def _through_owners(dev, W, items, eng, users, off, idx, xoff, xidx, idt, dump=None):
     """ranks_at_owners by hand over the W parts of `items`: every owner's positives, the full lists, neumf_rank_count per part into
