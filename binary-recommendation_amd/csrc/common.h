@@ -106,6 +106,21 @@ __device__ __forceinline__ float sigmoidf_acc(float x) {
   float r = 1.0f / (1.0f + e);
   return x >= 0.f ? r : e * r;
 }
+// sigmoidf_acc(x) and its complement 1 - sigmoid(x) = sigmoid(-x) from the same e and r: the complement formed as 1.f - s is quantised
+// in steps of 2^-24 once s sits next to 1 (x > 0: 1e-3 relative at x = 8, exactly 0 from x = 17 on), e * r keeps ~3 roundings at every x
+__device__ __forceinline__ void sigmoid_pair(float x, float& s, float& c) {
+  float e = expf(-fabsf(x));
+  float r = 1.0f / (1.0f + e);
+  const float er = e * r;
+  s = x >= 0.f ? r : er;
+  c = x >= 0.f ? er : r;
+}
+
+// an id outside its table: OR the range bit into the step's error flag (a capacity bit raised earlier stays; an atomicOr from a side
+// stream is not overwritten).  Error path only.  The wave-per-row lookups call it BEHIND their loads (lookup_wave.h LOOKUP WAITS).
+__device__ __forceinline__ void flag_range(int* err, bool ok, bool writer) {
+  if (!ok && err && writer) atomicOr(err, BR_ERRFLAG_RANGE);
+}
 
 __device__ __forceinline__ float act_apply(float z, int act) {
   if (act == BR_ACT_SIGMOID) return sigmoidf_hw(z);

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherArgs a, int dim,
   for (int t = 0; t < NT; ++t) {
     id[t] = load_id(reinterpret_cast<const IdT*>(a.ids[t]), b);
     ok[t] = (uint64_t)id[t] < (uint64_t)a.rows[t];
-    if (!ok[t] && err && lir == 0) *err = 1;
+    flag_range(err, ok[t], lir == 0);
   }
   for (int c = lir; c < chunks; c += lpr) {
     V v[NT];
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void gather_rows_seg_kernel(GatherSegJobs jobs
   const int64_t p = seg_phys(b, seg_len, seg_stride, jb.seg_off);
   const int64_t id = load_id((const IdT*)jb.ids, p);
   const bool ok = (uint64_t)id < (uint64_t)jb.rows;
-  if (!ok && err && lir == 0) *err = 1;
+  flag_range(err, ok, lir == 0);
   for (int c = lir; c < chunks; c += lpr)
     vstore<VEC>(jb.out + p * ld_out + c * VEC, ok ? vload<VEC>(jb.table + id * dim + c * VEC) : vzero<VEC>());
 }
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void neumf_embed_fwd_kernel(
   if (!live) b = batch - 1;
   const int64_t u = load_id(users, b), i = load_id(items, b);
   const bool uok = (uint64_t)u < (uint64_t)user_rows, iok = (uint64_t)i < (uint64_t)item_rows;
-  if ((!uok || !iok) && err && lir == 0) *err = 1;
+  flag_range(err, uok && iok, lir == 0);
   float* xrow = x0 + b * (2 * (int64_t)dim);
   const int uoff = item_first ? dim : 0, ioff = item_first ? 0 : dim;
   float s = 0.f;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void neumf_embed_fwd_deferred_kernel(
   if (!live) b = batch - 1;
   int64_t u = load_id(users, b), i = load_id(items, b);
   const bool uok = (uint64_t)u < (uint64_t)user_rows, iok = (uint64_t)i < (uint64_t)item_rows;
-  if ((!uok || !iok) && err && lir == 0) *err = 1;
+  flag_range(err, uok && iok, lir == 0);
   if (!uok) u = 0;
   if (!iok) i = 0;
   const uint32_t t = ss->step;                       // the step being computed: rows must include steps <= t-1
@@ -230,7 +230,8 @@ __global__ __launch_bounds__(256) void gather_rows_deferred_kernel(
   if (b >= n) return;
   int64_t r = load_id(ids, b);
   const bool ok = (uint64_t)r < (uint64_t)rows;
-  if (!ok) { if (err && lir == 0) *err = 1; r = 0; }
+  flag_range(err, ok, lir == 0);
+  if (!ok) r = 0;
   const uint32_t t = ss->step, seen = (uint32_t)last[r];
   for (int c = lir; c < chunks; c += lpr) {
     const int64_t off = r * dim + c * VEC;
@@ -352,9 +353,9 @@ __global__ __launch_bounds__(256) void bpr_fwd_bwd_kernel(
   const int64_t u = load_id(users, b), p = load_id(pos, b), n = load_id(neg, b);
   const bool uok = (uint64_t)u < (uint64_t)user_rows;
   const bool pok = (uint64_t)p < (uint64_t)item_rows, nok = (uint64_t)n < (uint64_t)item_rows;
-  if (!(uok && pok && nok) && err && lir == 0) *err = 1;
+  flag_range(err, uok && pok && nok, lir == 0);
   float sp = 0.f, sn = 0.f;
-  // single-pass fast path keeps the three rows in registers (chunks <= lpr: dim <= 256)
+  // single-pass fast path keeps the three rows in registers (chunks <= lpr = 64 lanes: dim <= 256 at VEC 4, 128 at VEC 2, 64 at VEC 1)
   const bool one_pass = chunks <= lpr;
   V eu = vzero<VEC>(), ep = vzero<VEC>(), en = vzero<VEC>();
   if (one_pass) {
@@ -377,9 +378,9 @@ __global__ __launch_bounds__(256) void bpr_fwd_bwd_kernel(
   sp = rowgroup_sum(sp, lpr);
   sn = rowgroup_sum(sn, lpr);
   const float x = sp - sn;
-  const float s = sigmoidf_acc(x);
-  const float l = 1.f - s;
-  const float dx = -s * (1.f - s) * inv_batch;
+  float s, l;                        // l = 1 - sigmoid(x) without the cancellation (common.h sigmoid_pair)
+  sigmoid_pair(x, s, l);
+  const float dx = -s * l * inv_batch;
   if (live) {
     if (per_triplet && lir == 0) per_triplet[b] = l;
     float* gu = g_user + b * dim;
@@ -639,7 +640,7 @@ extern "C" int brGatherRowsPairSeg(const float* table_a, int64_t rows_a, const f
 extern "C" int brMfGradInplace(float* stash_user, float* stash_item, int64_t ld, const float* ddot, int64_t batch, int dim, brStream stream) {
   BR_CHECK_ARG(stash_user && stash_item && ddot && dim >= 1 && ld >= dim && batch >= 0, "brMfGradInplace: bad args");
   if (batch == 0) return BR_OK;
-  const RowGeom g = row_geom_ld(dim, vec_width({ld}));
+  const RowGeom g = row_geom_ld(dim, vec_width({ld}, {stash_user, stash_item}));
   const unsigned grid = (unsigned)ceil_div(batch * g.chunks, 256);
   BR_DISPATCH_VEC(g.vec, (mf_grad_inplace_kernel<VEC><<<grid, 256, 0, (hipStream_t)stream>>>(stash_user, stash_item, ld, ddot, batch, g.chunks)));
   BR_CHECK_LAUNCH("brMfGradInplace");

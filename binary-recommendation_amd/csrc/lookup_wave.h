@@ -54,11 +54,7 @@ __device__ __forceinline__ ReplayK load_k_id_pair(const StepStateDev* ss, const 
   i = items ? (int64_t)ii : b;
   return k;
 }
-// an id outside its table: OR the range bit into the step's error flag (a capacity bit raised earlier stays).  Called BEHIND the
-// wave's loads.
-__device__ __forceinline__ void flag_range(int* err, bool ok, bool writer) {
-  if (!ok && err && writer) atomicOr(err, BR_ERRFLAG_RANGE);
-}
+// (flag_range - an id outside its table ORs the range bit into the step's error flag - is in common.h; here it is called BEHIND the wave's loads)
 
 // pair b (wave-uniform) of embed_dim = 32 * VEC: a lane owns VEC columns of the fused user row and the same columns of the item row
 template <typename IdT, int VEC>

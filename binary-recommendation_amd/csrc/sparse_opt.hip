@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void scatter_add_kernel(float* __restrict__ gt
   const int d = (int)(e - b * dim);
   const int64_t id = load_id(ids, b);
   if ((uint64_t)id >= (uint64_t)table_rows) {
-    if (err) *err = 1;
+    flag_range(err, false, d == 0);
     return;
   }
   atomicAdd(gt + id * dim + d, rows[e]);

@@ -231,6 +231,14 @@ def neumf_embed_backward(user_mf, item_mf, users, items, item_first, dx0, ddot, 
           "brNeumfEmbedBackward")
 
 
+def mf_grad_inplace(stash_user, stash_item, ddot):
+    """(u, i) -> (ddot * i, ddot * u) in place on the MF rows the forward stashed: (B, dim) views of one row stride (brMfGradInplace)."""
+    if stash_user.shape != stash_item.shape or stash_user.stride(0) != stash_item.stride(0) or stash_user.shape[0] < ddot.shape[0]:
+        raise ValueError("stashes must share a shape and a row stride and hold the batch")
+    check(_lib.load().brMfGradInplace(_p(stash_user), _p(stash_item), stash_user.stride(0), _f32(ddot, "ddot").data_ptr(), ddot.shape[0],
+                                      stash_user.shape[1], _stream()), "brMfGradInplace")
+
+
 # ------------------------------------------------------------------------------ L3 BPR
 def bpr_forward_backward(user_table, item_table, users, pos, neg, inv_batch, loss_sum, g_user, g_item,
                          per_triplet=None, err_flag=None):

@@ -478,9 +478,9 @@ def bpr_step_grads(user_table, item_table, u, pos, neg, dt=np.float64):
     eu, ep, en = f(gather_rows(user_table, u)), f(gather_rows(item_table, pos)), f(gather_rows(item_table, neg))
     x = row_dot(eu, ep) - row_dot(eu, en)
     s = sigmoid(x)
-    l = 1.0 - s
+    l = sigmoid(-x)                # = 1 - s without the cancellation (1.0 - s is quantised in steps of 1e-16 and is 0 from x = 37 on)
     B = x.shape[0]
-    dx = (-s * (1.0 - s) / B).astype(dt)
+    dx = (-s * l / B).astype(dt)
     gu = dx[:, None] * (ep - en)
     gp = dx[:, None] * eu
     gn = -dx[:, None] * eu

@@ -68,6 +68,8 @@ def test_argument_errors_are_reported_not_crashed(built):
     # replayed-rows optimizer entry and the graph-resident probe
     assert h.brAdamRowsSortedDeferredReplayed(None, None, None, None, 10, 64, None, 0, None, 4, None, 64, None, 0, 0, None, 64, None, 0.9, 0.999, 1e-7, None, None) == -1
     assert b"Replayed" in h.brGetLastError()
+    # the in-place MF gradient: a row stride below the row width (0x1000 stands for device memory, never dereferenced)
+    assert h.brMfGradInplace(0x1000, 0x1000, 63, 0x1000, 8, 64, None) == -1 and b"brMfGradInplace" in h.brGetLastError()
     assert h.brProbeGraphNodes() == 0 and h.brProbeGraphArm(None, 0) == -1 and h.brProbeGraphRead(0, None) == -1
 
 
