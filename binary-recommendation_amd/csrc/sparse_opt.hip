@@ -635,7 +635,8 @@ extern "C" int brSegmentSumRows(const void* sorted_ids, int id_type, const int32
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brSegmentSumRows: bad id_type");
   if (n == 0) return BR_OK;
   BR_CHECK_ARG(sorted_ids && sorted_pos && row_grads && out_rows && dim >= 1 && ldg >= dim, "brSegmentSumRows: bad args");
-  const RowGeom g = row_geom_ld(dim, ldg);
+  // widest vector that the source's stride and every base the kernels address by vector honour (rows of out / seg_ws are dim apart)
+  const RowGeom g = row_geom_ld(dim, vec_width({ldg, dim}, {row_grads, out_rows, seg_ws}));
   const unsigned grid = (unsigned)ceil_div(n, 256 >> g.lpr_log2);
   hipStream_t s = (hipStream_t)stream;
   if (seg_ws) {
@@ -945,7 +946,7 @@ extern "C" int brAdagradRowsSorted(float* table, float* acc, int64_t table_rows,
   if (n == 0) return BR_OK;
   BR_CHECK_ARG(table && acc && sorted_ids && sorted_pos && row_grads && dim >= 1 && ldg >= dim && table_rows > 0,
                "brAdagradRowsSorted: bad args");
-  const RowGeom g = row_geom_ld(dim, ldg);
+  const RowGeom g = row_geom_ld(dim, vec_width({ldg, dim}, {row_grads, table, acc, seg_ws}));
   const unsigned grid = (unsigned)ceil_div(n, 256 >> g.lpr_log2);
   hipStream_t s = (hipStream_t)stream;
   if (seg_ws) {

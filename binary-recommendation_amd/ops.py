@@ -399,6 +399,22 @@ def adam_rows_sorted(table, m, v, index: RowIndex, row_grads, ldg, alpha_t, beta
                                        _p(mark), index.seg_ws(table.shape[1]).data_ptr(), _stream()), "brAdamRowsSorted")
 
 
+def adam_rows_sorted_pair(tab_a, m_a, v_a, idx_a: RowIndex, g_a, ldg_a, hi_a, ldg_hi_a, tab_b, m_b, v_b, idx_b: RowIndex, g_b, ldg_b, hi_b, ldg_hi_b,
+                          split, alpha_t, beta1=0.9, beta2=0.999, eps=1e-7, hi_scale=None, mark_a=None, mark_b=None):
+    """two swept tables of one row width in ONE launch (brAdamRowsSortedPair): columns [0, split) of table x take their gradients from g_x,
+    [split, dim) from hi_x times hi_scale[position] (n floats, or None: as stored); both indexes hold the same number of positions."""
+    dim = tab_a.shape[1]
+    if tab_b.shape[1] != dim or idx_a.id_type != idx_b.id_type or idx_a.n != idx_b.n:
+        raise ValueError("adam_rows_sorted_pair: the two tables must share dim, id type and the number of positions")
+    check(_lib.load().brAdamRowsSortedPair(
+        _f32(tab_a, "tab_a").data_ptr(), _f32(m_a, "m_a").data_ptr(), _f32(v_a, "v_a").data_ptr(), tab_a.shape[0], idx_a.sorted_ids.data_ptr(),
+        idx_a.sorted_pos.data_ptr(), g_a.data_ptr(), int(ldg_a), hi_a.data_ptr(), int(ldg_hi_a), _p(mark_a), None,
+        _f32(tab_b, "tab_b").data_ptr(), _f32(m_b, "m_b").data_ptr(), _f32(v_b, "v_b").data_ptr(), tab_b.shape[0], idx_b.sorted_ids.data_ptr(),
+        idx_b.sorted_pos.data_ptr(), g_b.data_ptr(), int(ldg_b), hi_b.data_ptr(), int(ldg_hi_b), _p(mark_b), None,
+        dim, idx_a.id_type, idx_a.n, int(split), _p(hi_scale), None, float(alpha_t), float(beta1), float(beta2), float(eps),
+        idx_a.seg_ws(dim).data_ptr(), idx_b.seg_ws(dim).data_ptr(), _stream()), "brAdamRowsSortedPair")
+
+
 def adam_dense_sweep(table, m, v, alpha_t, beta1=0.9, beta2=0.999, eps=1e-7, mark=None):
     check(_lib.load().brAdamDenseSweep(_f32(table, "table").data_ptr(), _f32(m, "m").data_ptr(), _f32(v, "v").data_ptr(),
                                        table.shape[0], table.shape[1], float(alpha_t), float(beta1), float(beta2), float(eps),
