@@ -28,8 +28,13 @@ struct StepStateDev {
   float pow1[BR_ALPHA_RING], pow2[BR_ALPHA_RING];   // beta1^k, beta2^k (k < BR_ALPHA_RING): the moments of a lag of k steps in one product
 };
 // arguments of the step-state advance (step += 1, alpha_t, ring entry, the step's double scratch zeroed): a launch of its own
-// (brStepStateAdvance) or one extra workgroup of the chunk-rank launch (neumf_step.cpp defer_advance)
-struct StepAdvance { StepStateDev* st = nullptr; double lr = 0, b1 = 0, b2 = 0; double* zero = nullptr; int64_t n_zero = 0; };
+// (brStepStateAdvance), one extra workgroup of the chunk-rank launch (neumf_step.cpp defer_advance) or, in the later steps of a
+// multi-step group, of the segment-partials launch.  zero_more: the double scratch of the group's later steps (n_zero doubles each),
+// cleared by further workgroups of the head's chunk-rank launch (step_state_zero_more)
+struct StepAdvance {
+  StepStateDev* st = nullptr; double lr = 0, b1 = 0, b2 = 0; double* zero = nullptr; int64_t n_zero = 0;
+  double* zero_more[BR_GROUP_MAX - 1] = {}; int n_more = 0;
+};
 const StepStateDev* current_step_state();
 void set_current_step_state(const StepStateDev* p);
 void probe_split(int first_tag, hipStream_t s);   // launch probe of the step driver (neumf_step.cpp), a no-op unless a record is open

@@ -87,6 +87,8 @@ struct AdamPairCall {
   float *seg_ws_a, *seg_ws_b;
   // deferred tables: the rows as the step's lookup replayed them, by position (columns [0,split) | [split,dim)), or null
   const float *th_lo_a = nullptr, *th_hi_a = nullptr, *th_lo_b = nullptr, *th_hi_b = nullptr; int64_t ld_th = 0;
+  // a later step of a multi-step group: the step state is advanced by one extra workgroup of the segment-partials launch (which must exist)
+  const StepAdvance* adv = nullptr;
 };
 // fin != NULL: the launch may also carry the dense finalize as riders of its grid; *fin_done tells whether it did
 struct FinalArgs;
@@ -99,7 +101,13 @@ struct IndexPairArgs {
   void* sorted_ids_b; int32_t* sorted_pos_b; void* ws_b; int64_t ws_b_bytes;
 };
 bool lookup_with_index_supported(int dim, int64_t n, int64_t upper_a, int64_t upper_b, int64_t ld_stash, const void* x0, const void* stash_a, const void* stash_b);
-int lookup_with_index(const LookupArgs& la, int dim, int id_type, const IndexPairArgs& ix, brStream stream, const StepAdvance* adv = nullptr);
+// the later steps of a multi-step group, whose chunk sorts and ranks ride with the head step's (n: at most BR_GROUP_MAX - 1)
+struct GroupIndexArgs { int n = 0; const void* users[BR_GROUP_MAX - 1]; const void* items[BR_GROUP_MAX - 1]; IndexPairArgs ix[BR_GROUP_MAX - 1]; };
+int lookup_with_index(const LookupArgs& la, int dim, int id_type, const IndexPairArgs& ix, brStream stream, const StepAdvance* adv = nullptr,
+                      const GroupIndexArgs* later = nullptr);
+int lookup_index_chunks(int64_t n);      // chunks per id stream of the fused lookup + sort launch
+// gather.hip: the plain one-wave-per-pair deferred lookup (the shapes of lookup_with_index_supported), step_add / spec as given
+int lookup_wave_launch(const LookupArgs& la, int dim, int id_type, brStream stream);
 
 int dense_backward_fused(const BwdArgs& a, hipStream_t s);    // BR_ERR_UNSUPPORTED when the LDS image does not fit
 int dense_bwd_fused_grid(int64_t batch);                      // workgroups = slabs written

@@ -6,6 +6,7 @@
 #include "rows.h"
 #include "adam_math.h"
 #include "lookup_wave.h"
+#include "dense.h"
 
 namespace br {
 
@@ -507,6 +508,17 @@ extern "C" int brNeumfEmbedForwardStash(const float* user_mlp, const float* item
   return BR_OK;
 }
 
+// the one-wave-per-pair launch (the caller checked the shapes: wave_pair_vec(dim) != 0, strides and bases aligned to it)
+int br::lookup_wave_launch(const LookupArgs& la, int dim, int id_type, brStream stream) {
+  const int wvec = wave_pair_vec(dim);
+  BR_CHECK_ARG(wvec == 2 || wvec == 4, "lookup_wave_launch: embed_dim 64 or 128");
+  const unsigned wgrid = (unsigned)ceil_div(la.batch, 4);
+  hipStream_t s = (hipStream_t)stream;
+  BR_DISPATCH_ID(id_type, { if (wvec == 2) neumf_embed_fwd_deferred_wave_kernel<IdT, 2><<<wgrid, 256, 0, s>>>(la); else neumf_embed_fwd_deferred_wave_kernel<IdT, 4><<<wgrid, 256, 0, s>>>(la); });
+  BR_CHECK_LAUNCH("brNeumfEmbedForwardDeferred(wave)");
+  return BR_OK;
+}
+
 extern "C" int brNeumfEmbedForwardDeferred(const float* user_tab, const float* user_m, const float* user_v, const int32_t* user_last,
                                            const float* item_tab, const float* item_m, const float* item_v, const int32_t* item_last,
                                            int64_t user_rows, int64_t item_rows, const void* users, const void* items, int id_type,
@@ -526,12 +538,9 @@ extern "C" int brNeumfEmbedForwardDeferred(const float* user_tab, const float* u
   const int wvec = wave_pair_vec(dim);      // (units of 32 floats: a lane owns the same columns of the user row and the item row)
   if (wave_rows_enabled() && wvec && ld_stash % wvec == 0 &&
       ((reinterpret_cast<uintptr_t>(stash_user) | reinterpret_cast<uintptr_t>(stash_item) | reinterpret_cast<uintptr_t>(x0)) & (4 * wvec - 1)) == 0) {
-    const unsigned wgrid = (unsigned)ceil_div(batch, 4);
     const LookupArgs la{user_tab, user_m, user_v, user_last, item_tab, item_m, item_v, item_last, user_rows, item_rows, users, items, batch, item_first, ss, h,
                         x0, dot, stash_user, stash_item, ld_stash, err_flag};
-    BR_DISPATCH_ID(id_type, { if (wvec == 2) neumf_embed_fwd_deferred_wave_kernel<IdT, 2><<<wgrid, 256, 0, s>>>(la); else neumf_embed_fwd_deferred_wave_kernel<IdT, 4><<<wgrid, 256, 0, s>>>(la); });
-    BR_CHECK_LAUNCH("brNeumfEmbedForwardDeferred(wave)");
-    return BR_OK;
+    return lookup_wave_launch(la, dim, id_type, stream);
   }
   BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (neumf_embed_fwd_deferred_kernel<IdT, VEC><<<grid, 256, 0, s>>>(
                                                      user_tab, user_m, user_v, user_last, item_tab, item_m, item_v, item_last, user_rows, item_rows, (const IdT*)users,

@@ -201,6 +201,22 @@ extern "C" int64_t brNeumfStepSlabFloats(int64_t batch, int dim, int n1, int n2,
 
 static int step_run_impl(const brNeumfStep* s, uint32_t ph, brStream stream);
 
+// Multi-step groups whose index is built at the head (include/binrec.h brNeumfStep.group_size): the shapes.  Exactly where a training
+// call with every phase takes the fused lookup + index launch AND defers the step-state advance into the chunk-rank launch, with the
+// segment partials there to carry the advance of the later steps.
+extern "C" int64_t brNeumfGroupSetSizeof(void) { return (int64_t)sizeof(brNeumfGroupSet); }
+static bool group_index_shape_ok(const brNeumfStep* s, int steps) {
+  return steps >= 2 && steps <= BR_GROUP_MAX && s->training && s->adam_dense == 2 && s->step_state && s->user_last && s->item_last &&
+         (s->dropout <= 0.f || s->keep_ready) && s->u_seg_ws && s->i_seg_ws && s->dim >= 1 &&
+         br::lookup_with_index_supported(s->dim, s->batch, s->user_rows, s->item_rows, 2 * s->dim, s->x0, s->g_user + s->dim, s->g_item + s->dim);
+}
+extern "C" int brNeumfGroupIndexPlan(const brNeumfStep* s, int steps) {
+  if (!s) return 0;
+  const char* e = getenv("BR_GROUP_INDEX");      // (read on every call, like BR_FUSED_SORT: one process can capture both forms)
+  if ((e && e[0] == '0') || !group_index_shape_ok(s, steps)) return 0;
+  return 2 * br::lookup_index_chunks(s->batch) * steps;
+}
+
 extern "C" int brNeumfStepRun(const brNeumfStep* s, uint32_t ph, brStream stream) {
   BR_CHECK_ARG(s != nullptr, "brNeumfStepRun: null struct");
   br::set_current_step_state(reinterpret_cast<const br::StepStateDev*>(s->step_state));
@@ -268,6 +284,17 @@ static int step_run_impl(const brNeumfStep* s, uint32_t ph, brStream stream) {
   // state behind the lookup (which then computes its step as ss->step + 1) - one launch less in the chain
   const bool need_advance = (ph & BR_PH_FWD1) && (ph & BR_PH_EMBED) && train && s->step_state;
   const bool defer_advance = need_advance && fused_index && (s->dropout <= 0.f || s->keep_ready);
+  // a step of a multi-step group whose index the head builds (include/binrec.h group_size): head = the two launches below over the
+  // streams of every step; a later step = the plain lookup, and the advance as a workgroup of its segment-partials launch
+  const bool grouped = s->group_size != 0;
+  if (grouped) {
+    BR_CHECK_ARG((ph & BR_PH_ALL) == BR_PH_ALL && fused_index && defer_advance && group_index_shape_ok(s, s->group_size) && s->group_sets &&
+                     s->group_pos >= 0 && s->group_pos < s->group_size,
+                 "brNeumfStepRun: group_size set on a call that brNeumfGroupIndexPlan does not cover");
+  }
+  const bool group_later = grouped && s->group_pos > 0;
+  br::StepAdvance adv_later;
+  if (group_later) { adv_later.st = reinterpret_cast<br::StepStateDev*>(s->step_state); adv_later.lr = s->lr; adv_later.b1 = s->beta1; adv_later.b2 = s->beta2; }
   if (need_advance && !defer_advance)
     RUN(BR_TAG_STEP_STATE, brStepStateAdvance(s->step_state, s->lr, s->beta1, s->beta2, s->dstat, n_dstat, stream));
   // dropout keep-bit planes of the three sites [2D | n1 | n2], filled once per step (after the step counter advanced)
@@ -317,9 +344,24 @@ static int step_run_impl(const brNeumfStep* s, uint32_t ph, brStream stream) {
         la2.step_add = 1;
         adv.st = reinterpret_cast<br::StepStateDev*>(s->step_state); adv.lr = s->lr; adv.b1 = s->beta1; adv.b2 = s->beta2; adv.zero = s->dstat; adv.n_zero = n_dstat;
       }
+      br::GroupIndexArgs later;
+      if (grouped && !group_later) {      // head: the streams and the scratch of steps 1 .. group_size - 1 ride along
+        later.n = s->group_size - 1;
+        adv.n_more = later.n;
+        for (int k = 0; k < later.n; ++k) {
+          const brNeumfGroupSet& g = s->group_sets[k + 1];
+          BR_CHECK_ARG(g.dstat && g.dstat != s->dstat, "brNeumfStepRun: every step of a group needs a dstat of its own");
+          later.users[k] = g.users; later.items[k] = g.items;
+          later.ix[k] = br::IndexPairArgs{g.u_sorted_ids, g.u_sorted_pos, g.u_ws, s->u_ws_bytes, g.i_sorted_ids, g.i_sorted_pos, g.i_ws, s->i_ws_bytes};
+          adv.zero_more[k] = g.dstat;
+        }
+      }
       // (its first launch is retagged EMBED_FWD by probe_split; under capture with EMBED_FWD selected the record nodes bracket that launch)
       const int ltag = (g_gp.sel == BR_TAG_EMBED_FWD && capturing(hs)) ? BR_TAG_EMBED_FWD : BR_TAG_INDEX_USER;
-      RUN(ltag, br::lookup_with_index(la2, D, s->id_type, ix, stream, defer_advance ? &adv : nullptr));
+      if (group_later)     // the head built this step's index and cleared its scratch; the advance rides in the partials launch below
+        RUN(BR_TAG_EMBED_FWD, br::lookup_wave_launch(la2, D, s->id_type, stream));
+      else
+        RUN(ltag, br::lookup_with_index(la2, D, s->id_type, ix, stream, defer_advance ? &adv : nullptr, later.n ? &later : nullptr));
     } else if ((ph & BR_PH_EMBED) && deferred && train)
       RUN(BR_TAG_EMBED_FWD, brNeumfEmbedForwardDeferred(s->user_tab, s->user_m, s->user_v, s->user_last, s->item_tab, s->item_m, s->item_v, s->item_last,
                               s->user_rows, s->item_rows, s->users, s->items, s->id_type, D, B, s->item_first, s->step_state, s->beta1, s->beta2,
@@ -451,7 +493,8 @@ static int step_run_impl(const brNeumfStep* s, uint32_t ph, brStream stream) {
           deferred ? s->item_last : nullptr, 2 * D, s->id_type, B, D, fuse_mf ? s->ddot : nullptr, s->step_state, s->alpha_t, s->beta1, s->beta2, s->adam_eps,
           s->u_seg_ws, s->i_seg_ws,
           // the rows as this step's lookup replayed them: MLP halves in x0, MF halves in the stashes (both untouched since)
-          fuse_mf ? s->x0 + uoff : nullptr, fuse_mf ? s->g_user + D : nullptr, fuse_mf ? s->x0 + ioff : nullptr, fuse_mf ? s->g_item + D : nullptr, 2 * D};
+          fuse_mf ? s->x0 + uoff : nullptr, fuse_mf ? s->g_user + D : nullptr, fuse_mf ? s->x0 + ioff : nullptr, fuse_mf ? s->g_item + D : nullptr, 2 * D,
+          group_later ? &adv_later : nullptr};
       // keep_prefetch == 2: the next step's planes and the dense finalize ride in this launch's grid (no fork / join in the step)
       br::FinalArgs fin;
       bool fin_ok = false, fin_done = false;

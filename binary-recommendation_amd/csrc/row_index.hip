@@ -75,7 +75,10 @@ struct IdxJob {
   int n_chunks = 0;   // its chunk count then
 };
 
-struct IdxJobs { IdxJob j[2]; };
+// the id streams of a launch (blockIdx.y, or the sort workgroups' stream number): two of a step - or the two of every step of a
+// multi-step group, whose head builds all of them (streams 2 k and 2 k + 1: step k).  Passed by value: 16 jobs are 1.4 KB of the 4 KB
+constexpr int kIdxJobsMax = 2 * BR_GROUP_MAX;
+struct IdxJobs { IdxJob j[kIdxJobsMax]; };
 
 // chunk `chunk` of id stream `which` by the calling workgroup of kSortThreads threads
 template <typename IdT, int kChunk, int kSortThreads>
@@ -111,9 +114,10 @@ __global__ __launch_bounds__(kSortThreads) void chunk_sort_kernel(IdxJobs jobs, 
 // 16 pairs that flow around them.  As a launch of their own on a side stream the sorts needed a fork and a join in the step's
 // hipGraph (~10 us each on the main branch, ROCm 7.2) and stretched the lookup they ran beside; the chunk-rank launch follows on the
 // same stream.  LDS: the sort's image is reserved by every workgroup (two per CU = 32 waves: the lookup's full occupancy anyway).
+// n_streams: 2, or 2 S at the head of a group of S steps (all streams of n ids: the lookup workgroups serve the head's pairs only).
 template <typename IdT, int VEC, int R>
-__global__ __launch_bounds__(kThreadsL, 8) void lookup_sort_kernel(const LookupArgs a, IdxJobs jobs, int64_t n, int n_chunks) {
-  const int n_sort = 2 * n_chunks;
+__global__ __launch_bounds__(kThreadsL, 8) void lookup_sort_kernel(const LookupArgs a, IdxJobs jobs, int64_t n, int n_chunks, int n_streams) {
+  const int n_sort = n_streams * n_chunks;
   if ((int)blockIdx.x < n_sort) {
     chunk_sort_block<IdT, kChunkL, kThreadsL>(jobs, n, (int)blockIdx.x % n_chunks, (int)blockIdx.x / n_chunks);
     return;
@@ -162,11 +166,13 @@ __global__ __launch_bounds__(kThreadsL) void gather_sort_kernel(const GatherDefJ
 }
 
 // adv.st != NULL: the grid has one extra column of workgroups, whose y = 0 member advances the step state (nothing in this launch reads it;
-// the lookup in front computed its step as ss->step + 1, everything behind sees the advanced state) - one launch less per step
+// the lookup in front computed its step as ss->step + 1, everything behind sees the advanced state) - one launch less per step.
+// Head of a multi-step group (gridDim.y = all the group's streams): members 1 .. adv.n_more of that column clear the later steps' scratch
 template <typename IdT, int kChunk>
 __global__ __launch_bounds__(256) void chunk_rank_kernel(IdxJobs jobs, int64_t n, int n_chunks, const StepAdvance adv) {      // (n: the longer stream's keys)
   if (adv.st && blockIdx.x == gridDim.x - 1) {
     if (blockIdx.y == 0) step_state_advance_block(adv);
+    else if ((int)blockIdx.y <= adv.n_more) step_state_zero_more(adv, (int)blockIdx.y - 1);
     return;
   }
   const IdxJob& job = jobs.j[blockIdx.y];
@@ -418,29 +424,40 @@ bool br::lookup_with_index_supported(int dim, int64_t n, int64_t upper_a, int64_
          ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(stash_a) | reinterpret_cast<uintptr_t>(stash_b)) & (4 * wvec - 1)) == 0 &&
          n > kChunkSwitchN && rank_path_ok(n, upper_a) && rank_path_ok(n, upper_b);
 }
-int br::lookup_with_index(const LookupArgs& la, int dim, int id_type, const IndexPairArgs& ix, brStream stream, const StepAdvance* adv) {
+int br::lookup_index_chunks(int64_t n) { return (int)ceil_div(n, kChunkL); }
+int br::lookup_with_index(const LookupArgs& la, int dim, int id_type, const IndexPairArgs& ix, brStream stream, const StepAdvance* adv,
+                          const GroupIndexArgs* later) {
   const int64_t n = la.batch;
-  BR_CHECK_ARG(ix.sorted_ids_a && ix.sorted_ids_b && ix.sorted_pos_a && ix.sorted_pos_b && ix.ws_a && ix.ws_b, "lookup_with_index: null pointer");
+  const int n_later = later ? later->n : 0;
+  BR_CHECK_ARG(n_later >= 0 && n_later < BR_GROUP_MAX, "lookup_with_index: at most %d steps per group", (int)BR_GROUP_MAX);
   const int64_t need = brRowIndexWorkspaceBytes(n, id_type);
-  if (ix.ws_a_bytes < need || ix.ws_b_bytes < need) { set_error("lookup_with_index: workspace < required %lld", (long long)need); return BR_ERR_WORKSPACE; }
   IdxJobs jobs;
-  jobs.j[0] = make_job(la.users, ix.sorted_ids_a, ix.sorted_pos_a, ix.ws_a, n, la.user_rows);
-  jobs.j[1] = make_job(la.items, ix.sorted_ids_b, ix.sorted_pos_b, ix.ws_b, n, la.item_rows);
+  for (int k = 0; k <= n_later; ++k) {      // streams 2 k, 2 k + 1: step k of the group (0: this step)
+    const IndexPairArgs& x = k ? later->ix[k - 1] : ix;
+    const void* users = k ? later->users[k - 1] : la.users;
+    const void* items = k ? later->items[k - 1] : la.items;
+    BR_CHECK_ARG(x.sorted_ids_a && x.sorted_ids_b && x.sorted_pos_a && x.sorted_pos_b && x.ws_a && x.ws_b && (!k || (users && items)), "lookup_with_index: null pointer");
+    if (x.ws_a_bytes < need || x.ws_b_bytes < need) { set_error("lookup_with_index: workspace < required %lld", (long long)need); return BR_ERR_WORKSPACE; }
+    jobs.j[2 * k] = make_job(users, x.sorted_ids_a, x.sorted_pos_a, x.ws_a, n, la.user_rows);
+    jobs.j[2 * k + 1] = make_job(items, x.sorted_ids_b, x.sorted_pos_b, x.ws_b, n, la.item_rows);
+  }
+  const int n_streams = 2 * (n_later + 1);
+  const StepAdvance av = adv ? *adv : StepAdvance{};
+  BR_CHECK_ARG(av.n_more >= 0 && av.n_more <= n_later && (av.n_more == 0 || av.st), "lookup_with_index: scratch buffers of later steps without their streams");
   const int n_chunks = (int)ceil_div(n, kChunkL);
   hipStream_t s = (hipStream_t)stream;
   const int wvec = wave_pair_vec(dim);      // (lookup_with_index_supported: 2 or 4)
   const int ppw = wvec == 2 ? lookup_pairs_per_wave() : 1;
-  const unsigned grid = (unsigned)(2 * n_chunks + ceil_div(ceil_div(n, (int64_t)(ppw < 1 ? 1 : ppw)), (int64_t)(kThreadsL / 64)));
+  const unsigned grid = (unsigned)(n_streams * n_chunks + ceil_div(ceil_div(n, (int64_t)(ppw < 1 ? 1 : ppw)), (int64_t)(kThreadsL / 64)));
   BR_DISPATCH_ID(id_type, {
-    if (wvec == 2 && ppw == 0) lookup_sort_kernel<IdT, 2, 0><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else if (wvec == 2 && ppw == 2) lookup_sort_kernel<IdT, 2, 2><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else if (wvec == 2) lookup_sort_kernel<IdT, 2, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
-    else lookup_sort_kernel<IdT, 4, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks);
+    if (wvec == 2 && ppw == 0) lookup_sort_kernel<IdT, 2, 0><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks, n_streams);
+    else if (wvec == 2 && ppw == 2) lookup_sort_kernel<IdT, 2, 2><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks, n_streams);
+    else if (wvec == 2) lookup_sort_kernel<IdT, 2, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks, n_streams);
+    else lookup_sort_kernel<IdT, 4, 1><<<grid, kThreadsL, 0, s>>>(la, jobs, n, n_chunks, n_streams);
   });
   BR_CHECK_LAUNCH("lookup_with_index(lookup + sort)");
   probe_split(BR_TAG_EMBED_FWD, s);
-  const StepAdvance av = adv ? *adv : StepAdvance{};
-  const dim3 g2((unsigned)(ceil_div(n, 256) + (av.st ? 1 : 0)), 2);
+  const dim3 g2((unsigned)(ceil_div(n, 256) + (av.st ? 1 : 0)), (unsigned)n_streams);
   BR_DISPATCH_ID(id_type, (chunk_rank_kernel<IdT, kChunkL><<<g2, 256, 0, s>>>(jobs, n, n_chunks, av)));
   BR_CHECK_LAUNCH("lookup_with_index(rank)");
   return BR_OK;

@@ -15,6 +15,7 @@
 #include "adam_math.h"
 #include "finalize.h"
 #include "dense.h"
+#include "step_state.h"
 
 #include <algorithm>
 
@@ -122,8 +123,12 @@ struct SegJob {                // one table's gradient source for the partials
 struct SegJobs { SegJob j[2]; };
 
 template <typename IdT, int VEC>
-__global__ __launch_bounds__(256) void segment_partials_kernel(SegJobs jobs, int64_t n_launch, int dim, int chunks, int lpr_log2, int split) {
+__global__ __launch_bounds__(256) void segment_partials_kernel(SegJobs jobs, int64_t n_launch, int dim, int chunks, int lpr_log2, int split, const StepAdvance adv) {
   using V = typename VecT<VEC>::type;
+  if (adv.st && blockIdx.x == gridDim.x - 1) {      // (see segment_partials_wave_kernel)
+    if (blockIdx.y == 0) step_state_advance_block(adv);
+    return;
+  }
   const SegJob& jb = jobs.j[blockIdx.y];
   const int64_t n = jb.n ? jb.n : n_launch;
   const IdT* __restrict__ sid = (const IdT*)jb.sid;
@@ -153,8 +158,15 @@ __global__ __launch_bounds__(256) void segment_partials_kernel(SegJobs jobs, int
 // length is a ballot, and the rows are requested eight at a time by position (readlane) and added in position order - the order
 // seg_walk adds them in.  On a Zipf(1.05) batch ~70 % of the blocks continue a run: 40 us in the row-group form.
 template <typename IdT, int VEC>
-__global__ __launch_bounds__(256) void segment_partials_wave_kernel(SegJobs jobs, int64_t n_launch, int split) {
+__global__ __launch_bounds__(256) void segment_partials_wave_kernel(SegJobs jobs, int64_t n_launch, int split, const StepAdvance adv) {
   using V = typename VecT<VEC>::type;
+  // adv.st != NULL (a later step of a multi-step group, which has no chunk-rank launch): the grid has one extra column of workgroups,
+  // whose y = 0 member advances the step state.  Nothing in this launch reads the state; the step's lookup in front computed its step
+  // as ss->step + 1, the Adam-rows launch behind reads the advanced counter and alpha_t
+  if (adv.st && blockIdx.x == gridDim.x - 1) {
+    if (blockIdx.y == 0) step_state_advance_block(adv);
+    return;
+  }
   constexpr int dim = 64 * VEC;
   const SegJob& jb = jobs.j[blockIdx.y];
   const int64_t n = jb.n ? jb.n : n_launch;
@@ -611,20 +623,25 @@ using namespace br;
 extern "C" int64_t brSegmentScratchFloats(int64_t n, int dim) { return ceil_div(n > 0 ? n : 1, kSegBlock) * (int64_t)dim; }
 
 // partial rows of every kSegBlock-aligned block that continues a segment (see seg_acc); jobs share n / dim / split
-static int launch_partials(const SegJob* jobs, int n_jobs, int id_type, int64_t n, int dim, const RowGeom& g, int split, hipStream_t s) {
+// (adv: the step-state advance as one extra workgroup of the launch, which must then exist)
+static int launch_partials(const SegJob* jobs, int n_jobs, int id_type, int64_t n, int dim, const RowGeom& g, int split, hipStream_t s,
+                           const StepAdvance* adv = nullptr) {
   const int64_t blocks = ceil_div(n, kSegBlock) - 1;
+  BR_CHECK_ARG(!adv || blocks > 0, "segment partials: no launch to carry the step-state advance");
   if (blocks <= 0) return BR_OK;
+  const StepAdvance av = adv ? *adv : StepAdvance{};
+  const unsigned extra = av.st ? 1u : 0u;
   SegJobs J;
   for (int q = 0; q < 2; ++q) J.j[q] = jobs[q < n_jobs ? q : 0];
   const int wvec = wave_row_vec(dim);
   if (wave_rows_enabled() && wvec && g.vec >= wvec) {     // (g.vec: the widest vector the sources' strides honour)
-    const dim3 wgrid((unsigned)ceil_div(blocks, 4), (unsigned)n_jobs);
-    BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(wvec, (segment_partials_wave_kernel<IdT, VEC><<<wgrid, 256, 0, s>>>(J, n, split))));
+    const dim3 wgrid((unsigned)ceil_div(blocks, 4) + extra, (unsigned)n_jobs);
+    BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(wvec, (segment_partials_wave_kernel<IdT, VEC><<<wgrid, 256, 0, s>>>(J, n, split, av))));
     BR_CHECK_LAUNCH("segment partials (wave)");
     return BR_OK;
   }
-  const dim3 grid((unsigned)ceil_div(blocks, 256 >> g.lpr_log2), (unsigned)n_jobs);
-  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (segment_partials_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, n, dim, g.chunks, g.lpr_log2, split))));
+  const dim3 grid((unsigned)ceil_div(blocks, 256 >> g.lpr_log2) + extra, (unsigned)n_jobs);
+  BR_DISPATCH_ID(id_type, BR_DISPATCH_VEC(g.vec, (segment_partials_kernel<IdT, VEC><<<grid, 256, 0, s>>>(J, n, dim, g.chunks, g.lpr_log2, split, av))));
   BR_CHECK_LAUNCH("segment partials");
   return BR_OK;
 }
@@ -738,7 +755,7 @@ struct AdamRowsArgs {      // one table's host-side arguments
 
 static int adam_rows_launch(const AdamRowsArgs* a, int n_jobs, int dim, int id_type, int64_t n, int split, double alpha_t, double beta1,
                             double beta2, double eps, const StepStateDev* ss, brStream stream, const KeepArgs* keep = nullptr,
-                            const FinalArgs* fin = nullptr, bool* fin_done = nullptr) {
+                            const FinalArgs* fin = nullptr, bool* fin_done = nullptr, const StepAdvance* adv = nullptr) {
   if (fin_done) *fin_done = false;
   BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, "brAdamRowsSorted: bad id_type");
   if (n == 0) return BR_OK;
@@ -775,8 +792,9 @@ static int adam_rows_launch(const AdamRowsArgs* a, int n_jobs, int dim, int id_t
   const int wvec = wave_row_vec(dim);
   const bool wave_ok = wave_rows_enabled() && wvec && ldmin >= wvec && th_min >= wvec && all_stashed;
   BR_CHECK_ARG(!per_job_n || wave_ok, "brAdamRowsSorted: tables of different lengths in one launch need the one-wave-per-row shapes");
+  BR_CHECK_ARG(!adv || with_partials, "brAdamRowsSorted: the step-state advance rides in the segment-partials launch (seg_ws missing)");
   if (with_partials) {
-    const int rc = launch_partials(segs, n_jobs, id_type, n_max, dim, g, split, (hipStream_t)stream);
+    const int rc = launch_partials(segs, n_jobs, id_type, n_max, dim, g, split, (hipStream_t)stream, adv);
     if (rc != BR_OK) return rc;
     probe_split(BR_TAG_SEG_PARTIALS, (hipStream_t)stream);
   }
@@ -890,7 +908,7 @@ int br::adam_rows_pair_keep(const AdamPairCall& c, const KeepArgs* keep, brStrea
                              {c.table_b, c.m_b, c.v_b, c.rows_b, c.sorted_ids_b, c.sorted_pos_b, c.grads_b, c.ldg_b, c.grads_hi_b, c.ldg_hi_b, c.mark_b, c.last_b, c.seg_ws_b, c.hi_scale,
                               c.th_lo_b, c.th_hi_b, c.ld_th}};
   return adam_rows_launch(a, 2, c.dim, c.id_type, c.n, c.split, c.alpha_t, c.beta1, c.beta2, c.eps, c.last_a ? (const StepStateDev*)c.step_state : nullptr, stream, keep,
-                          fin, fin_done);
+                          fin, fin_done, c.adv);
 }
 
 extern "C" int brAdamFlush(float* table, float* m, float* v, int32_t* last, int64_t table_rows, int dim, const void* step_state,

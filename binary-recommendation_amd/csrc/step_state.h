@@ -1,5 +1,5 @@
-// The step-state advance as a workgroup: a launch of its own (step_state.hip) or an extra workgroup of the chunk-rank launch
-// (row_index.hip).
+// The step-state advance as a workgroup: a launch of its own (step_state.hip), an extra workgroup of the chunk-rank launch
+// (row_index.hip) or of the segment-partials launch (sparse_opt.hip: the later steps of a multi-step group have no rank launch).
 #pragma once
 #include "common.h"
 
@@ -23,6 +23,13 @@ __device__ __forceinline__ void step_state_advance_block(const StepAdvance& a) {
     st->alpha_hist[t & (BR_ALPHA_RING - 1)] = al;
     if ((t & (BR_ALPHA_RING - 1)) < (uint32_t)BR_RING_MIRROR) st->alpha_hist[BR_ALPHA_RING + (t & (BR_ALPHA_RING - 1))] = al;   // the mirror behind the ring's end
   }
+}
+
+// the double scratch of later step `which` of a multi-step group, zeroed by one workgroup (its last reader - the previous group's
+// finalize of that step - is behind the launch on the stream, its next writer - this group's fwd L1 of that step - in front)
+__device__ __forceinline__ void step_state_zero_more(const StepAdvance& a, int which) {
+  double* __restrict__ z = a.zero_more[which];
+  for (int64_t i = threadIdx.x; i < a.n_zero; i += blockDim.x) z[i] = 0.0;
 }
 
 }  // namespace br

@@ -301,11 +301,13 @@ class NeuMFEngine(RowAdam):
         self._graph = None
         self._graph_multi = None
 
-    def _bind_indexes(self, st):
-        ui, ii = self.user_index, self.item_index
+    def _bind_indexes(self, st, ui=None, ii=None):
+        """the step's index buffers: the engine's own, or (ui, ii) - a later step of a multi-step group (the segment scratch, written and
+        read inside one step, stays the engine's)"""
+        ui, ii = ui or self.user_index, ii or self.item_index
         st.u_sorted_ids, st.u_sorted_pos, st.u_ws, st.u_ws_bytes = ui.sorted_ids.data_ptr(), ui.sorted_pos.data_ptr(), ui.ws.data_ptr(), ui.ws_bytes
         st.i_sorted_ids, st.i_sorted_pos, st.i_ws, st.i_ws_bytes = ii.sorted_ids.data_ptr(), ii.sorted_pos.data_ptr(), ii.ws.data_ptr(), ii.ws_bytes
-        st.u_seg_ws, st.i_seg_ws = ui.seg_ws(2 * self.cfg.dim).data_ptr(), ii.seg_ws(2 * self.cfg.dim).data_ptr()
+        st.u_seg_ws, st.i_seg_ws = self.user_index.seg_ws(2 * self.cfg.dim).data_ptr(), self.item_index.seg_ws(2 * self.cfg.dim).data_ptr()
 
     def _run(self, phases: int):
         _lib.check(_lib.load().brNeumfStepRun(ctypes.byref(self.step_struct), phases, ops._stream()), "brNeumfStepRun")
@@ -492,7 +494,12 @@ class NeuMFEngine(RowAdam):
         the steps of a group lives on the device (step counter, alpha_t, the alpha ring, the dropout planes the previous step's
         Adam-rows launch prefetched); the group's ids / labels are staged by one brStageBatch launch into static buffers of `steps`
         batches.  Needs the single-step graph (captured here if absent: it runs the dry step that loads every code object).
-        probe_tag: bench.py's measurement - only the LAST step of the group carries the event-record nodes around that kernel."""
+        Where the step takes the fused lookup + index path (brNeumfGroupIndexPlan: batch > 16 384, deferred tables, embed_dim 64 / 128,
+        planes prefetched or no dropout, steps <= 8) the group's first step builds the row index of every step and the later steps
+        launch neither sorts nor a rank; the returned dict's "sets" then holds each step's (user index, item index, double scratch),
+        else None.  BR_GROUP_INDEX=0 at capture: every step builds its own index, as in the single-step graph.
+        probe_tag: bench.py's measurement - only the LAST step of the group carries the event-record nodes around that kernel (a tag
+        that step does not launch - the fused lookup + index call, once the head has built the index - places none)."""
         S = int(steps)
         if S < 2:
             raise ValueError("enable_graph_multi: steps >= 2 (enable_graph is the single-step form)")
@@ -505,25 +512,61 @@ class NeuMFEngine(RowAdam):
             self.in_users_m = torch.zeros(S * B, dtype=self.id_dtype, device=dev)
             self.in_items_m = torch.zeros(S * B, dtype=self.id_dtype, device=dev)
             self.in_labels_m = torch.zeros(S * B, dtype=torch.float32, device=dev)
+            gm = None
         lib = _lib.load()
+        batch_of = lambda k: (self.in_users_m[k * B:(k + 1) * B], self.in_items_m[k * B:(k + 1) * B], self.in_labels_m[k * B:(k + 1) * B])
+        # The group's index built once, at its head (include/binrec.h brNeumfStep.group_size; BR_GROUP_INDEX=0: every step its own, as
+        # the single-step graph has it): the ids of all S steps are in the static buffers before the group's first kernel runs, so the
+        # head's lookup launch carries the chunk sorts of all 2 S id streams and ONE chunk-rank launch ranks them; steps 2..S are the
+        # plain lookup and no rank.  Every step then has index buffers and BatchNorm double scratch of its own (step 0: the engine's),
+        # kept with the capture - an earlier capture of the same S and batch that is still replayed shares them.
+        self._set_batch(*batch_of(0), B, True, 0, B)
+        st.keep_ready = 1 if st.keep_prefetch else 0
+        sets = None
+        if lib.brNeumfGroupIndexPlan(ctypes.byref(st), S) > 0:
+            sets = gm.get("sets") if gm is not None else None
+            if sets is None:
+                sets = [(self.user_index, self.item_index, self.dstat)]
+                sets += [(ops.RowIndex(self.max_batch, self.id_dtype, dev), ops.RowIndex(self.max_batch, self.id_dtype, dev), torch.zeros_like(self.dstat))
+                         for _ in range(S - 1)]
+
+            class GroupSet(ctypes.Structure):
+                _fields_ = _lib.parse_struct("brNeumfGroupSet")
+            if ctypes.sizeof(GroupSet) != lib.brNeumfGroupSetSizeof():
+                raise _lib.BinrecError("brNeumfGroupSet layout mismatch between include/binrec.h and libbinrec_hip.so")
+            arr = (GroupSet * S)()
+            for k, (ui, ii, ds) in enumerate(sets):
+                uk, ik, _ = batch_of(k)
+                arr[k].users, arr[k].items, arr[k].dstat = uk.data_ptr(), ik.data_ptr(), ds.data_ptr()
+                arr[k].u_sorted_ids, arr[k].u_sorted_pos, arr[k].u_ws = ui.sorted_ids.data_ptr(), ui.sorted_pos.data_ptr(), ui.ws.data_ptr()
+                arr[k].i_sorted_ids, arr[k].i_sorted_pos, arr[k].i_ws = ii.sorted_ids.data_ptr(), ii.sorted_pos.data_ptr(), ii.ws.data_ptr()
         g = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
         try:
+            if sets is not None:
+                st.group_size, st.group_sets = S, ctypes.addressof(arr)      # (a host array: read while the calls below are captured)
             with torch.cuda.graph(g):
                 for k in range(S):
-                    sl = slice(k * B, (k + 1) * B)
-                    self._set_batch(self.in_users_m[sl], self.in_items_m[sl], self.in_labels_m[sl], B, True, 0, B)
+                    self._set_batch(*batch_of(k), B, True, 0, B)
                     st.keep_ready = 1 if st.keep_prefetch else 0
+                    if sets is not None:
+                        st.group_pos = k
+                        self._bind_indexes(st, sets[k][0], sets[k][1])
+                        st.dstat = sets[k][2].data_ptr()
                     if probe_tag is not None and k == S - 1:
                         lib.brProbeGraphSelect(int(probe_tag))
                     self._run(PH["ALL"])
         finally:
             if probe_tag is not None:
                 lib.brProbeGraphSelect(-1)
+            # the step struct as the single-step graph and the eager step know it
+            st.group_size, st.group_pos, st.group_sets = 0, 0, None
+            self._bind_indexes(st)
+            st.dstat = self.dstat.data_ptr()
         if keep_graph:
             g.instantiate()
         self._set_batch(self.in_users, self.in_items, self.in_labels, B, True, 0, B)     # the single-step graph's view of the step struct
         st.keep_ready = 1 if st.keep_prefetch else 0
-        self._graph_multi = {"S": S, "batch": B, "graph": g}
+        self._graph_multi = {"S": S, "batch": B, "graph": g, "sets": sets}
         return self._graph_multi
 
     def train_steps(self, users, items, labels):

@@ -843,6 +843,16 @@ enum {
                                  call also holds FWD1 (joined before ROWS_* or at the end of the call), else inline */
   BR_PH_ALL = 16383
 };
+/* One step of a multi-step group (brNeumfStep.group_sets): what that step's own brNeumfStepRun call carries in `users`, `items`,
+ * the u_ / i_ index fields (workspaces of u_ws_bytes / i_ws_bytes, as the call's own) and `dstat`.  The head call of the group
+ * builds the index of every step from these; the later calls only read theirs. */
+enum { BR_GROUP_MAX = 8 };
+typedef struct brNeumfGroupSet {
+  const void* users; const void* items;
+  void* u_sorted_ids; int32_t* u_sorted_pos; void* u_ws;
+  void* i_sorted_ids; int32_t* i_sorted_pos; void* i_ws;
+  double* dstat;
+} brNeumfGroupSet;
 typedef struct brNeumfStep {
   int64_t batch, batch_total, row0, user_rows, item_rows;
   int32_t dim, n1, n2, n3, act, loss, item_first, mf_first, id_type, adam_dense, training, step;
@@ -897,6 +907,17 @@ typedef struct brNeumfStep {
                          workgroups of the paired Adam-rows launch when the call holds BR_PH_ROWS_ITEM too (no fork / join - 4 us less
                          per step inside a hipGraph - but that launch then takes 101 instead of 94 us).  The host sets keep_ready on
                          the next call if that call's step / row0 are the ones prefetched */
+  int32_t group_size; /* 0: a step on its own.  2 .. BR_GROUP_MAX: this call is step group_pos of a group of group_size consecutive
+                         training steps issued back to back on one stream (NeuMFEngine.enable_graph_multi), all of whose ids are on the
+                         device before the first call: the row index of EVERY step is built by the head call (group_pos == 0: the chunk
+                         sorts of all 2 * group_size id streams ride in its lookup launch, one chunk-rank launch ranks them, advances
+                         the step state for the head and clears the `dstat` of every step).  A later call (group_pos >= 1) launches
+                         the plain one-wave-per-pair lookup, no sort and no rank, and advances the step state by one extra workgroup
+                         of its segment-partials launch - behind its lookup, in front of its Adam-rows launch.  Only where
+                         brNeumfGroupIndexPlan() > 0 for the struct, with phases == BR_PH_ALL; anything else is BR_ERR_ARG */
+  int32_t group_pos;
+  const brNeumfGroupSet* group_sets;   /* HOST array of group_size entries, read during the call (entry k: step k; the head's own
+                                          entry 0 is not read, its fields above count); every step its own index buffers and dstat */
 } brNeumfStep;
 /* step_state: device {uint32 step; float alpha_t; double b1^step, b2^step; float alpha_hist[BR_ALPHA_RING + BR_RING_MIRROR]; replay form},
  * brStepStateBytes() bytes, zero-initialised (or step / alpha_t set by the host after a reload).
@@ -1005,6 +1026,13 @@ int64_t brNeumfStepSizeof(void);
 /* floats of brNeumfStep.slabs for batches up to `batch`: the three slab regions [tail | layer 2 | layer 1] back to back */
 int64_t brNeumfStepSlabFloats(int64_t batch, int dim, int n1, int n2, int n3);
 int brNeumfStepRun(const brNeumfStep* s, uint32_t phases, brStream stream);
+int64_t brNeumfGroupSetSizeof(void);
+/* Host only: may `s` (filled as for a training call of the group; group_size / group_pos / group_sets are not read) run as a step of a
+ * group of `steps` steps whose index is built at the head (brNeumfStep.group_size)?  -> the sort workgroups of the head's lookup
+ * launch, 2 * chunks * steps, or 0: the step's own fused lookup + index path would not be taken (single GPU, deferred tables,
+ * batch > 16 384, embed_dim 64 / 128, BR_FUSED_SORT != 0), the dropout planes are not prefetched (dropout > 0 without keep_ready),
+ * steps is outside 2 .. BR_GROUP_MAX, the segment scratch is missing, or BR_GROUP_INDEX=0 (read on every call: A/B runs). */
+int brNeumfGroupIndexPlan(const brNeumfStep* s, int steps);
 
 /* Optional launch probe for measurement (bench.py roofline leg): HIP events on the launch stream
  * around every inner launch of brNeumfStepRun, tagged BR_TAG_*.  brProbeEnable(capacity) creates
