@@ -11,6 +11,8 @@
 //     MODE_LSE_GRAD_R = MODE_LSE and MODE_GRAD_R in ONE sweep (the training step needs both): the accumulator of dQ is kept relative
 //                 to the running row maximum and rescaled when it grows (online softmax); dQ_i = acc_i / l_i - C_diag(i) at the end.
 //                 The score tiles are formed twice per step instead of three times (4 GEMMs instead of 5 for lse + dQ + dC)
+//     MODE_THR    owned = queries     streamed = candidates   hard negatives: the key (score, column) of each query's M-th best negative;
+//                 the HARD forms of the four softmax modes then run over the partner and those M columns only (InbatchHardArgs below)
 //   MFMA: v_mfma_f32_32x32x2_f32.  The score tile is formed TRANSPOSED, D[m = streamed entity][n = owned row]: in the result
 //   layout a lane then holds ONE owned row (n = lane % 32) and its 16 registers hold 16 streamed entities
 //   (m = 8 (r / 4) + 4 (lane / 32) + r % 4), so
@@ -38,6 +40,7 @@
 //   (consecutive registers = consecutive k slots).  BR_MLP_MATH=f32 keeps the fp32 MFMAs.
 #include "common.h"
 #include "dense.h"
+#include <type_traits>
 
 namespace br {
 
@@ -56,10 +59,17 @@ __device__ __forceinline__ f32x16 mfma32x6(bf16x8 xh, bf16x8 xm, bf16x8 xl, bf16
   c = mfma32b(xm, wh, c); c = mfma32b(xh, wm, c); c = mfma32b(xh, wh, c);
   return c;
 }
+// the same six products with the operand roles swapped (the candidate-owned hard sweep: x = query, w = candidate): issued so that the
+// piece pairs meet the accumulator in the order of mfma32x6 with x = candidate, w = query - the score bits of the query-owned sweeps
+__device__ __forceinline__ f32x16 mfma32x6m(bf16x8 xh, bf16x8 xm, bf16x8 xl, bf16x8 wh, bf16x8 wm, bf16x8 wl, f32x16 c) {
+  c = mfma32b(xh, wl, c); c = mfma32b(xl, wh, c); c = mfma32b(xm, wm, c);
+  c = mfma32b(xh, wm, c); c = mfma32b(xm, wh, c); c = mfma32b(xh, wh, c);
+  return c;
+}
 constexpr int kGs = 33;                      // 16-B slots per (..., lane half) group of the piece images: 32 + 1 (the staging's half-word stores of
                                              // the 8 groups a wave touches would otherwise hit the same banks)
 
-enum { MODE_SCORES = 0, MODE_LSE = 1, MODE_GRAD_R = 2, MODE_GRAD_C = 3, MODE_LSE_GRAD_R = 4 };
+enum { MODE_SCORES = 0, MODE_LSE = 1, MODE_GRAD_R = 2, MODE_GRAD_C = 3, MODE_LSE_GRAD_R = 4, MODE_THR = 5 };
 
 // exp of a non-positive argument (score - running max, score - lse) on the hardware exp2: one evaluation per score made
 // these kernels VALU-bound with the accurate expf (~30 instructions each).  |x| <= ~88; the relative
@@ -82,9 +92,32 @@ struct InbatchArgs {
   int64_t t_per_split;                       // streamed rows per blockIdx.y (multiple of kTs)
 };
 
+// Hard negatives (tfrs HardNegativeMining): per query the softmax runs over its partner column and its M best other
+// columns by (masked score descending, column ascending).  MODE_THR finds the key (score, column) of the M-th of them in a sweep of
+// its own, in the tile layout and arithmetic of the sweeps that use it; the HARD forms of the four sweeps keep a column iff it is
+// the partner, or x > thr_s, or x == thr_s and column <= thr_p, and give every other column x = -inf.
+struct InbatchHardArgs : InbatchArgs {
+  const float* thr_s; const int32_t* thr_p;  // HARD: key of the last kept negative per query (owned rows; GRAD_C: streamed rows)
+  float* thr_s_out; int32_t* thr_p_out;      // THR without splits
+  uint2* lists; int M;                       // THR with splits: [n_r][n_split][M] keys (score bits, column), unordered
+  int64_t col0;                              // HARD GRAD_C: the owned candidates are columns [col0, col0 + n_r) of those thr_p counts over
+};
+constexpr int kThrNone = 0x7FFFFFFF;         // column of the key (-inf, kThrNone): nothing is cut
+// what a HARD instantiation keeps per lane; the plain instantiations get the empty forms, so nothing of it exists in their code
+template <bool ON> struct HardKey {};
+template <> struct HardKey<true> { float ts = -INFINITY; int tp = kThrNone; int tl = 0; };      // a key, and tp as a tile-local column (minus jb)
+template <bool ON> struct HardKeys4 {};
+template <> struct HardKeys4<true> { float ts[4]; int tp[4]; };
+// key a is ranked after key b: lower score, or the same score at a higher column
+__device__ __forceinline__ bool key_worse(float xa, int ja, float xb, int jb) { return xa < xb || (xa == xb && ja > jb); }
+
 // KQ = 16-byte vectors per lane half of the feature axis: features are padded to Kp = 8 KQ
-template <int MODE, int KQ, typename IdT, bool EMU>
-__global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
+// ArgsT: InbatchHardArgs for MODE_THR and the HARD forms, else InbatchArgs - the plain instantiations take no new argument.  (A parameter
+// of its own, not a type computed from MODE in the signature: the unnamed enum would enter the mangled name, differently on host and device.)
+template <int MODE, int KQ, typename IdT, bool EMU, bool HARD = false, typename ArgsT = InbatchArgs>
+__global__ __launch_bounds__(256, 2) void inbatch_kernel(const ArgsT a) {
+  static_assert(std::is_same<ArgsT, InbatchHardArgs>::value == (HARD || MODE == MODE_THR), "the hard arguments go with MODE_THR and the HARD forms");
+  static_assert(!HARD || MODE == MODE_LSE || MODE == MODE_GRAD_R || MODE == MODE_GRAD_C || MODE == MODE_LSE_GRAD_R, "hard forms of the four softmax sweeps");
   constexpr int KH = 4 * KQ, Kp = 8 * KQ, ldt = Kp + 4;
   constexpr int FT = (Kp + 31) / 32;                     // 32-feature tiles of the second GEMM
   constexpr int KB = (Kp + 15) / 16;                     // EMU: 16-deep k-blocks of the score product
@@ -97,6 +130,9 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
   float* TsT = Ts + (EMU ? kTpFloats : kTs * ldt);       // [FT*32][68]   transposed (A operand of the second GEMM), GRAD only.  EMU: TT
   float* tlse = TsT + (EMU ? kTtFloats : (GRAD ? FT * 32 * kLdT : 0));       // [64]          GRAD_C: lse of the streamed queries
   IdT* tid = reinterpret_cast<IdT*>(tlse + kTs);         // [64]          ids of the streamed entities
+  float* tths = reinterpret_cast<float*>(tid + kTs);     // [64]          HARD GRAD_C: threshold score of the streamed queries
+  int32_t* tthp = reinterpret_cast<int32_t*>(tths + kTs);   // [64]                      ... and column
+  uint2* heap = reinterpret_cast<uint2*>(tid + kTs);     // [M][128]      THR: per owned row a min-heap of its M best keys, the worst at slot 0
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l32 = lane & 31, hb = lane >> 5;
@@ -143,6 +179,13 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
     if (has_ids) own_id = reinterpret_cast<const IdT*>(a.own_ids)[own];
     if (MODE == MODE_GRAD_R) own_lse = a.lse_in[own];
   }
+  HardKey<HARD && MODE != MODE_GRAD_C> ok;               // HARD, queries own: the key of this row's last kept negative
+  if constexpr (HARD && MODE != MODE_GRAD_C) {
+    if (own_ok) { ok.ts = a.thr_s[own]; ok.tp = a.thr_p[own]; }
+  }
+  if constexpr (MODE == MODE_THR) {
+    for (int idx = threadIdx.x; idx < a.M * kOwn; idx += 256) heap[idx] = make_uint2(__float_as_uint(-INFINITY), (uint32_t)kThrNone);
+  }
   float run_m = -INFINITY, run_l = 0.f, diag_s = 0.f;    // LSE
   f32x16 gacc[GRAD ? FT : 1];
 #pragma unroll
@@ -162,6 +205,7 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
   float4 pre[NPRE];
   IdT pre_id = (IdT)-2;
   float pre_lse = 0.f;
+  HardKey<HARD && MODE == MODE_GRAD_C> pk;               // HARD, candidates own: the key of the streamed query this thread stages
   auto fetch = [&](int64_t c0) {
     const int64_t gr = c0 + sr;
     const bool rin = gr < t_end;
@@ -181,6 +225,7 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
     if (cg == 0) {
       pre_id = (rin && has_ids) ? reinterpret_cast<const IdT*>(a.str_ids)[gr] : (IdT)-2;
       if (MODE == MODE_GRAD_C) pre_lse = rin ? a.lse_in[gr] : 0.f;
+      if constexpr (HARD && MODE == MODE_GRAD_C) { pk.ts = rin ? a.thr_s[gr] : -INFINITY; pk.tp = rin ? a.thr_p[gr] : kThrNone; }
     }
   };
   if (t_begin < t_end) fetch(t_begin);
@@ -252,6 +297,7 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
     if (cg == 0) {
       tid[sr] = pre_id;
       if (MODE == MODE_GRAD_C) tlse[sr] = pre_lse;
+      if constexpr (HARD && MODE == MODE_GRAD_C) { tths[sr] = pk.ts; tthp[sr] = pk.tp; }
     }
     __syncthreads();
     if (c0 + kTs < t_end) fetch(c0 + kTs);                // in flight during this step's MFMA work
@@ -270,8 +316,13 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
           x0[p3] = frag8(*reinterpret_cast<const float4*>(tp + ((((0 * KB + kb) * 3 + p3) * 2 * kGs) << 2)));
           x1[p3] = frag8(*reinterpret_cast<const float4*>(tp + ((((1 * KB + kb) * 3 + p3) * 2 * kGs) << 2)));
         }
-        s0 = mfma32x6(x0[0], x0[1], x0[2], rh[kb], rm[kb], rl[kb], s0);
-        s1 = mfma32x6(x1[0], x1[1], x1[2], rh[kb], rm[kb], rl[kb], s1);
+        if constexpr (HARD && MODE == MODE_GRAD_C) {       // the streamed operand is the query here: the piece order of the query-owned sweeps
+          s0 = mfma32x6m(x0[0], x0[1], x0[2], rh[kb], rm[kb], rl[kb], s0);
+          s1 = mfma32x6m(x1[0], x1[1], x1[2], rh[kb], rm[kb], rl[kb], s1);
+        } else {
+          s0 = mfma32x6(x0[0], x0[1], x0[2], rh[kb], rm[kb], rl[kb], s0);
+          s1 = mfma32x6(x1[0], x1[1], x1[2], rh[kb], rm[kb], rl[kb], s1);
+        }
       }
     } else {
     const float* ap = Ts + l32 * ldt + KH * hb;
@@ -296,6 +347,85 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
       continue;
     }
     const int dd = (int)((partner - c0 < -1) ? -1 : (partner - c0 > 4096 ? 4096 : partner - c0)) - jb;   // tile-local diag index minus jb
+    // HARD, queries own: tile-local column of the threshold key minus jb (a column at the threshold score is kept up to it)
+    if constexpr (HARD && MODE != MODE_GRAD_C) {
+      const int64_t t = (int64_t)ok.tp - c0;
+      ok.tl = (int)(t < -1 ? -1 : (t > 4096 ? 4096 : t)) - jb;
+    }
+    if constexpr (MODE == MODE_THR) {
+      const int lim = (int)(t_end - c0) - jb;
+      float v[32];                                        // the masked scores of this lane's 32 columns; NaN = not a negative (partner, past the end)
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          IdT ids4[4];
+          if (has_ids) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ids4[e] = tid[32 * sub + 8 * rq + jb + e];
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int cj = 32 * sub + 8 * rq + e;
+            float x = sub ? s1[4 * rq + e] : s0[4 * rq + e];
+            const bool dg = cj == dd;
+            if (has_ids) x += (!dg && ids4[e] == own_id) ? kMinFloat : 0.f;
+            v[16 * sub + 4 * rq + e] = (cj < lim && !dg) ? x : __builtin_nanf("");
+          }
+        }
+      // the two lane halves of a row share its heap: one half at a time (a wave runs in lockstep, so the halves' updates are
+      // ordered); each half starts from the heap's current worst key and keeps it in registers, so a score that does not
+      // beat it costs the compares alone
+      const int hrow = wave * 32 + l32;
+      const int cb = (int)c0 + jb;
+#pragma unroll 1
+      for (int ph = 0; ph < 2; ++ph) {
+        if (hb == ph && own_ok) {
+          uint2 root = heap[hrow];
+          float ts = __uint_as_float(root.x);
+          int tj = (int)root.y;
+          // the scores that beat the key as it stands (a superset of those that will: it only rises), one bit each; then every lane
+          // inserts ITS candidates in a loop of its own, so a tile costs the wave max-over-lanes sifts, not one per score slot
+          // in which any lane inserts.  (The kept set does not depend on the order of insertion.)
+          uint32_t todo = 0;
+#pragma unroll
+          for (int i = 0; i < 32; ++i) {
+            const int col = cb + 32 * (i >> 4) + 8 * ((i & 15) >> 2) + (i & 3);
+            todo |= (v[i] > ts || (v[i] == ts && col < tj)) ? (1u << i) : 0u;
+          }
+          while (todo) {
+            const int i = __ffs(todo) - 1;
+            todo &= todo - 1;
+            float x = v[0];
+#pragma unroll
+            for (int k = 1; k < 32; ++k) x = (k == i) ? v[k] : x;
+            const int col = cb + 32 * (i >> 4) + 8 * ((i & 15) >> 2) + (i & 3);
+            if (x > ts || (x == ts && col < tj)) {        // beats the worst kept key: it leaves, the new key sifts down from the root
+              int k = 0;
+              for (;;) {
+                int ch = 2 * k + 1;
+                if (ch >= a.M) break;
+                uint2 kc = heap[ch * kOwn + hrow];
+                if (ch + 1 < a.M) {
+                  const uint2 k2 = heap[(ch + 1) * kOwn + hrow];
+                  if (key_worse(__uint_as_float(k2.x), (int)k2.y, __uint_as_float(kc.x), (int)kc.y)) { kc = k2; ch = ch + 1; }
+                }
+                if (!key_worse(__uint_as_float(kc.x), (int)kc.y, x, col)) break;
+                heap[k * kOwn + hrow] = kc;
+                k = ch;
+              }
+              heap[k * kOwn + hrow] = make_uint2(__float_as_uint(x), (uint32_t)col);
+              root = heap[hrow];
+              ts = __uint_as_float(root.x);
+              tj = (int)root.y;
+            }
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+      continue;
+    }
     if (MODE == MODE_LSE) {
       const int lim = (int)(t_end - c0) - jb;             // tile-local validity bound (only the last tile is partial)
       float v[32];
@@ -315,6 +445,7 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
             const bool dg = cj == dd;
             if (has_ids) x += (!dg && ids4[e] == own_id) ? kMinFloat : 0.f;
             diag_s = dg ? x : diag_s;
+            if constexpr (HARD && MODE != MODE_GRAD_C) x = (dg || x > ok.ts || (x == ok.ts && cj <= ok.tl)) ? x : -INFINITY;
             v[16 * sub + 4 * rq + e] = cj < lim ? x : -INFINITY;
           }
         }
@@ -322,6 +453,15 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
 #pragma unroll
       for (int i = 1; i < 32; ++i) m = fmaxf(m, v[i]);
       const float nm = fmaxf(run_m, m);                   // > -inf: every tile has at least one valid entity
+      if constexpr (HARD) {                               // ... but not necessarily a kept one: nothing kept so far leaves (-inf, 0)
+        const float ne = nm > -INFINITY ? nm : 0.f;
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) sum += exp_hw(v[i] - ne);
+        run_l = run_l * exp_hw(run_m - ne) + sum;
+        run_m = nm;
+        continue;
+      }
       float sum = 0.f;
 #pragma unroll
       for (int i = 0; i < 32; ++i) sum += exp_hw(v[i] - nm);
@@ -348,6 +488,7 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
             const bool dg = cj == dd;
             if (has_ids) x += (!dg && ids4[e] == own_id) ? kMinFloat : 0.f;
             diag_s = dg ? x : diag_s;
+            if constexpr (HARD && MODE != MODE_GRAD_C) x = (dg || x > ok.ts || (x == ok.ts && cj <= ok.tl)) ? x : -INFINITY;
             v[16 * sub + 4 * rq + e] = cj < (int)(t_end - c0) - jb ? x : -INFINITY;
           }
         }
@@ -356,11 +497,12 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
       for (int i = 1; i < 32; ++i) m = fmaxf(m, v[i]);
       m = fmaxf(m, __shfl_xor(m, 32, 64));               // both lane halves of an owned row feed the same accumulator: one maximum
       const float nm = fmaxf(run_m, m);                   // > -inf: every tile has at least one valid entity
-      const float sc = exp_hw(run_m - nm);                // 0 on the first step (run_m = -inf)
+      const float ne = (HARD && !(nm > -INFINITY)) ? 0.f : nm;   // HARD: ... but not necessarily a kept one (then every term below is 0)
+      const float sc = exp_hw(run_m - ne);                // 0 on the first step (run_m = -inf)
       run_m = nm;
       float sum = 0.f;
 #pragma unroll
-      for (int i = 0; i < 32; ++i) { v[i] = exp_hw(v[i] - nm); sum += v[i]; }
+      for (int i = 0; i < 32; ++i) { v[i] = exp_hw(v[i] - ne); sum += v[i]; }
       run_l = run_l * sc + sum;
 #pragma unroll
       for (int t = 0; t < FT; ++t)
@@ -410,6 +552,13 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
           const float4 t = *reinterpret_cast<const float4*>(tlse + j0);
           l4[0] = t.x; l4[1] = t.y; l4[2] = t.z; l4[3] = t.w;
         }
+        HardKeys4<HARD && MODE == MODE_GRAD_C> k4;
+        if constexpr (HARD && MODE == MODE_GRAD_C) {
+          const float4 t = *reinterpret_cast<const float4*>(tths + j0);
+          const int4 u = *reinterpret_cast<const int4*>(tthp + j0);
+          k4.ts[0] = t.x; k4.ts[1] = t.y; k4.ts[2] = t.z; k4.ts[3] = t.w;
+          k4.tp[0] = u.x; k4.tp[1] = u.y; k4.tp[2] = u.z; k4.tp[3] = u.w;
+        }
         float p[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -417,6 +566,8 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
           float x = sub ? s1[4 * rq + e] : s0[4 * rq + e];
           const bool dg = cj == dd;
           if (has_ids) x += (!dg && ids4[e] == own_id) ? kMinFloat : 0.f;
+          if constexpr (HARD && MODE == MODE_GRAD_C) x = (dg || x > k4.ts[e] || (x == k4.ts[e] && own + a.col0 <= (int64_t)k4.tp[e])) ? x : -INFINITY;   // this lane's candidate in the streamed query's kept set
+          else if constexpr (HARD) x = (dg || x > ok.ts || (x == ok.ts && cj <= ok.tl)) ? x : -INFINITY;
           p[e] = exp_hw(x - (MODE == MODE_GRAD_R ? own_lse : l4[e])) - (dg ? 1.f : 0.f);
           pv[4 * rq + e] = p[e];
         }
@@ -435,6 +586,25 @@ __global__ __launch_bounds__(256, 2) void inbatch_kernel(const InbatchArgs a) {
     }
   }
 
+  if constexpr (MODE == MODE_THR) {
+    // a row with at most M negatives cuts nothing; otherwise slot 0 of its heap is the M-th best key of this split's columns
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (a.lists) {
+      const int64_t ns = gridDim.y;
+      for (int r = 0; r < 32; ++r) {
+        const int64_t row = (int64_t)blockIdx.x * kOwn + wave * 32 + r;
+        if (row >= a.n_r) break;
+        for (int k = lane; k < a.M; k += 64) a.lists[(row * ns + blockIdx.y) * a.M + k] = heap[k * kOwn + wave * 32 + r];
+      }
+    } else if (hb == 0 && own_ok) {
+      const int64_t n_neg = a.n_t - ((partner >= 0 && partner < a.n_t) ? 1 : 0);
+      const uint2 root = heap[wave * 32 + l32];
+      a.thr_s_out[own] = n_neg > a.M ? __uint_as_float(root.x) : -INFINITY;
+      a.thr_p_out[own] = n_neg > a.M ? (int32_t)root.y : kThrNone;
+    }
+    return;
+  }
   if (FUSED) {
     // run_m is already common to the two lane halves of a row; l and the diagonal score are per half
     const float l = run_l + __shfl_xor(run_l, 32, 64);
@@ -611,6 +781,43 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
   }
 }
 
+// threshold sweep with splits: the M-th best key of the union of a query's per-split lists, one wave per query.  The keys are held in
+// LDS and the M best are taken one after the other, each the best key ranked strictly after the one before (the order is total:
+// real keys have distinct columns, and the fillers (-inf, kThrNone) of a short list are never ranked after themselves) -
+// no atomics, the same result whatever the split count.
+__global__ __launch_bounds__(64) void thr_combine_kernel(const uint2* __restrict__ lists, int n_keys, int M, int64_t n_t, int64_t diag,
+                                                          float* __restrict__ thr_s, int32_t* __restrict__ thr_p) {
+  extern __shared__ __attribute__((aligned(16))) uint2 keys[];
+  const int64_t i = blockIdx.x;
+  const int lane = threadIdx.x;
+  for (int k = lane; k < n_keys; k += 64) keys[k] = lists[i * n_keys + k];
+  __syncthreads();
+  float prev_s = INFINITY;
+  int prev_j = -1;
+  for (int t = 0; t < M; ++t) {
+    float best = -INFINITY;
+    int bestj = kThrNone;
+    for (int k = lane; k < n_keys; k += 64) {
+      const float s = __uint_as_float(keys[k].x);
+      const int j = (int)keys[k].y;
+      if (key_worse(s, j, prev_s, prev_j) && key_worse(best, bestj, s, j)) { best = s; bestj = j; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float os = __shfl_xor(best, off, 64);
+      const int oj = __shfl_xor(bestj, off, 64);
+      if (key_worse(best, bestj, os, oj)) { best = os; bestj = oj; }
+    }
+    prev_s = best; prev_j = bestj;
+  }
+  if (lane == 0) {
+    const int64_t partner = i + diag;
+    const int64_t n_neg = n_t - ((partner >= 0 && partner < n_t) ? 1 : 0);
+    thr_s[i] = n_neg > M ? prev_s : -INFINITY;
+    thr_p[i] = n_neg > M ? prev_j : kThrNone;
+  }
+}
+
 // E1: stable top-k of one score row per workgroup (ties keep the lower item position).
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ scores, int64_t n_items, int k,
                                                          float* __restrict__ out_s, int32_t* __restrict__ out_i) {
@@ -711,6 +918,59 @@ void launch_inbatch(InbatchArgs a, int n_split, int id_type, hipStream_t s) {
   if (id_type == BR_IDS_I64) launch_inbatch_t<MODE, int64_t>(a, n_split, s);
   else launch_inbatch_t<MODE, int32_t>(a, n_split, s);
 }
+// ---- hard negatives: the threshold sweep (MODE_THR) and the HARD forms.  ONE arithmetic per call: the body is chosen from the
+// candidate count and the width alone and handed to every sweep of the call, whichever operand it streams - the selection is
+// only reproducible on the same score bits (the plain rule above picks per mode and per streamed length).
+bool hard_emu(int64_t Bc, int dim) { return mlp_bf16x6() && Bc >= 4096 && (dim + 7) / 8 <= 8; }
+
+template <int MODE, int KQ, typename IdT, bool EMU, bool HARD>
+void launch_hard_e(const InbatchHardArgs& a, int n_split, hipStream_t s) {
+  constexpr int Kp = 8 * KQ, FT = (Kp + 31) / 32, KB = (Kp + 15) / 16;
+  constexpr bool GRAD = MODE == MODE_GRAD_R || MODE == MODE_GRAD_C || MODE == MODE_LSE_GRAD_R;
+  const size_t img = EMU ? (size_t)2 * KB * 3 * 2 * kGs * 4 + (GRAD ? (size_t)2 * 2 * FT * 3 * 2 * kGs * 4 : 0)
+                         : (size_t)kTs * (Kp + 4) + (GRAD ? (size_t)FT * 32 * kLdT : 0);
+  const size_t extra = MODE == MODE_THR ? (size_t)a.M * kOwn * sizeof(uint2) : (MODE == MODE_GRAD_C ? (size_t)kTs * 8 : 0);   // the heaps / the streamed thresholds
+  const size_t shmem = (img + kTs) * sizeof(float) + kTs * sizeof(IdT) + extra;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)inbatch_kernel<MODE, KQ, IdT, EMU, HARD, InbatchHardArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    attr = true;
+  }
+  const dim3 grid((unsigned)ceil_div(a.n_r, (int64_t)kOwn), (unsigned)n_split);
+  inbatch_kernel<MODE, KQ, IdT, EMU, HARD, InbatchHardArgs><<<grid, 256, shmem, s>>>(a);
+}
+template <int MODE, int KQ, typename IdT, bool HARD>
+void launch_hard_k(const InbatchHardArgs& a, int n_split, bool emu, hipStream_t s) {
+  if constexpr (KQ <= 8) {
+    if (emu) { launch_hard_e<MODE, KQ, IdT, true, HARD>(a, n_split, s); return; }
+  }
+  launch_hard_e<MODE, KQ, IdT, false, HARD>(a, n_split, s);
+}
+template <int MODE, typename IdT, bool HARD>
+void launch_hard_t(const InbatchHardArgs& a, int n_split, bool emu, hipStream_t s) {
+  const int kq = (a.dim + 7) / 8;
+  if (kq <= 4) launch_hard_k<MODE, 4, IdT, HARD>(a, n_split, emu, s);
+  else if (kq <= 7) launch_hard_k<MODE, 7, IdT, HARD>(a, n_split, emu, s);
+  else if (kq <= 8) launch_hard_k<MODE, 8, IdT, HARD>(a, n_split, emu, s);
+  else if (kq <= 13) launch_hard_k<MODE, 13, IdT, HARD>(a, n_split, emu, s);
+  else launch_hard_k<MODE, 16, IdT, HARD>(a, n_split, emu, s);
+}
+// emu: hard_emu of the CALL (not of this sweep's streamed length)
+template <int MODE>
+void launch_hard(InbatchHardArgs a, int n_split, int id_type, bool emu, hipStream_t s) {
+  constexpr bool HARD = MODE != MODE_THR;
+  const int64_t steps = ceil_div(a.n_t, (int64_t)kTs);
+  a.t_per_split = ceil_div(steps, (int64_t)n_split) * kTs;
+  n_split = (int)ceil_div(a.n_t, a.t_per_split);       // no empty split
+  if (id_type == BR_IDS_I64) launch_hard_t<MODE, int64_t, HARD>(a, n_split, emu, s);
+  else launch_hard_t<MODE, int32_t, HARD>(a, n_split, emu, s);
+}
+InbatchHardArgs hard_args(const InbatchArgs& b, const float* thr_s, const int32_t* thr_p) {
+  InbatchHardArgs h;
+  static_cast<InbatchArgs&>(h) = b;
+  h.thr_s = thr_s; h.thr_p = thr_p; h.thr_s_out = nullptr; h.thr_p_out = nullptr; h.lists = nullptr; h.M = 0; h.col0 = 0;
+  return h;
+}
 }  // namespace
 
 extern "C" int64_t brInBatchSoftmaxWorkspaceBytes(int64_t Bq, int64_t Bc, int dim) {
@@ -807,6 +1067,141 @@ extern "C" int brInBatchSoftmaxGrad(const float* Q, const float* C, const void* 
   if (dQ) { const int rc = grad_sweep<MODE_GRAD_R>(Q, C, Bq, Bc, dim, q_pos_ids, cand_ids, id_type, diag_offset, row_lse, dQ, ws, ws_bytes, s); if (rc) return rc; }
   // dC: candidates own, queries stream; the partner of candidate j is query j - diag_offset (the slabs of dQ are consumed by then)
   if (dC) { const int rc = grad_sweep<MODE_GRAD_C>(C, Q, Bc, Bq, dim, cand_ids, q_pos_ids, id_type, -diag_offset, row_lse, dC, ws, ws_bytes, s); if (rc) return rc; }
+  return BR_OK;
+}
+
+// ---- hard negatives: C-ABI ----
+#define BR_CHECK_HARD_COMMON(name)                                                                                                                  \
+  BR_CHECK_ARG(Q && C && Bq >= 0 && Bc >= 1 && Bc < ((int64_t)1 << 31) && dim >= 1 && dim <= 128, name ": bad args (dim <= 128, Bc < 2^31)");      \
+  BR_CHECK_ARG((q_pos_ids == nullptr) == (cand_ids == nullptr), name ": ids both or neither");                                                       \
+  BR_CHECK_ARG(id_type == BR_IDS_I32 || id_type == BR_IDS_I64, name ": bad id_type");                                                                \
+  BR_CHECK_ARG(ws_bytes >= 0 && (ws != nullptr || ws_bytes == 0), name ": bad workspace")
+
+extern "C" int64_t brInBatchSoftmaxHardWorkspaceBytes(int64_t Bq, int64_t Bc, int dim, int M) {
+  if (Bq <= 0 || Bc <= 0 || dim <= 0 || M < 1 || M > 64) return 0;
+  const int64_t plain = brInBatchSoftmaxWorkspaceBytes(Bq, Bc, dim);
+  const int64_t ns = choose_splits(Bq, Bc, 64);
+  const int64_t lists = ns > 1 ? ns * Bq * M * (int64_t)sizeof(uint2) : 0;
+  return plain > lists ? plain : lists;
+}
+
+extern "C" int brInBatchSoftmaxHardThreshold(const float* Q, const float* C, const void* q_pos_ids, const void* cand_ids, int id_type, int64_t Bq,
+                                             int64_t Bc, int dim, int64_t diag_offset, int M, float* thr_score, int32_t* thr_pos, void* ws,
+                                             int64_t ws_bytes, brStream stream) {
+  BR_CHECK_HARD_COMMON("brInBatchSoftmaxHardThreshold");
+  BR_CHECK_ARG(M >= 1 && M <= 64, "brInBatchSoftmaxHardThreshold: 1 <= M <= 64");
+  BR_CHECK_ARG(thr_score && thr_pos, "brInBatchSoftmaxHardThreshold: thr_score and thr_pos are required");
+  if (Bq == 0) return BR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int n_split = choose_splits(Bq, Bc, ws ? ws_bytes / (Bq * M * (int64_t)sizeof(uint2)) : 1);
+  const int64_t tps = ceil_div(ceil_div(Bc, (int64_t)kTs), (int64_t)n_split) * kTs;
+  const int ns = (int)ceil_div(Bc, tps);                 // splits actually launched (launch_hard recomputes the same)
+  InbatchHardArgs a = hard_args(InbatchArgs{Q, C, Bq, Bc, dim, q_pos_ids, cand_ids, diag_offset, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0}, nullptr, nullptr);
+  a.M = M;
+  if (n_split > 1) a.lists = (uint2*)ws; else { a.thr_s_out = thr_score; a.thr_p_out = thr_pos; }
+  launch_hard<MODE_THR>(a, n_split, id_type, hard_emu(Bc, dim), s);
+  BR_CHECK_LAUNCH("brInBatchSoftmaxHardThreshold");
+  if (n_split > 1) {
+    thr_combine_kernel<<<(unsigned)Bq, 64, (size_t)ns * M * sizeof(uint2), s>>>((const uint2*)ws, ns * M, M, Bc, diag_offset, thr_score, thr_pos);
+    BR_CHECK_LAUNCH("brInBatchSoftmaxHardThreshold(combine)");
+  }
+  return BR_OK;
+}
+
+extern "C" int brInBatchSoftmaxLseHard(const float* Q, const float* C, const void* q_pos_ids, const void* cand_ids, int id_type, int64_t Bq,
+                                       int64_t Bc, int dim, int64_t diag_offset, float* row_lse, double* loss_sum, const float* thr_score,
+                                       const int32_t* thr_pos, void* ws, int64_t ws_bytes, brStream stream) {
+  BR_CHECK_HARD_COMMON("brInBatchSoftmaxLseHard");
+  BR_CHECK_ARG(row_lse && thr_score && thr_pos, "brInBatchSoftmaxLseHard: row_lse, thr_score and thr_pos are required");
+  if (Bq == 0) return BR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int n_split = choose_splits(Bq, Bc, ws ? ws_bytes / (int64_t)(3 * Bq * sizeof(float)) : 1);
+  const InbatchHardArgs a = hard_args(InbatchArgs{Q, C, Bq, Bc, dim, q_pos_ids, cand_ids, diag_offset, nullptr, nullptr, 0, n_split > 1 ? (float*)ws : nullptr, row_lse, loss_sum, 0},
+                                      thr_score, thr_pos);
+  launch_hard<MODE_LSE>(a, n_split, id_type, hard_emu(Bc, dim), s);
+  BR_CHECK_LAUNCH("brInBatchSoftmaxLseHard");
+  if (n_split > 1) {
+    const int64_t tps = ceil_div(ceil_div(Bc, (int64_t)kTs), (int64_t)n_split) * kTs;
+    lse_combine_kernel<<<(unsigned)ceil_div(Bq, (int64_t)256), 256, 0, s>>>((const float*)ws, (int)ceil_div(Bc, tps), Bq, row_lse, loss_sum);
+    BR_CHECK_LAUNCH("brInBatchSoftmaxLseHard(combine)");
+  }
+  return BR_OK;
+}
+
+// one hard gradient sweep (grad_sweep with the thresholds of the QUERIES, owned or streamed)
+template <int MODE>
+static int grad_sweep_hard(const float* own, const float* str, int64_t n_own, int64_t n_str, int dim, const void* own_ids, const void* str_ids, int id_type,
+                           int64_t diag, const float* lse, const float* thr_s, const int32_t* thr_p, bool emu, int64_t col0, float* out, void* ws,
+                           int64_t ws_bytes, hipStream_t s) {
+  const int n_split = choose_splits(n_own, n_str, ws ? ws_bytes / (int64_t)(n_own * dim * sizeof(float)) : 1);
+  InbatchHardArgs a = hard_args(InbatchArgs{own, str, n_own, n_str, dim, own_ids, str_ids, diag, lse, n_split > 1 ? (float*)ws : out, dim, nullptr, nullptr, nullptr, 0},
+                                thr_s, thr_p);
+  a.col0 = col0;                                         // candidates own: their first column in the count of thr_p
+  launch_hard<MODE>(a, n_split, id_type, emu, s);
+  BR_CHECK_LAUNCH("brInBatchSoftmaxGradHard");
+  if (n_split > 1) {
+    const int64_t tps = ceil_div(ceil_div(n_str, (int64_t)kTs), (int64_t)n_split) * kTs;
+    const int64_t n = n_own * dim;
+    slab_sum_kernel<<<(unsigned)ceil_div(ceil_div(n, (int64_t)4), (int64_t)256), 256, 0, s>>>((const float*)ws, (int)ceil_div(n_str, tps), n, out);
+    BR_CHECK_LAUNCH("brInBatchSoftmaxGradHard(slab sum)");
+  }
+  return BR_OK;
+}
+
+extern "C" int brInBatchSoftmaxGradHard(const float* Q, const float* C, const void* q_pos_ids, const void* cand_ids, int id_type, int64_t Bq,
+                                        int64_t Bc, int dim, int64_t diag_offset, const float* row_lse, float* dQ, float* dC, const float* thr_score,
+                                        const int32_t* thr_pos, void* ws, int64_t ws_bytes, brStream stream) {
+  BR_CHECK_HARD_COMMON("brInBatchSoftmaxGradHard");
+  BR_CHECK_ARG(row_lse && thr_score && thr_pos, "brInBatchSoftmaxGradHard: row_lse, thr_score and thr_pos are required");
+  BR_CHECK_ARG(dQ || dC, "brInBatchSoftmaxGradHard: nothing to compute");
+  if (Bq == 0) return BR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bool emu = hard_emu(Bc, dim);
+  if (dQ) { const int rc = grad_sweep_hard<MODE_GRAD_R>(Q, C, Bq, Bc, dim, q_pos_ids, cand_ids, id_type, diag_offset, row_lse, thr_score, thr_pos, emu, 0, dQ, ws, ws_bytes, s); if (rc) return rc; }
+  if (dC) { const int rc = grad_sweep_hard<MODE_GRAD_C>(C, Q, Bc, Bq, dim, cand_ids, q_pos_ids, id_type, -diag_offset, row_lse, thr_score, thr_pos, emu, 0, dC, ws, ws_bytes, s); if (rc) return rc; }
+  return BR_OK;
+}
+
+// dC of a SLICE of the candidates the thresholds were taken over (the data-parallel step: every rank owns B of the world * B gathered
+// candidates).  The body is chosen from the candidate count of the threshold sweep, Bc_total, not from the slice's: the keys are only
+// meaningful against scores of the arithmetic that formed them.
+extern "C" int brInBatchSoftmaxGradHardSlice(const float* Q, const float* C, const void* q_pos_ids, const void* cand_ids, int id_type, int64_t Bq,
+                                             int64_t Bc, int dim, int64_t diag_offset, const float* row_lse, float* dC, const float* thr_score,
+                                             const int32_t* thr_pos, int64_t c0, int64_t Bc_total, void* ws, int64_t ws_bytes, brStream stream) {
+  BR_CHECK_HARD_COMMON("brInBatchSoftmaxGradHardSlice");
+  BR_CHECK_ARG(row_lse && dC && thr_score && thr_pos, "brInBatchSoftmaxGradHardSlice: row_lse, dC, thr_score and thr_pos are required");
+  BR_CHECK_ARG(c0 >= 0 && c0 + Bc <= Bc_total && Bc_total < ((int64_t)1 << 31), "brInBatchSoftmaxGradHardSlice: the slice [c0, c0 + Bc) must lie in [0, Bc_total), Bc_total < 2^31");
+  if (Bq == 0) return BR_OK;
+  return grad_sweep_hard<MODE_GRAD_C>(C, Q, Bc, Bq, dim, cand_ids, q_pos_ids, id_type, -diag_offset, row_lse, thr_score, thr_pos, hard_emu(Bc_total, dim), c0, dC, ws,
+                                      ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int brInBatchSoftmaxLseGradQHard(const float* Q, const float* C, const void* q_pos_ids, const void* cand_ids, int id_type, int64_t Bq,
+                                            int64_t Bc, int dim, int64_t diag_offset, float* row_lse, double* loss_sum, float* dQ,
+                                            const float* thr_score, const int32_t* thr_pos, void* ws, int64_t ws_bytes, brStream stream) {
+  BR_CHECK_HARD_COMMON("brInBatchSoftmaxLseGradQHard");
+  BR_CHECK_ARG(row_lse && dQ && thr_score && thr_pos, "brInBatchSoftmaxLseGradQHard: row_lse, dQ, thr_score and thr_pos are required");
+  if (Bq == 0) return BR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (dim > 64) {      // as brInBatchSoftmaxLseGradQ: the fused sweep's registers only fit up to 64 features
+    const int rc = brInBatchSoftmaxLseHard(Q, C, q_pos_ids, cand_ids, id_type, Bq, Bc, dim, diag_offset, row_lse, loss_sum, thr_score, thr_pos, ws, ws_bytes, stream);
+    if (rc != BR_OK) return rc;
+    return brInBatchSoftmaxGradHard(Q, C, q_pos_ids, cand_ids, id_type, Bq, Bc, dim, diag_offset, row_lse, dQ, nullptr, thr_score, thr_pos, ws, ws_bytes, stream);
+  }
+  const int64_t per_split = (Bq * dim + 3 * Bq) * (int64_t)sizeof(float);
+  const int n_split = choose_splits(Bq, Bc, ws ? ws_bytes / per_split : 1);
+  const int64_t tps = ceil_div(ceil_div(Bc, (int64_t)kTs), (int64_t)n_split) * kTs;
+  const int ns = (int)ceil_div(Bc, tps);
+  float* slabs = (float*)ws;
+  float* part = n_split > 1 ? slabs + (int64_t)ns * Bq * dim : nullptr;
+  const InbatchHardArgs a = hard_args(InbatchArgs{Q, C, Bq, Bc, dim, q_pos_ids, cand_ids, diag_offset, nullptr, n_split > 1 ? slabs : dQ, dim, part, row_lse, loss_sum, 0},
+                                      thr_score, thr_pos);
+  launch_hard<MODE_LSE_GRAD_R>(a, n_split, id_type, hard_emu(Bc, dim), s);
+  BR_CHECK_LAUNCH("brInBatchSoftmaxLseGradQHard");
+  if (n_split > 1) {
+    lse_grad_combine_kernel<<<(unsigned)ceil_div(Bq, (int64_t)4), 256, 0, s>>>(part, slabs, ns, Bq, dim, dim, C, Bc, diag_offset, row_lse, loss_sum, dQ);
+    BR_CHECK_LAUNCH("brInBatchSoftmaxLseGradQHard(combine)");
+  }
   return BR_OK;
 }
 

@@ -670,16 +670,19 @@ class TwoTowerModel:
     """trainers/twoTower.py:19-111 with the same constructor arguments."""
 
     def __init__(self, embedDim, nbrItem, nbrUser, userKey, itemKey, usersId, itemsId, eval_batch_size=8000, loss=None,
-                 rdZero=False, resKey=None, semb=100, device="cuda:0", max_batch=65536, learningRate=0.1, optimiser="Adagrad"):
+                 rdZero=False, resKey=None, semb=100, device="cuda:0", max_batch=65536, learningRate=0.1, optimiser="Adagrad",
+                 numHardNegatives=None, temperature=None):
+        """numHardNegatives / temperature: num_hard_negatives and temperature of tfrs.tasks.Retrieval (TwoTowerEngine); not with rdZero."""
         self.userKey, self.itemKey, self.resKey, self.rdZero, self.eval_batch_size = userKey, itemKey, resKey, rdZero, eval_batch_size
+        opts = dict(num_hard_negatives=numHardNegatives, temperature=temperature)
         self.userTowerIn, self.itemTowerIn = StringLookup(usersId), StringLookup(itemsId)
         ctx = _dist_ctx()
         if ctx is not None:      # under a process group the tables are row-sharded over the ranks (as NeuMFModel / BPRModel.compileModel)
             from .parallel import make_sharded_two_tower
             self.engine = make_sharded_two_tower(TwoTowerEngine)(embedDim, nbrItem, nbrUser, semb, _rank_device(device, ctx), max_batch, ctx,
-                                                                 lr=learningRate, optimizer=optimiser, rd_zero=rdZero)
+                                                                 lr=learningRate, optimizer=optimiser, rd_zero=rdZero, **opts)
         else:
-            self.engine = TwoTowerEngine(embedDim, nbrItem, nbrUser, semb, device, max_batch, lr=learningRate, optimizer=optimiser, rd_zero=rdZero)
+            self.engine = TwoTowerEngine(embedDim, nbrItem, nbrUser, semb, device, max_batch, lr=learningRate, optimizer=optimiser, rd_zero=rdZero, **opts)
         self._owners = ctx is not None       # candidates stay with the ranks that own their rows (engine.recommend, a collective)
         self.device = self.engine.device
         self._cand, self._cand_ids, self._cand_idx, self._k = None, None, None, None
@@ -701,7 +704,14 @@ class TwoTowerModel:
         ids = self.itemTowerIn(info[self.itemKey], self.device)
         slots = torch.zeros(ops.SUM_SLOTS, dtype=torch.float64, device=self.device)
         lse = torch.empty(q.shape[0], dtype=torch.float32, device=self.device)
-        ops.inbatch_softmax_lse(q, c, ids, ids, 0, lse, slots)
+        e = self.engine
+        if e.temperature is not None:
+            q = q * (1.0 / e.temperature)
+        thr = None
+        if e.num_hard_negatives is not None:
+            thr = (torch.empty_like(lse), torch.empty(q.shape[0], dtype=torch.int32, device=self.device))
+            ops.inbatch_softmax_hard_threshold(q, c, ids, ids, 0, e.num_hard_negatives, *thr)
+        ops.inbatch_softmax_lse(q, c, ids, ids, 0, lse, slots, thr=thr)
         return slots.sum().float()
 
     def computeLossRdZero(self, usersCaracteristics, itemCaracteristics, info):

@@ -640,9 +640,13 @@ METRIC_SUMS = 8  # BR_METRIC_SUMS: [loss, se, ae, correct, bce, tp, fp, fn]
 _softmax_ws = {}
 
 
-def _softmax_workspace(Q, C):
-    """scratch of the split in-batch softmax sweeps, one grow-only buffer per (device, stream)."""
-    need = int(_lib.load().brInBatchSoftmaxWorkspaceBytes(Q.shape[0], C.shape[0], Q.shape[1]))
+def _softmax_workspace(Q, C, hard_m=None):
+    """scratch of the split in-batch softmax sweeps, one grow-only buffer per (device, stream).  hard_m: the threshold sweep of M hard
+    negatives (its per-split key lists; never less than the plain count)."""
+    if hard_m is None:
+        need = int(_lib.load().brInBatchSoftmaxWorkspaceBytes(Q.shape[0], C.shape[0], Q.shape[1]))
+    else:
+        need = int(_lib.load().brInBatchSoftmaxHardWorkspaceBytes(Q.shape[0], C.shape[0], Q.shape[1], int(hard_m)))
     key = (Q.device, _stream())
     buf = _softmax_ws.get(key)
     if buf is None or buf.numel() < need:
@@ -651,29 +655,83 @@ def _softmax_workspace(Q, C):
     return buf
 
 
-def inbatch_softmax_lse(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum):
+MAX_HARD_NEGATIVES = 64
+
+
+def _thr(thr, Bq):
+    """thr = (thr_score float32 (Bq), thr_pos int32 (Bq)) of inbatch_softmax_hard_threshold -> the two pointers"""
+    ts, tp = thr
+    if ts.dtype != torch.float32 or tp.dtype != torch.int32 or not ts.is_contiguous() or not tp.is_contiguous() or ts.shape[0] != Bq or tp.shape[0] != Bq:
+        raise ValueError("thr = (thr_score float32, thr_pos int32), contiguous, one entry per query")
+    return ts.data_ptr(), tp.data_ptr()
+
+
+def inbatch_softmax_hard_threshold(Q, C, q_pos_ids, cand_ids, diag_offset, num_hard_negatives, thr_score, thr_pos):
+    """Per query the key (masked score, column) of the last of its num_hard_negatives (1..64) best negatives by (score descending,
+    column ascending) -> thr_score float32 (Bq), thr_pos int32 (Bq); (-inf, INT32_MAX) where nothing is cut.  The pair is the
+    thr= argument of the three wrappers below, which then run over the partner and those negatives only."""
+    qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
+    id_type = _same_id_type(qt, ct) if qi is not None else I32
+    ws = _softmax_workspace(Q, C, hard_m=num_hard_negatives)
+    tsp, tpp = _thr((thr_score, thr_pos), Q.shape[0])
+    check(_lib.load().brInBatchSoftmaxHardThreshold(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                    Q.shape[1], int(diag_offset), int(num_hard_negatives), tsp, tpp, ws.data_ptr(), ws.numel(), _stream()),
+          "brInBatchSoftmaxHardThreshold")
+
+
+def inbatch_softmax_lse(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, thr=None):
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C)
+    if thr is not None:
+        tsp, tpp = _thr(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxLseHard(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                  Q.shape[1], int(diag_offset), _f32(row_lse, "row_lse").data_ptr(), loss_sum.data_ptr(), tsp, tpp,
+                                                  ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxLseHard")
+        return
     check(_lib.load().brInBatchSoftmaxLse(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
                                           Q.shape[1], int(diag_offset), _f32(row_lse, "row_lse").data_ptr(), loss_sum.data_ptr(),
                                           ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxLse")
 
 
-def inbatch_softmax_lse_grad_q(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, dQ):
+def inbatch_softmax_lse_grad_q(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, dQ, thr=None):
     """lse + loss + dQ in one sweep (online softmax): the training step's first softmax pass."""
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C)
+    if thr is not None:
+        tsp, tpp = _thr(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxLseGradQHard(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                       Q.shape[1], int(diag_offset), _f32(row_lse, "row_lse").data_ptr(), loss_sum.data_ptr(),
+                                                       _f32(dQ, "dQ").data_ptr(), tsp, tpp, ws.data_ptr(), ws.numel(), _stream()),
+              "brInBatchSoftmaxLseGradQHard")
+        return
     check(_lib.load().brInBatchSoftmaxLseGradQ(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
                                                Q.shape[1], int(diag_offset), _f32(row_lse, "row_lse").data_ptr(), loss_sum.data_ptr(),
                                                _f32(dQ, "dQ").data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxLseGradQ")
 
 
-def inbatch_softmax_grad(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, dQ=None, dC=None):
+def inbatch_softmax_grad(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, dQ=None, dC=None, thr=None, thr_slice=None):
+    """thr: the hard form (inbatch_softmax_hard_threshold on the same Q and C).  thr_slice = (c0, Bc_total): C and cand_ids are rows
+    [c0, c0 + Bc) of the Bc_total candidates the thresholds were taken over (dC only; diag_offset relative to the slice, thr as the
+    threshold sweep wrote it) - the arithmetic then follows Bc_total, as the sweep that formed the keys."""
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C)
+    if thr_slice is not None:
+        if thr is None or dQ is not None or dC is None:
+            raise ValueError("thr_slice goes with thr and computes dC only")
+        tsp, tpp = _thr(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxGradHardSlice(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                        Q.shape[1], int(diag_offset), row_lse.data_ptr(), _p(dC), tsp, tpp, int(thr_slice[0]), int(thr_slice[1]),
+                                                        ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxGradHardSlice")
+        return
+    if thr is not None:
+        tsp, tpp = _thr(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxGradHard(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                   Q.shape[1], int(diag_offset), row_lse.data_ptr(), _p(dQ), _p(dC), tsp, tpp, ws.data_ptr(), ws.numel(),
+                                                   _stream()), "brInBatchSoftmaxGradHard")
+        return
     check(_lib.load().brInBatchSoftmaxGrad(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
                                            Q.shape[1], int(diag_offset), row_lse.data_ptr(), _p(dQ), _p(dC), ws.data_ptr(), ws.numel(), _stream()),
           "brInBatchSoftmaxGrad")

@@ -1047,13 +1047,20 @@ def make_sharded_two_tower(base_cls):
             ctx = self.ctx
             off = ctx.rank * B
             c_all, ids_all = ctx.all_gather_rows(c.contiguous()), ctx.all_gather_rows(items.contiguous())
+            q = self._scaled_q(q, B)
+            thr = self._hard_thr(q, c_all, items, ids_all, off, B)       # my queries against ALL candidates: the stripe sweep
             if dq is None:
-                ops.inbatch_softmax_lse(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots)
+                ops.inbatch_softmax_lse(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, thr=thr)
                 return
-            ops.inbatch_softmax_lse_grad_q(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, dq)     # lse + loss + dQ in one sweep
+            ops.inbatch_softmax_lse_grad_q(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, dq, thr=thr)     # lse + loss + dQ in one sweep
             q_all, lse_all = ctx.all_gather_rows(q.contiguous()), ctx.all_gather_rows(self.lse[:B].contiguous())
+            # the thresholds of ALL queries: their columns count over c_all, of which my candidates are rows [off, off + B) - and the dC sweep
+            # runs on the arithmetic of the stripe sweep that formed them (chosen from c_all's row count, not from B)
+            thr_all = None if thr is None else (ctx.all_gather_rows(thr[0].contiguous()), ctx.all_gather_rows(thr[1].contiguous()))
             # dC of MY candidates against ALL queries: query g's positive is my candidate g - rank*B
-            ops.inbatch_softmax_grad(q_all, c.contiguous(), ids_all, items, -off, lse_all, None, dc)
+            ops.inbatch_softmax_grad(q_all, c.contiguous(), ids_all, items, -off, lse_all, None, dc, thr=thr_all,
+                                     thr_slice=None if thr is None else (off, c_all.shape[0]))
+            self._unscale_dq(dq)
 
         def _apply_tables(self, users, items, B):
             xu, xi = self.xu, self.xi

@@ -32,10 +32,22 @@ class StringLookup:
 
 class TwoTowerEngine:
     def __init__(self, embed_dim: int, nbr_item: int, nbr_user: int, semb: int, device, max_batch: int, lr: float = 0.1,
-                 optimizer: str = "Adagrad", rd_zero: bool = False, id_dtype=torch.int32, init_seed: int = 0):
+                 optimizer: str = "Adagrad", rd_zero: bool = False, id_dtype=torch.int32, init_seed: int = 0,
+                 num_hard_negatives: int | None = None, temperature: float | None = None):
+        """num_hard_negatives / temperature: the options of tfrs.tasks.Retrieval [TF-sem]: the logits are divided by the temperature,
+        accidental hits masked, and each query's cross-entropy runs over its positive and its num_hard_negatives (1..64)
+        highest-scoring other candidates (ties to the lower batch position).  None: the plain in-batch softmax."""
         assert optimizer in ("Adagrad", "Adam")
         if embed_dim > 128 or semb > 128:
             raise ValueError("embedDim and semb <= 128 in this build")
+        if rd_zero and (num_hard_negatives is not None or temperature is not None):
+            raise ValueError("num_hard_negatives and temperature are options of the retrieval (softmax) loss: not with rd_zero")
+        if num_hard_negatives is not None and not 1 <= int(num_hard_negatives) <= ops.MAX_HARD_NEGATIVES:
+            raise ValueError(f"num_hard_negatives in 1..{ops.MAX_HARD_NEGATIVES}")
+        if temperature is not None and not (float(temperature) > 0 and math.isfinite(float(temperature))):
+            raise ValueError("temperature must be a positive finite number")
+        self.num_hard_negatives = None if num_hard_negatives is None else int(num_hard_negatives)
+        self.temperature = None if temperature is None else float(temperature)
         dev = self.device = torch.device(device)
         self.E, self.S, self.max_batch, self.lr, self.optimizer, self.rd_zero, self.id_dtype = embed_dim, semb, int(max_batch), lr, optimizer, rd_zero, id_dtype
         g = torch.Generator(device="cpu").manual_seed(init_seed)
@@ -56,6 +68,10 @@ class TwoTowerEngine:
         self.eu, self.ei, self.q, self.c = f(B, E), f(B, E), f(B, S), f(B, S)
         self.dq, self.dc, self.deu, self.dei = f(B, S), f(B, S), f(B, E), f(B, E)
         self.lse, self.z, self.dz, self.prob = f(B), f(B), f(B), f(B)
+        if self.temperature is not None:
+            self.q_t = f(B, S)                                   # q / temperature: what the softmax sweeps read
+        if self.num_hard_negatives is not None:                  # the key of every query's last kept negative (ops.inbatch_softmax_hard_threshold)
+            self.thr_score, self.thr_pos = f(B), torch.empty(B, dtype=torch.int32, device=dev)
         self.loss_slots = torch.zeros(ops.SUM_SLOTS, dtype=torch.float64, device=dev)
         self.ns = ops.dense_backward_slabs(B, E, S)
         self.slabs = f(self.ns * (E * S + S))
@@ -87,13 +103,35 @@ class TwoTowerEngine:
         """G1: both embedding lookups in one launch -> eu, ei (B x E)."""
         ops.gather_rows([self.user_emb, self.item_emb], [users, items], [self.eu[:B], self.ei[:B]], err_flag=self.err)
 
+    def _scaled_q(self, q, B):
+        """the logits are q.c / temperature: q is scaled once into a buffer, so the sweeps (VALU-bound) do no extra work per score;
+        dC comes out right as it stands and dq is scaled back by _unscale_dq"""
+        if self.temperature is None:
+            return q
+        return torch.mul(q, 1.0 / self.temperature, out=self.q_t[:B])
+
+    def _unscale_dq(self, dq):
+        if self.temperature is not None and dq is not None:
+            dq.mul_(1.0 / self.temperature)
+
+    def _hard_thr(self, q, c, q_ids, c_ids, off, B):
+        """the threshold sweep of the hard negatives -> the thr= of the softmax sweeps (None: plain)"""
+        if self.num_hard_negatives is None:
+            return None
+        thr = (self.thr_score[:B], self.thr_pos[:B])
+        ops.inbatch_softmax_hard_threshold(q, c, q_ids, c_ids, off, self.num_hard_negatives, *thr)
+        return thr
+
     def _softmax(self, q, c, items, B, dq, dc):
         """L4: in-batch softmax loss (+ gradients when dq is given) over the local batch."""
+        q = self._scaled_q(q, B)
+        thr = self._hard_thr(q, c, items, items, 0, B)
         if dq is None:
-            ops.inbatch_softmax_lse(q, c, items, items, 0, self.lse[:B], self.loss_slots)
+            ops.inbatch_softmax_lse(q, c, items, items, 0, self.lse[:B], self.loss_slots, thr=thr)
             return
-        ops.inbatch_softmax_lse_grad_q(q, c, items, items, 0, self.lse[:B], self.loss_slots, dq)      # lse + loss + dQ in one sweep
-        ops.inbatch_softmax_grad(q, c, items, items, 0, self.lse[:B], None, dc)
+        ops.inbatch_softmax_lse_grad_q(q, c, items, items, 0, self.lse[:B], self.loss_slots, dq, thr=thr)      # lse + loss + dQ in one sweep
+        ops.inbatch_softmax_grad(q, c, items, items, 0, self.lse[:B], None, dc, thr=thr)
+        self._unscale_dq(dq)
 
     def _start_indexes(self, users, items):
         """the two dedup indexes depend only on the ids: each on a side stream of its own beside the lookup / towers / softmax, joined in

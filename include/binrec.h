@@ -410,6 +410,54 @@ int brInBatchSoftmaxGrad(const float* Q, const float* C, const void* q_pos_ids,
                          int64_t diag_offset, const float* row_lse, float* dQ, float* dC,
                          void* ws, int64_t ws_bytes, brStream stream);
 
+/* ---- L4 with hard negatives (tfrs.tasks.Retrieval num_hard_negatives = M) [TF-sem] -------------
+ * Per query i the softmax runs over its partner column p_i = i + diag_offset and the set H_i: the first min(M, #negatives)
+ * of the columns j != p_i ordered by (masked score x_ij descending, j ascending) - a tie at the cut goes to the lower
+ * column, as tf.nn.top_k does.  x_ij is the score of the plain entries, accidental-hit mask included.  1 <= M <= 64.
+ * Scratch for every entry below (>= brInBatchSoftmaxWorkspaceBytes; the per-split key lists of the threshold sweep). */
+int64_t brInBatchSoftmaxHardWorkspaceBytes(int64_t Bq, int64_t Bc, int dim, int M);
+/* The key of the LAST member of H_i: thr_score[i] (float32) and thr_pos[i] (its column, int32).  A query with at most M
+ * negatives gets (-inf, INT32_MAX): nothing is cut.  One sweep in the tile layout of brInBatchSoftmaxLse (queries own,
+ * candidates stream) with the M best keys of every owned query in LDS; with a workspace the candidate axis is split and a
+ * second launch takes the M-th key of the union of a query's lists in a fixed order (bit-reproducible, no atomics).
+ * Bc < 2^31. */
+int brInBatchSoftmaxHardThreshold(const float* Q, const float* C, const void* q_pos_ids,
+                                  const void* cand_ids, int id_type, int64_t Bq, int64_t Bc,
+                                  int dim, int64_t diag_offset, int M, float* thr_score,
+                                  int32_t* thr_pos, void* ws, int64_t ws_bytes, brStream stream);
+/* The three entries above over the kept columns only: column j of query i takes part iff j == p_i, or x_ij > thr_score[i],
+ * or x_ij == thr_score[i] and j <= thr_pos[i] (thr_score / thr_pos per QUERY, of brInBatchSoftmaxHardThreshold on the same
+ * Q, C, ids, Bq, Bc, dim and diag_offset; both required).  Every sweep of these entries and the threshold sweep forms
+ * its scores with one arithmetic, chosen from (Bc, dim) alone, so that all of them agree on H_i bit for bit. */
+int brInBatchSoftmaxLseHard(const float* Q, const float* C, const void* q_pos_ids,
+                            const void* cand_ids, int id_type, int64_t Bq, int64_t Bc, int dim,
+                            int64_t diag_offset, float* row_lse, double* loss_sum,
+                            const float* thr_score, const int32_t* thr_pos, void* ws,
+                            int64_t ws_bytes, brStream stream);
+/* brInBatchSoftmaxLseGradQ over the kept columns (above 64 features: brInBatchSoftmaxLseHard + brInBatchSoftmaxGradHard(dQ)). */
+int brInBatchSoftmaxLseGradQHard(const float* Q, const float* C, const void* q_pos_ids,
+                                 const void* cand_ids, int id_type, int64_t Bq, int64_t Bc,
+                                 int dim, int64_t diag_offset, float* row_lse, double* loss_sum,
+                                 float* dQ, const float* thr_score, const int32_t* thr_pos,
+                                 void* ws, int64_t ws_bytes, brStream stream);
+/* brInBatchSoftmaxGrad over the kept columns; the dC sweep streams the queries with their thresholds.  C must be the
+ * candidates the thresholds were taken over, all of them: thr_pos counts their columns and the arithmetic follows their count. */
+int brInBatchSoftmaxGradHard(const float* Q, const float* C, const void* q_pos_ids,
+                             const void* cand_ids, int id_type, int64_t Bq, int64_t Bc, int dim,
+                             int64_t diag_offset, const float* row_lse, float* dQ, float* dC,
+                             const float* thr_score, const int32_t* thr_pos, void* ws,
+                             int64_t ws_bytes, brStream stream);
+/* dC of a SLICE of those candidates (the data-parallel step: a rank owns B of the world * B gathered candidates, all Bq
+ * gathered queries stream past them with their thresholds): C and cand_ids hold rows [c0, c0 + Bc) of the Bc_total
+ * candidates of the threshold sweep, diag_offset is relative to the slice (query i's positive is row i + diag_offset of
+ * C), thr_pos stays as the threshold sweep wrote it.  The arithmetic is chosen from (Bc_total, dim) - that of the sweep that
+ * formed the keys - not from the slice's Bc, so every rank keeps exactly the columns the whole-batch call would keep. */
+int brInBatchSoftmaxGradHardSlice(const float* Q, const float* C, const void* q_pos_ids,
+                                  const void* cand_ids, int id_type, int64_t Bq, int64_t Bc,
+                                  int dim, int64_t diag_offset, const float* row_lse, float* dC,
+                                  const float* thr_score, const int32_t* thr_pos, int64_t c0,
+                                  int64_t Bc_total, void* ws, int64_t ws_bytes, brStream stream);
+
 /* scores[q][c] = Q[q]·C[c] (n_q x n_c, row stride ld_scores): candidate scoring for top-k
  * (TwoTower BruteForce, twoTower.py:64-69,229-230; bpr_predict, src/models/bpr.py:122-133). */
 int brScoreMatrix(const float* Q, const float* C, int64_t n_q, int64_t n_c, int dim, float* scores,
