@@ -666,15 +666,53 @@ class BPRModel(RModel):
         return hist
 
 
+def sampling_probability_rows(p, itemsId):
+    """candidateSamplingProbability of TwoTowerModel -> one float64 per row of the item table (len(itemsId) + 2): a sequence aligned with
+    itemsId, or a dict item -> p (an item it lacks: ValueError).  The two reserved rows ('' and OOV) get p = 1: no correction."""
+    items = [str(i) for i in itemsId]
+    if isinstance(p, dict):
+        by = {str(k): v for k, v in p.items()}
+        missing = [i for i in items if i not in by]
+        if missing:
+            raise ValueError(f"candidateSamplingProbability: no value for {len(missing)} item(s), e.g. {missing[0]!r}")
+        vals = [float(by[i]) for i in items]
+    else:
+        vals = np.asarray(p, dtype=np.float64).reshape(-1)
+        if vals.shape[0] != len(items):
+            raise ValueError(f"candidateSamplingProbability: one value per entry of itemsId ({len(items)}), got {vals.shape[0]}")
+    return np.concatenate([np.ones(2), np.asarray(vals, dtype=np.float64)])
+
+
+def item_frequencies(batches, itemKey, itemsId):
+    """count / total of info[itemKey] over an iterable of info dicts, aligned with itemsId (float64; items outside itemsId count in the
+    total only, as the OOV row would) - the usual source of candidateSamplingProbability."""
+    pos = {str(v): i for i, v in enumerate(itemsId)}
+    count = np.zeros(len(pos), dtype=np.int64)
+    total = 0
+    for info in batches:
+        keys = info[itemKey]
+        keys = keys.tolist() if hasattr(keys, "tolist") else list(keys)
+        total += len(keys)
+        idx = [pos[str(k)] for k in keys if str(k) in pos]
+        if idx:
+            count += np.bincount(np.asarray(idx, dtype=np.int64), minlength=len(pos))
+    return count / max(total, 1)
+
+
 class TwoTowerModel:
     """trainers/twoTower.py:19-111 with the same constructor arguments."""
 
     def __init__(self, embedDim, nbrItem, nbrUser, userKey, itemKey, usersId, itemsId, eval_batch_size=8000, loss=None,
                  rdZero=False, resKey=None, semb=100, device="cuda:0", max_batch=65536, learningRate=0.1, optimiser="Adagrad",
-                 numHardNegatives=None, temperature=None):
-        """numHardNegatives / temperature: num_hard_negatives and temperature of tfrs.tasks.Retrieval (TwoTowerEngine); not with rdZero."""
+                 numHardNegatives=None, temperature=None, candidateSamplingProbability=None):
+        """numHardNegatives / temperature: num_hard_negatives and temperature of tfrs.tasks.Retrieval (TwoTowerEngine); not with rdZero.
+        candidateSamplingProbability: the task's candidate_sampling_probability (log-Q correction) - a sequence aligned with itemsId or a
+        dict item -> p (sampling_probability_rows; itemFrequencies gives the usual one); not with rdZero."""
         self.userKey, self.itemKey, self.resKey, self.rdZero, self.eval_batch_size = userKey, itemKey, resKey, rdZero, eval_batch_size
+        self.itemsId = list(itemsId)
         opts = dict(num_hard_negatives=numHardNegatives, temperature=temperature)
+        if candidateSamplingProbability is not None:
+            opts["candidate_sampling_probability"] = sampling_probability_rows(candidateSamplingProbability, self.itemsId)
         self.userTowerIn, self.itemTowerIn = StringLookup(usersId), StringLookup(itemsId)
         ctx = _dist_ctx()
         if ctx is not None:      # under a process group the tables are row-sharded over the ranks (as NeuMFModel / BPRModel.compileModel)
@@ -687,6 +725,13 @@ class TwoTowerModel:
         self.device = self.engine.device
         self._cand, self._cand_ids, self._cand_idx, self._k = None, None, None, None
         self._loss_seen = torch.zeros((), dtype=torch.float64, device=self.device)
+
+    def itemFrequencies(self, batches):
+        """count / total of info[itemKey] over an iterable of info dicts, aligned with itemsId (item_frequencies)."""
+        return item_frequencies(batches, self.itemKey, self.itemsId)
+
+    def setCandidateSamplingProbability(self, p):
+        self.engine.set_candidate_sampling_probability(None if p is None else sampling_probability_rows(p, self.itemsId))
 
     def _ids(self, info):
         return (self.userTowerIn(info[self.userKey], self.device), self.itemTowerIn(info[self.itemKey], self.device))
@@ -707,11 +752,12 @@ class TwoTowerModel:
         e = self.engine
         if e.temperature is not None:
             q = q * (1.0 / e.temperature)
+        logq = e._logq(ids, torch.empty_like(lse))                # the log-Q correction of the batch's candidates (None: not set)
         thr = None
         if e.num_hard_negatives is not None:
             thr = (torch.empty_like(lse), torch.empty(q.shape[0], dtype=torch.int32, device=self.device))
-            ops.inbatch_softmax_hard_threshold(q, c, ids, ids, 0, e.num_hard_negatives, *thr)
-        ops.inbatch_softmax_lse(q, c, ids, ids, 0, lse, slots, thr=thr)
+            ops.inbatch_softmax_hard_threshold(q, c, ids, ids, 0, e.num_hard_negatives, *thr, logq=logq)
+        ops.inbatch_softmax_lse(q, c, ids, ids, 0, lse, slots, thr=thr, logq=logq)
         return slots.sum().float()
 
     def computeLossRdZero(self, usersCaracteristics, itemCaracteristics, info):

@@ -666,23 +666,47 @@ def _thr(thr, Bq):
     return ts.data_ptr(), tp.data_ptr()
 
 
-def inbatch_softmax_hard_threshold(Q, C, q_pos_ids, cand_ids, diag_offset, num_hard_negatives, thr_score, thr_pos):
+def _logq(logq, Bc):
+    """logq = log of the clipped sampling probability of every candidate ROW of the C that is passed (float32, Bc) -> its pointer"""
+    if logq.dtype != torch.float32 or not logq.is_contiguous() or logq.numel() != Bc:
+        raise ValueError("logq: float32, contiguous, one entry per candidate row")
+    return logq.data_ptr()
+
+
+def _thr_or_null(thr, Bq):
+    return (None, None) if thr is None else _thr(thr, Bq)
+
+
+def inbatch_softmax_hard_threshold(Q, C, q_pos_ids, cand_ids, diag_offset, num_hard_negatives, thr_score, thr_pos, logq=None):
     """Per query the key (masked score, column) of the last of its num_hard_negatives (1..64) best negatives by (score descending,
     column ascending) -> thr_score float32 (Bq), thr_pos int32 (Bq); (-inf, INT32_MAX) where nothing is cut.  The pair is the
-    thr= argument of the three wrappers below, which then run over the partner and those negatives only."""
+    thr= argument of the three wrappers below, which then run over the partner and those negatives only.
+    logq= (here and below): the log-Q correction, scores Q.C - logq[column] before the mask and the selection; every
+    sweep of one step takes the same logq."""
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C, hard_m=num_hard_negatives)
     tsp, tpp = _thr((thr_score, thr_pos), Q.shape[0])
+    if logq is not None:
+        check(_lib.load().brInBatchSoftmaxHardThresholdLogQ(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                            Q.shape[1], int(diag_offset), int(num_hard_negatives), tsp, tpp, _logq(logq, C.shape[0]),
+                                                            ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxHardThresholdLogQ")
+        return
     check(_lib.load().brInBatchSoftmaxHardThreshold(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
                                                     Q.shape[1], int(diag_offset), int(num_hard_negatives), tsp, tpp, ws.data_ptr(), ws.numel(), _stream()),
           "brInBatchSoftmaxHardThreshold")
 
 
-def inbatch_softmax_lse(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, thr=None):
+def inbatch_softmax_lse(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, thr=None, logq=None):
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C)
+    if logq is not None:
+        tsp, tpp = _thr_or_null(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxLseLogQ(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                  Q.shape[1], int(diag_offset), _f32(row_lse, "row_lse").data_ptr(), loss_sum.data_ptr(), tsp, tpp,
+                                                  _logq(logq, C.shape[0]), ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxLseLogQ")
+        return
     if thr is not None:
         tsp, tpp = _thr(thr, Q.shape[0])
         check(_lib.load().brInBatchSoftmaxLseHard(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
@@ -694,11 +718,18 @@ def inbatch_softmax_lse(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_su
                                           ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxLse")
 
 
-def inbatch_softmax_lse_grad_q(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, dQ, thr=None):
+def inbatch_softmax_lse_grad_q(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, loss_sum, dQ, thr=None, logq=None):
     """lse + loss + dQ in one sweep (online softmax): the training step's first softmax pass."""
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C)
+    if logq is not None:
+        tsp, tpp = _thr_or_null(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxLseGradQLogQ(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                       Q.shape[1], int(diag_offset), _f32(row_lse, "row_lse").data_ptr(), loss_sum.data_ptr(),
+                                                       _f32(dQ, "dQ").data_ptr(), tsp, tpp, _logq(logq, C.shape[0]), ws.data_ptr(), ws.numel(), _stream()),
+              "brInBatchSoftmaxLseGradQLogQ")
+        return
     if thr is not None:
         tsp, tpp = _thr(thr, Q.shape[0])
         check(_lib.load().brInBatchSoftmaxLseGradQHard(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
@@ -711,13 +742,23 @@ def inbatch_softmax_lse_grad_q(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, 
                                                _f32(dQ, "dQ").data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxLseGradQ")
 
 
-def inbatch_softmax_grad(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, dQ=None, dC=None, thr=None, thr_slice=None):
+def inbatch_softmax_grad(Q, C, q_pos_ids, cand_ids, diag_offset, row_lse, dQ=None, dC=None, thr=None, thr_slice=None, logq=None):
     """thr: the hard form (inbatch_softmax_hard_threshold on the same Q and C).  thr_slice = (c0, Bc_total): C and cand_ids are rows
     [c0, c0 + Bc) of the Bc_total candidates the thresholds were taken over (dC only; diag_offset relative to the slice, thr as the
-    threshold sweep wrote it) - the arithmetic then follows Bc_total, as the sweep that formed the keys."""
+    threshold sweep wrote it) - the arithmetic then follows Bc_total, as the sweep that formed the keys.
+    logq: the log-Q form; with thr_slice it is the slice form (logq of the slice's rows; thr may then be None: the plain softmax)."""
     qi, qt = _ids(q_pos_ids, "q_pos_ids"); ci, ct = _ids(cand_ids, "cand_ids")
     id_type = _same_id_type(qt, ct) if qi is not None else I32
     ws = _softmax_workspace(Q, C)
+    if logq is not None:
+        if thr_slice is not None and (dQ is not None or dC is None):
+            raise ValueError("thr_slice computes dC only")
+        c0, total = (0, C.shape[0]) if thr_slice is None else (int(thr_slice[0]), int(thr_slice[1]))
+        tsp, tpp = _thr_or_null(thr, Q.shape[0])
+        check(_lib.load().brInBatchSoftmaxGradLogQ(_f32(Q, "Q").data_ptr(), _f32(C, "C").data_ptr(), _p(qi), _p(ci), id_type, Q.shape[0], C.shape[0],
+                                                   Q.shape[1], int(diag_offset), row_lse.data_ptr(), _p(dQ), _p(dC), tsp, tpp, _logq(logq, C.shape[0]),
+                                                   c0, total, ws.data_ptr(), ws.numel(), _stream()), "brInBatchSoftmaxGradLogQ")
+        return
     if thr_slice is not None:
         if thr is None or dQ is not None or dC is None:
             raise ValueError("thr_slice goes with thr and computes dC only")

@@ -1048,18 +1048,26 @@ def make_sharded_two_tower(base_cls):
             off = ctx.rank * B
             c_all, ids_all = ctx.all_gather_rows(c.contiguous()), ctx.all_gather_rows(items.contiguous())
             q = self._scaled_q(q, B)
-            thr = self._hard_thr(q, c_all, items, ids_all, off, B)       # my queries against ALL candidates: the stripe sweep
+            # log-Q: the table is replicated (item rows x 4 bytes), so b of ALL candidates is a local gather from the gathered ids - no collective
+            b_all = None
+            if self.cand_log_q is not None:
+                if getattr(self, "_logq_all", None) is None or self._logq_all.numel() < ids_all.shape[0]:
+                    self._logq_all = torch.empty(max(ids_all.shape[0], ctx.world * self.max_batch), dtype=torch.float32, device=self.device)
+                b_all = self._logq(ids_all, self._logq_all[:ids_all.shape[0]])
+            thr = self._hard_thr(q, c_all, items, ids_all, off, B, logq=b_all)       # my queries against ALL candidates: the stripe sweep
             if dq is None:
-                ops.inbatch_softmax_lse(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, thr=thr)
+                ops.inbatch_softmax_lse(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, thr=thr, logq=b_all)
                 return
-            ops.inbatch_softmax_lse_grad_q(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, dq, thr=thr)     # lse + loss + dQ in one sweep
+            ops.inbatch_softmax_lse_grad_q(q, c_all, items, ids_all, off, self.lse[:B], self.loss_slots, dq, thr=thr, logq=b_all)     # lse + loss + dQ in one sweep
             q_all, lse_all = ctx.all_gather_rows(q.contiguous()), ctx.all_gather_rows(self.lse[:B].contiguous())
             # the thresholds of ALL queries: their columns count over c_all, of which my candidates are rows [off, off + B) - and the dC sweep
             # runs on the arithmetic of the stripe sweep that formed them (chosen from c_all's row count, not from B)
             thr_all = None if thr is None else (ctx.all_gather_rows(thr[0].contiguous()), ctx.all_gather_rows(thr[1].contiguous()))
-            # dC of MY candidates against ALL queries: query g's positive is my candidate g - rank*B
+            # dC of MY candidates against ALL queries: query g's positive is my candidate g - rank*B.  (log-Q: the slice form also without
+            # thresholds - the arithmetic of a log-Q call follows the whole candidate count)
             ops.inbatch_softmax_grad(q_all, c.contiguous(), ids_all, items, -off, lse_all, None, dc, thr=thr_all,
-                                     thr_slice=None if thr is None else (off, c_all.shape[0]))
+                                     thr_slice=None if (thr is None and b_all is None) else (off, c_all.shape[0]),
+                                     logq=None if b_all is None else b_all[off:off + B])
             self._unscale_dq(dq)
 
         def _apply_tables(self, users, items, B):

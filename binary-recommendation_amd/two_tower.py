@@ -30,11 +30,31 @@ class StringLookup:
         return torch.tensor(idx, dtype=dtype, device=device)
 
 
+LOGQ_CLIP = 1e-6      # tfrs.tasks.Retrieval: log(clip(candidate_sampling_probability, 1e-6, 1))
+
+
+def candidate_log_q(p, rows: int) -> torch.Tensor:
+    """The table of the log-Q correction from the sampling probability of every row of the item table (a tensor or an array of `rows`
+    values): log(clip(p, 1e-6, 1)), formed in float64 and rounded once -> float32 (rows,) on the host.  A wrong length, a NaN or a
+    negative value raises ValueError (checked here, on the host, before anything reaches a kernel)."""
+    t = torch.as_tensor(p).detach().to("cpu", torch.float64).reshape(-1)
+    if t.numel() != rows:
+        raise ValueError(f"candidate_sampling_probability: one value per row of the item table ({rows}), got {t.numel()}")
+    if bool(torch.isnan(t).any()):
+        raise ValueError("candidate_sampling_probability: NaN")
+    if bool((t < 0).any()):
+        raise ValueError("candidate_sampling_probability: negative value")
+    return torch.log(torch.clamp(t, LOGQ_CLIP, 1.0)).to(torch.float32)
+
+
 class TwoTowerEngine:
     def __init__(self, embed_dim: int, nbr_item: int, nbr_user: int, semb: int, device, max_batch: int, lr: float = 0.1,
                  optimizer: str = "Adagrad", rd_zero: bool = False, id_dtype=torch.int32, init_seed: int = 0,
-                 num_hard_negatives: int | None = None, temperature: float | None = None):
-        """num_hard_negatives / temperature: the options of tfrs.tasks.Retrieval [TF-sem]: the logits are divided by the temperature,
+                 num_hard_negatives: int | None = None, temperature: float | None = None, candidate_sampling_probability=None):
+        """candidate_sampling_probability: Retrieval's log-Q correction (Yi et al. 2019): one probability per row of the item table
+        (nbr_item + 2); the logit of candidate j is q.c_j / temperature - log(clip(p_j, 1e-6, 1)), the positive's included, before the
+        accidental-hit mask and the hard negatives.  Serving (recommend, catalog_ranks, rank_metrics) keeps q.c.
+        num_hard_negatives / temperature: the options of tfrs.tasks.Retrieval [TF-sem]: the logits are divided by the temperature,
         accidental hits masked, and each query's cross-entropy runs over its positive and its num_hard_negatives (1..64)
         highest-scoring other candidates (ties to the lower batch position).  None: the plain in-batch softmax."""
         assert optimizer in ("Adagrad", "Adam")
@@ -46,6 +66,10 @@ class TwoTowerEngine:
             raise ValueError(f"num_hard_negatives in 1..{ops.MAX_HARD_NEGATIVES}")
         if temperature is not None and not (float(temperature) > 0 and math.isfinite(float(temperature))):
             raise ValueError("temperature must be a positive finite number")
+        if rd_zero and candidate_sampling_probability is not None:
+            raise ValueError("candidate_sampling_probability is an option of the retrieval (softmax) loss: not with rd_zero")
+        self.item_rows = nbr_item + 2
+        logq = None if candidate_sampling_probability is None else candidate_log_q(candidate_sampling_probability, self.item_rows)
         self.num_hard_negatives = None if num_hard_negatives is None else int(num_hard_negatives)
         self.temperature = None if temperature is None else float(temperature)
         dev = self.device = torch.device(device)
@@ -72,6 +96,10 @@ class TwoTowerEngine:
             self.q_t = f(B, S)                                   # q / temperature: what the softmax sweeps read
         if self.num_hard_negatives is not None:                  # the key of every query's last kept negative (ops.inbatch_softmax_hard_threshold)
             self.thr_score, self.thr_pos = f(B), torch.empty(B, dtype=torch.int32, device=dev)
+        self.cand_log_q = None                                   # (item rows,) float32: the log-Q table, replicated on every rank
+        self.logq_b = f(B)                                       # its entries at the step's candidates
+        if logq is not None:
+            self.cand_log_q = logq.to(dev)
         self.loss_slots = torch.zeros(ops.SUM_SLOTS, dtype=torch.float64, device=dev)
         self.ns = ops.dense_backward_slabs(B, E, S)
         self.slabs = f(self.ns * (E * S + S))
@@ -114,23 +142,49 @@ class TwoTowerEngine:
         if self.temperature is not None and dq is not None:
             dq.mul_(1.0 / self.temperature)
 
-    def _hard_thr(self, q, c, q_ids, c_ids, off, B):
+    def set_candidate_sampling_probability(self, p):
+        """Set, replace or (None) drop the log-Q table.  Replacing a table writes in place: a captured graph stays valid and its next
+        replay uses the new values.  Turning the option on or off changes the step's launches: the graph is dropped."""
+        if p is None:
+            if self.cand_log_q is not None:
+                self.disable_graph()
+            self.cand_log_q = None
+            return
+        if self.rd_zero:
+            raise ValueError("candidate_sampling_probability is an option of the retrieval (softmax) loss: not with rd_zero")
+        logq = candidate_log_q(p, self.item_rows)
+        if self.cand_log_q is None:
+            self.disable_graph()
+            self.cand_log_q = logq.to(self.device)
+        else:
+            self.cand_log_q.copy_(logq)
+
+    def _logq(self, c_ids, out):
+        """b of the step's candidates: one gather from the log-Q table viewed as (rows, 1) (an out-of-range id raises the error flag and
+        reads as 0, as in the embedding lookups) -> the logq= of the softmax sweeps (None: no correction)"""
+        if self.cand_log_q is None:
+            return None
+        ops.gather_rows([self.cand_log_q.view(-1, 1)], [c_ids], [out.view(-1, 1)], err_flag=self.err)
+        return out
+
+    def _hard_thr(self, q, c, q_ids, c_ids, off, B, logq=None):
         """the threshold sweep of the hard negatives -> the thr= of the softmax sweeps (None: plain)"""
         if self.num_hard_negatives is None:
             return None
         thr = (self.thr_score[:B], self.thr_pos[:B])
-        ops.inbatch_softmax_hard_threshold(q, c, q_ids, c_ids, off, self.num_hard_negatives, *thr)
+        ops.inbatch_softmax_hard_threshold(q, c, q_ids, c_ids, off, self.num_hard_negatives, *thr, logq=logq)
         return thr
 
     def _softmax(self, q, c, items, B, dq, dc):
         """L4: in-batch softmax loss (+ gradients when dq is given) over the local batch."""
         q = self._scaled_q(q, B)
-        thr = self._hard_thr(q, c, items, items, 0, B)
+        logq = self._logq(items, self.logq_b[:B])
+        thr = self._hard_thr(q, c, items, items, 0, B, logq=logq)
         if dq is None:
-            ops.inbatch_softmax_lse(q, c, items, items, 0, self.lse[:B], self.loss_slots, thr=thr)
+            ops.inbatch_softmax_lse(q, c, items, items, 0, self.lse[:B], self.loss_slots, thr=thr, logq=logq)
             return
-        ops.inbatch_softmax_lse_grad_q(q, c, items, items, 0, self.lse[:B], self.loss_slots, dq, thr=thr)      # lse + loss + dQ in one sweep
-        ops.inbatch_softmax_grad(q, c, items, items, 0, self.lse[:B], None, dc, thr=thr)
+        ops.inbatch_softmax_lse_grad_q(q, c, items, items, 0, self.lse[:B], self.loss_slots, dq, thr=thr, logq=logq)      # lse + loss + dQ in one sweep
+        ops.inbatch_softmax_grad(q, c, items, items, 0, self.lse[:B], None, dc, thr=thr, logq=logq)
         self._unscale_dq(dq)
 
     def _start_indexes(self, users, items):
@@ -308,9 +362,16 @@ class TwoTowerEngine:
     def state_dict(self) -> dict:
         sd = {"t": self.t}
         sd.update({k: getattr(self, k) for k in self._state_names()})
+        if self.cand_log_q is not None:                          # only with the option: the state dicts of engines without it stay as they were
+            sd["cand_log_q"] = self.cand_log_q
         return sd
 
     def load_state_dict(self, sd: dict):
         self.t = int(sd["t"])
         for k in self._state_names():
             getattr(self, k).copy_(sd[k])
+        if "cand_log_q" in sd:
+            if self.cand_log_q is None:
+                self.disable_graph()
+                self.cand_log_q = torch.empty(self.item_rows, dtype=torch.float32, device=self.device)
+            self.cand_log_q.copy_(sd["cand_log_q"])

@@ -458,6 +458,44 @@ int brInBatchSoftmaxGradHardSlice(const float* Q, const float* C, const void* q_
                                   const float* thr_score, const int32_t* thr_pos, int64_t c0,
                                   int64_t Bc_total, void* ws, int64_t ws_bytes, brStream stream);
 
+/* Log-Q correction: Retrieval's candidate_sampling_probability (tfrs.tasks.Retrieval; twoTower.py:47,82-83 builds the task
+ * and does not pass the option) [TF-sem], after Yi et al. 2019.  The score of every entry below is
+ * x_ij = Q_i . C_j - cand_logq[j], the partner's column included; then the accidental-hit mask, then the hard negatives
+ * (selected on the corrected, masked scores).  cand_logq: Bc floats, one per row of the C that is passed (as cand_ids),
+ * log of the clipped sampling probability; required, finite (device data is not checked).  Each entry is its Hard twin
+ * plus cand_logq; thr_score / thr_pos both NULL selects the plain softmax over every column (one without the other is
+ * refused).  One arithmetic per call, chosen from (Bc or Bc_total, dim) as the Hard entries choose it, with or without
+ * thresholds; the subtraction is one fp32 rounding of the finished dot product, fl(s - b), the same in every sweep.  Scratch:
+ * brInBatchSoftmaxHardWorkspaceBytes for M >= 1, brInBatchSoftmaxWorkspaceBytes otherwise. */
+/* brInBatchSoftmaxHardThreshold on the corrected scores (thr_score / thr_pos are its outputs: required). */
+int brInBatchSoftmaxHardThresholdLogQ(const float* Q, const float* C, const void* q_pos_ids,
+                                      const void* cand_ids, int id_type, int64_t Bq, int64_t Bc,
+                                      int dim, int64_t diag_offset, int M, float* thr_score,
+                                      int32_t* thr_pos, const float* cand_logq, void* ws,
+                                      int64_t ws_bytes, brStream stream);
+/* brInBatchSoftmaxLse / brInBatchSoftmaxLseHard on the corrected scores; the loss term of a row is lse_i - x_i,p_i. */
+int brInBatchSoftmaxLseLogQ(const float* Q, const float* C, const void* q_pos_ids,
+                            const void* cand_ids, int id_type, int64_t Bq, int64_t Bc, int dim,
+                            int64_t diag_offset, float* row_lse, double* loss_sum,
+                            const float* thr_score, const int32_t* thr_pos,
+                            const float* cand_logq, void* ws, int64_t ws_bytes, brStream stream);
+/* brInBatchSoftmaxLseGradQ / ...Hard on the corrected scores (above 64 features: ...LseLogQ + ...GradLogQ(dQ)). */
+int brInBatchSoftmaxLseGradQLogQ(const float* Q, const float* C, const void* q_pos_ids,
+                                 const void* cand_ids, int id_type, int64_t Bq, int64_t Bc,
+                                 int dim, int64_t diag_offset, float* row_lse, double* loss_sum,
+                                 float* dQ, const float* thr_score, const int32_t* thr_pos,
+                                 const float* cand_logq, void* ws, int64_t ws_bytes,
+                                 brStream stream);
+/* brInBatchSoftmaxGrad / ...GradHard / ...GradHardSlice on the corrected scores: dQ and / or dC.  c0, Bc_total as in
+ * brInBatchSoftmaxGradHardSlice (C, cand_ids and cand_logq hold rows [c0, c0 + Bc) of the Bc_total candidates; a proper
+ * slice forms dC only); c0 = 0, Bc_total = Bc: the whole batch. */
+int brInBatchSoftmaxGradLogQ(const float* Q, const float* C, const void* q_pos_ids,
+                             const void* cand_ids, int id_type, int64_t Bq, int64_t Bc, int dim,
+                             int64_t diag_offset, const float* row_lse, float* dQ, float* dC,
+                             const float* thr_score, const int32_t* thr_pos,
+                             const float* cand_logq, int64_t c0, int64_t Bc_total, void* ws,
+                             int64_t ws_bytes, brStream stream);
+
 /* scores[q][c] = Q[q]·C[c] (n_q x n_c, row stride ld_scores): candidate scoring for top-k
  * (TwoTower BruteForce, twoTower.py:64-69,229-230; bpr_predict, src/models/bpr.py:122-133). */
 int brScoreMatrix(const float* Q, const float* C, int64_t n_q, int64_t n_c, int dim, float* scores,
