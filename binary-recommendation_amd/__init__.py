@@ -13,4 +13,13 @@ Hand-written HIP kernels live in csrc/ behind the C-ABI of include/binrec.h
 from . import _lib  # noqa: F401
 from ._lib import BinrecError  # noqa: F401
 
-__all__ = ["BinrecError"]
+__all__ = ["BinrecError", "ALSEngine", "ALSModel"]
+
+_LAZY = {"ALSEngine": "als", "ALSModel": "models"}     # resolved on first use: the engines import torch and bind the library
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        from importlib import import_module
+        return getattr(import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -19,6 +19,7 @@ import torch
 
 from . import data as _data
 from . import ops
+from .als import ALSEngine, csr_pair
 from .bpr import BPREngine
 from .neumf import NeuMFConfig, NeuMFEngine
 from .two_tower import StringLookup, TwoTowerEngine
@@ -664,6 +665,59 @@ class BPRModel(RModel):
                 e.n_seen = sum(s[3] for s in slices) * 1
             hist.add({"loss": e.pop_loss()})
         return hist
+
+
+class ALSModel(RModel):
+    """Implicit-feedback ALS (Hu, Koren, Volinsky 2008) behind the surface of BPRModel: the same data, split, evaluation and
+    recommendation calls on an ALSEngine (als.py).  The reference has no such model; it is the closed-form baseline the sampled
+    models are compared against.  Single device: the row-sharded ALS is not built."""
+
+    def __init__(self, device="cuda:0"):
+        super().__init__("ALSModel", device)
+
+    def compileModel(self, distributedConfig, numUser: int, numItem: int, numFactor: int, reg: float = 0.01, alpha: float = 40.0, seed: int = 0):
+        self._refuse_sharded(distributedConfig)
+        self.model = ALSEngine(numUser, numItem, numFactor, self.device, reg=reg, alpha=alpha, init_seed=seed)
+        return self.model, None
+
+    @staticmethod
+    def _refuse_sharded(distributedConfig):
+        import torch.distributed as dist
+        if distributedConfig is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("ALSModel: the row-sharded ALS (Gram all-reduce + exchange of the gathered rows) is not built; "
+                                      "train on one device (distributedConfig=None)")
+
+    readData = BPRModel.readData
+
+    def train(self, path, rowLimit, metricDict: dict = None, distributedConfig=None, reg: float = 0.01, alpha: float = 40.0, seed: int = 0):
+        """The train/test split of BPRModel.train, then `epochs` ALS epochs (user half-step, item half-step) on the training split's
+        pairs, duplicates merged.  -> {'result': 'completed', 'metrics': [last objective], 'history': History} with
+        history['objective'] = the objective after every epoch (ALSEngine.objective)."""
+        from sklearn.model_selection import train_test_split
+        self._refuse_sharded(distributedConfig)
+        numItem, numUser, df = self.readData(path, rowLimit)
+        self.trainDf, self.testDf = train_test_split(df, test_size=self.testSize, random_state=seed)
+        customerIds = self.trainDf.CUSTOMER_ID.unique().tolist()
+        self.productIds = self.trainDf.PRODUCT_ID.unique().tolist()
+        nu, ni = max(customerIds) + 1, max(self.productIds) + 1
+        self.compileModel(distributedConfig, nu, ni, self.numFactor, reg=reg, alpha=alpha, seed=seed)
+        e = self.model
+        user_csr, item_csr = csr_pair(self.trainDf.CUSTOMER_ID.to_numpy(), self.trainDf.PRODUCT_ID.to_numpy(), nu, ni, e.device)
+        hist = History()
+        for _ in range(self.epochs):
+            e.epoch(user_csr, item_csr)
+            e.check_ids()
+            hist.add({"objective": e.objective(user_csr)})
+        return {"result": "completed", "metrics": [hist.history["objective"][-1]], "history": hist}
+
+    # evaluation and recommendation: BPRModel's, which only need the engine's serving surface
+    _scores = BPRModel._scores
+    full_auc = BPRModel.full_auc
+    mean_average_precision_k = BPRModel.mean_average_precision_k
+    rank_metrics = BPRModel.rank_metrics
+    getPredictableUsers = BPRModel.getPredictableUsers
+    recommendForUsers = BPRModel.recommendForUsers
+    predictForUser = BPRModel.predictForUser
 
 
 def sampling_probability_rows(p, itemsId):

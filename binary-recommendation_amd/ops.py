@@ -1685,3 +1685,65 @@ def ncf_negatives(users, items, pos_off, pos_items, num_items: int, size: int, s
             return ou, oi
         n_cand = int(n_cand * 1.6) + n        # more rounds of column shuffles
     raise RuntimeError("ncf_negatives: not enough distinct negatives (is the interaction matrix nearly full?)")
+
+
+# ------------------------------------------------------------------------------ implicit-feedback ALS (csrc/als.hip)
+ALS_MAX_DIM = 128          # widest rows brGram / brAlsSolveRows take
+
+
+def _ld(t) -> int:
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def gram(Y, out=None):
+    """G = Y^T Y (dim x dim float32, both triangles, exactly symmetric) of the rows x dim table Y (any row stride >= dim) on the
+    fp32-input MFMA; the workgroups' partials are added in a fixed order in double: two calls give the same bits."""
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
+        raise ValueError("gram: Y must be a 2-D tensor")
+    rows, dim = Y.shape
+    if not 1 <= dim <= ALS_MAX_DIM:
+        raise ValueError(f"gram: dim = {dim}: 1 <= dim <= {ALS_MAX_DIM}")
+    _rows_f32(Y, "Y")
+    if out is None:
+        out = torch.empty(dim, dim, dtype=torch.float32, device=Y.device)
+    elif tuple(out.shape) != (dim, dim):
+        raise ValueError(f"gram: out must be ({dim}, {dim})")
+    lib = _lib.load()
+    ws_bytes = int(lib.brGramWorkspaceBytes(rows, dim))
+    if ws_bytes < 0:
+        raise ValueError(f"gram: bad sizes rows={rows} dim={dim}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Y.device)
+    check(lib.brGram(Y.data_ptr(), _ld(Y), rows, dim, _f32(out, "out").data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "brGram")
+    return out
+
+
+def als_solve_rows(Y, G, off, idx, reg, alpha, conf=None, out=None, err_flag=None):
+    """One ALS half-step: for every row u of the CSR (off int64 [n_rows + 1], idx int32 positions into Y ascending per row -
+    ops.truth_csr / als.csr_pair - conf float32 >= 0 per entry or None = 1), c_e = alpha * conf[e],
+        out[u] = (G + reg I + sum_e c_e y_e y_e^T)^-1 sum_e (1 + c_e) y_e
+    with G = ops.gram(Y); a row without entries gets exact zeros.  out: (n_rows, dim) float32, any row stride >= dim (columns past
+    dim are left alone).  An idx outside Y sets BR_ERRFLAG_RANGE in err_flag and counts as absent."""
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
+        raise ValueError("als_solve_rows: Y must be a 2-D tensor")
+    n_y, dim = Y.shape
+    if not 1 <= dim <= ALS_MAX_DIM:
+        raise ValueError(f"als_solve_rows: dim = {dim}: 1 <= dim <= {ALS_MAX_DIM}")
+    _rows_f32(Y, "Y")
+    if tuple(G.shape) != (dim, dim):
+        raise ValueError(f"als_solve_rows: G must be ({dim}, {dim})")
+    _f32(G, "G")
+    n_rows = off.shape[0] - 1
+    off, idx_ = _csr((off, idx), n_rows, "csr")
+    if conf is not None:
+        if conf.dtype != torch.float32 or not conf.is_cuda or not conf.is_contiguous() or conf.shape != idx.shape:
+            raise TypeError("als_solve_rows: conf must be a contiguous float32 device tensor, one value per idx entry")
+        if conf.numel() == 0:
+            conf = None
+    if out is None:
+        out = torch.empty(n_rows, dim, dtype=torch.float32, device=Y.device)
+    elif out.dim() != 2 or out.shape[0] != n_rows or out.shape[1] < dim:
+        raise ValueError(f"als_solve_rows: out must be ({n_rows}, >= {dim})")
+    _rows_f32(out, "out")
+    check(_lib.load().brAlsSolveRows(Y.data_ptr(), _ld(Y), n_y, dim, G.data_ptr(), off.data_ptr(), idx_.data_ptr(), _p(conf), float(alpha),
+                                     float(reg), n_rows, out.data_ptr(), _ld(out), _p(err_flag), _stream()), "brAlsSolveRows")
+    return out

@@ -1120,6 +1120,25 @@ int64_t brNeumfGroupSetSizeof(void);
  * steps is outside 2 .. BR_GROUP_MAX, the segment scratch is missing, or BR_GROUP_INDEX=0 (read on every call: A/B runs). */
 int brNeumfGroupIndexPlan(const brNeumfStep* s, int steps);
 
+/* Implicit-feedback ALS (Hu, Koren, Volinsky 2008; csrc/als.hip).  Single device.
+ * brGram: G = Y^T Y of the rows x dim table Y (row stride ld), dim x dim row-major, both triangles, exactly symmetric.  Workgroups
+ *   multiply contiguous slices of rows on the fp32-input MFMA into partials in ws (brGramWorkspaceBytes(rows, dim); -1 outside the
+ *   limits); a second launch adds the partials in index order in double and rounds once.  No atomics: two calls on one input give the
+ *   same bits.  rows == 0 gives G = 0.
+ * brAlsSolveRows: one half-step.  For every row u of the CSR (off int64 [n_rows + 1] non-decreasing, idx int32 positions into Y,
+ *   conf float32 >= 0 per entry or NULL = 1) with c_e = alpha * conf[e]:
+ *       A_u = G + reg I + sum_e c_e y_e y_e^T,   b_u = sum_e (1 + c_e) y_e,   X[u] = A_u^-1 b_u
+ *   by an in-LDS Cholesky factorisation, one workgroup per row.  X[u] is a function of (G, reg, alpha, the row's entries in their
+ *   order and the rows of Y they name) alone; columns of X past dim are not written.  A row without entries gets exact zeros.  An
+ *   idx outside [0, n_y) is never dereferenced: it sets BR_ERRFLAG_RANGE in *err_flag (may be NULL) and counts as absent.  A pivot
+ *   that is not a positive finite number makes the row NaN.
+ * Limits: 1 <= dim <= 128 (any value), ld >= dim, n_y < 2^31, n_rows < 2^31, reg > 0 and alpha >= 0 finite; BR_ERR_ARG /
+ * BR_ERR_WORKSPACE before any launch; n_rows == 0 is BR_OK; no allocation and no sync inside. */
+int64_t brGramWorkspaceBytes(int64_t rows, int dim);
+int brGram(const float* Y, int64_t ld, int64_t rows, int dim, float* G, void* ws, int64_t ws_bytes, brStream stream);
+int brAlsSolveRows(const float* Y, int64_t ld_y, int64_t n_y, int dim, const float* G, const int64_t* off, const int32_t* idx,
+                   const float* conf, float alpha, float reg, int64_t n_rows, float* X, int64_t ld_x, int* err_flag, brStream stream);
+
 /* Optional launch probe for measurement (bench.py roofline leg): HIP events on the launch stream
  * around every inner launch of brNeumfStepRun, tagged BR_TAG_*.  brProbeEnable(capacity) creates
  * the events (capacity 0 disables and frees them); after synchronising the stream the host reads
