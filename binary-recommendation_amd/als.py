@@ -4,7 +4,9 @@ optimiser state: every unobserved pair is a weak negative in closed form, throug
 
 One half-step solves every row of one side against the other side's table Y (csrc/als.hip):
     G = Y^T Y (ops.gram),   x_u = (G + reg I + sum_e c_e y_e y_e^T)^-1 sum_e (1 + c_e) y_e (ops.als_solve_rows),  c_e = alpha * conf_e
-and an epoch is the user half-step followed by the item half-step on the transposed CSR.  The result is a (user table, item table)
+and an epoch is the user half-step followed by the item half-step on the transposed CSR.  solver="cg" replaces the exact solve by a few
+conjugate-gradient steps from the row's current vector (ops.als_solve_rows_cg, csrc/als_wide.hip): no dim x dim matrix
+per row, rows up to 512 features.  The result is a (user table, item table)
 pair of float rows: the fused catalogue kernels of the dot-product models (top-k, AUC, exact ranks) serve it unchanged.  Single device.
 """
 from __future__ import annotations
@@ -60,15 +62,25 @@ def _csr3(csr):
 
 class ALSEngine:
     """Tables `user` (num_users x num_factor) and `item` (num_items x num_factor), float32, N(0, 0.01) from init_seed; reg = the
-    ridge term lambda > 0, alpha = the confidence slope (an observed pair weighs 1 + alpha * conf).  Rows wider than 128 features
-    cannot be trained (ops.ALS_MAX_DIM)."""
+    ridge term lambda > 0, alpha = the confidence slope (an observed pair weighs 1 + alpha * conf).
+    solver = "cholesky" (the default): every row is solved exactly, num_factor <= ops.ALS_MAX_DIM = 128.
+    solver = "cg": cg_steps (1 .. 64) conjugate-gradient steps per row and half-step, warm-started from the row's vector, num_factor <=
+    ops.ALS_CG_MAX_DIM = 512.  Above 128 features only the fused serving forms exist (recommend, full_auc, catalog_ranks,
+    rank_metrics): predict_scores stops at 128, as for BPR."""
 
-    def __init__(self, num_users: int, num_items: int, num_factor: int, device, reg: float = 0.01, alpha: float = 40.0, init_seed: int = 0):
-        if not 1 <= int(num_factor) <= ops.ALS_MAX_DIM:
-            raise ValueError(f"num_factor = {num_factor}: 1 <= num_factor <= {ops.ALS_MAX_DIM}")
+    def __init__(self, num_users: int, num_items: int, num_factor: int, device, reg: float = 0.01, alpha: float = 40.0, init_seed: int = 0,
+                 solver: str = "cholesky", cg_steps: int = 3):
+        if solver not in ("cholesky", "cg"):
+            raise ValueError(f"solver must be 'cholesky' or 'cg', got {solver!r}")
+        max_dim = ops.ALS_MAX_DIM if solver == "cholesky" else ops.ALS_CG_MAX_DIM
+        if not 1 <= int(num_factor) <= max_dim:
+            raise ValueError(f"num_factor = {num_factor}: 1 <= num_factor <= {max_dim} with solver={solver!r}")
+        if not 1 <= int(cg_steps) <= 64:
+            raise ValueError(f"cg_steps = {cg_steps}: 1 <= cg_steps <= 64")
         if not (reg > 0 and alpha >= 0):
             raise ValueError("reg must be > 0 and alpha >= 0")
         self.device, self.dim, self.reg, self.alpha = torch.device(device), int(num_factor), float(reg), float(alpha)
+        self.solver, self.cg_steps = solver, int(cg_steps)
         self.id_dtype = torch.int32
         g = torch.Generator(device="cpu").manual_seed(init_seed)
         self.user = (torch.randn(num_users, self.dim, generator=g) * 0.01).to(self.device)
@@ -78,7 +90,8 @@ class ALSEngine:
 
     # ---- training ----
     def half_step(self, side: str, csr):
-        """Solve every row of `side` ("user" | "item") against the other table, in place: gram, then the fused per-row solve.  csr:
+        """Solve every row of `side` ("user" | "item") against the other table, in place: gram, then the fused per-row solve (Cholesky,
+        or cg_steps conjugate-gradient steps from the rows as they stand).  csr:
         (off, idx[, conf]) over the rows of `side` with positions into the other table (csr_pair).  No host sync."""
         if side not in ("user", "item"):
             raise ValueError(f"side must be 'user' or 'item', got {side!r}")
@@ -87,7 +100,10 @@ class ALSEngine:
         if off.shape[0] != X.shape[0] + 1:
             raise ValueError(f"half_step({side!r}): the CSR has {off.shape[0] - 1} rows, the table {X.shape[0]}")
         G = ops.gram(Y, out=self._gram)
-        ops.als_solve_rows(Y, G, off, idx, self.reg, self.alpha, conf=conf, out=X, err_flag=self.err)
+        if self.solver == "cg":
+            ops.als_solve_rows_cg(Y, G, off, idx, self.reg, self.alpha, X, steps=self.cg_steps, conf=conf, err_flag=self.err)
+        else:
+            ops.als_solve_rows(Y, G, off, idx, self.reg, self.alpha, conf=conf, out=X, err_flag=self.err)
 
     def epoch(self, user_csr, item_csr):
         self.half_step("user", user_csr)
@@ -110,7 +126,7 @@ class ALSEngine:
 
     # ---- serving: the surface of BPREngine, on the same fused catalogue kernels ----
     def predict_scores(self, user_ids, item_ids=None):
-        """user vectors x item matrix^T"""
+        """user vectors x item matrix^T (rows up to 128 features, ops.score_matrix)"""
         u = ops.gather_rows([self.user], [user_ids])[0]
         it = self.item if item_ids is None else ops.gather_rows([self.item], [item_ids])[0]
         return ops.score_matrix(u, it)

@@ -670,14 +670,17 @@ class BPRModel(RModel):
 class ALSModel(RModel):
     """Implicit-feedback ALS (Hu, Koren, Volinsky 2008) behind the surface of BPRModel: the same data, split, evaluation and
     recommendation calls on an ALSEngine (als.py).  The reference has no such model; it is the closed-form baseline the sampled
-    models are compared against.  Single device: the row-sharded ALS is not built."""
+    models are compared against.  Single device: the row-sharded ALS is not built.  solver="cholesky" (numFactor <= 128) solves every
+    row exactly; solver="cg" takes cgSteps conjugate-gradient steps per row from its current vector and numFactor up to 512.  Above
+    128 features only the fused serving forms exist: _scores / method="matrix" stop at 128, as for BPR."""
 
     def __init__(self, device="cuda:0"):
         super().__init__("ALSModel", device)
 
-    def compileModel(self, distributedConfig, numUser: int, numItem: int, numFactor: int, reg: float = 0.01, alpha: float = 40.0, seed: int = 0):
+    def compileModel(self, distributedConfig, numUser: int, numItem: int, numFactor: int, reg: float = 0.01, alpha: float = 40.0, seed: int = 0,
+                     solver: str = "cholesky", cgSteps: int = 3):
         self._refuse_sharded(distributedConfig)
-        self.model = ALSEngine(numUser, numItem, numFactor, self.device, reg=reg, alpha=alpha, init_seed=seed)
+        self.model = ALSEngine(numUser, numItem, numFactor, self.device, reg=reg, alpha=alpha, init_seed=seed, solver=solver, cg_steps=cgSteps)
         return self.model, None
 
     @staticmethod
@@ -689,10 +692,11 @@ class ALSModel(RModel):
 
     readData = BPRModel.readData
 
-    def train(self, path, rowLimit, metricDict: dict = None, distributedConfig=None, reg: float = 0.01, alpha: float = 40.0, seed: int = 0):
+    def train(self, path, rowLimit, metricDict: dict = None, distributedConfig=None, reg: float = 0.01, alpha: float = 40.0, seed: int = 0,
+              solver: str = "cholesky", cgSteps: int = 3):
         """The train/test split of BPRModel.train, then `epochs` ALS epochs (user half-step, item half-step) on the training split's
         pairs, duplicates merged.  -> {'result': 'completed', 'metrics': [last objective], 'history': History} with
-        history['objective'] = the objective after every epoch (ALSEngine.objective)."""
+        history['objective'] = the objective after every epoch (ALSEngine.objective).  solver / cgSteps: compileModel."""
         from sklearn.model_selection import train_test_split
         self._refuse_sharded(distributedConfig)
         numItem, numUser, df = self.readData(path, rowLimit)
@@ -700,7 +704,7 @@ class ALSModel(RModel):
         customerIds = self.trainDf.CUSTOMER_ID.unique().tolist()
         self.productIds = self.trainDf.PRODUCT_ID.unique().tolist()
         nu, ni = max(customerIds) + 1, max(self.productIds) + 1
-        self.compileModel(distributedConfig, nu, ni, self.numFactor, reg=reg, alpha=alpha, seed=seed)
+        self.compileModel(distributedConfig, nu, ni, self.numFactor, reg=reg, alpha=alpha, seed=seed, solver=solver, cgSteps=cgSteps)
         e = self.model
         user_csr, item_csr = csr_pair(self.trainDf.CUSTOMER_ID.to_numpy(), self.trainDf.PRODUCT_ID.to_numpy(), nu, ni, e.device)
         hist = History()

@@ -1689,6 +1689,7 @@ def ncf_negatives(users, items, pos_off, pos_items, num_items: int, size: int, s
 
 # ------------------------------------------------------------------------------ implicit-feedback ALS (csrc/als.hip)
 ALS_MAX_DIM = 128          # widest rows brGram / brAlsSolveRows take
+ALS_CG_MAX_DIM = 512       # widest rows brGramWide / brAlsSolveRowsCg take (csrc/als_wide.hip)
 
 
 def _ld(t) -> int:
@@ -1697,23 +1698,25 @@ def _ld(t) -> int:
 
 def gram(Y, out=None):
     """G = Y^T Y (dim x dim float32, both triangles, exactly symmetric) of the rows x dim table Y (any row stride >= dim) on the
-    fp32-input MFMA; the workgroups' partials are added in a fixed order in double: two calls give the same bits."""
+    fp32-input MFMA; the workgroups' partials are added in a fixed order in double: two calls give the same bits.  dim <= 128 is
+    brGram; 129 .. 512 is brGramWide, the same contract in blocks of 128 columns."""
     if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
         raise ValueError("gram: Y must be a 2-D tensor")
     rows, dim = Y.shape
-    if not 1 <= dim <= ALS_MAX_DIM:
-        raise ValueError(f"gram: dim = {dim}: 1 <= dim <= {ALS_MAX_DIM}")
+    if not 1 <= dim <= ALS_CG_MAX_DIM:
+        raise ValueError(f"gram: dim = {dim}: 1 <= dim <= {ALS_CG_MAX_DIM}")
     _rows_f32(Y, "Y")
     if out is None:
         out = torch.empty(dim, dim, dtype=torch.float32, device=Y.device)
     elif tuple(out.shape) != (dim, dim):
         raise ValueError(f"gram: out must be ({dim}, {dim})")
     lib = _lib.load()
-    ws_bytes = int(lib.brGramWorkspaceBytes(rows, dim))
+    size, run, name = (lib.brGramWorkspaceBytes, lib.brGram, "brGram") if dim <= ALS_MAX_DIM else (lib.brGramWideWorkspaceBytes, lib.brGramWide, "brGramWide")
+    ws_bytes = int(size(rows, dim))
     if ws_bytes < 0:
         raise ValueError(f"gram: bad sizes rows={rows} dim={dim}")
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Y.device)
-    check(lib.brGram(Y.data_ptr(), _ld(Y), rows, dim, _f32(out, "out").data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "brGram")
+    check(run(Y.data_ptr(), _ld(Y), rows, dim, _f32(out, "out").data_ptr(), ws.data_ptr(), ws_bytes, _stream()), name)
     return out
 
 
@@ -1747,3 +1750,35 @@ def als_solve_rows(Y, G, off, idx, reg, alpha, conf=None, out=None, err_flag=Non
     check(_lib.load().brAlsSolveRows(Y.data_ptr(), _ld(Y), n_y, dim, G.data_ptr(), off.data_ptr(), idx_.data_ptr(), _p(conf), float(alpha),
                                      float(reg), n_rows, out.data_ptr(), _ld(out), _p(err_flag), _stream()), "brAlsSolveRows")
     return out
+
+
+def als_solve_rows_cg(Y, G, off, idx, reg, alpha, x, steps=3, conf=None, err_flag=None):
+    """One ALS half-step by `steps` (1 .. 64) conjugate-gradient steps per row, in place on x (n_rows, >= dim) float32, any row stride
+    >= dim (columns past dim are left alone): every row starts from its current vector (Takacs, Pilaszy, Tikk 2011; brAlsSolveRowsCg,
+    csrc/als_wide.hip).  The operator A_u = G + reg I + sum_e c_e y_e y_e^T of als_solve_rows is applied, never formed, so rows up to
+    ALS_CG_MAX_DIM = 512 features are taken.  CSR, conf, G = ops.gram(Y) and err_flag as for als_solve_rows; a row without entries
+    gets exact zeros.  -> x."""
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
+        raise ValueError("als_solve_rows_cg: Y must be a 2-D tensor")
+    n_y, dim = Y.shape
+    if not 1 <= dim <= ALS_CG_MAX_DIM:
+        raise ValueError(f"als_solve_rows_cg: dim = {dim}: 1 <= dim <= {ALS_CG_MAX_DIM}")
+    if not 1 <= int(steps) <= 64:
+        raise ValueError(f"als_solve_rows_cg: steps = {steps}: 1 <= steps <= 64")
+    _rows_f32(Y, "Y")
+    if tuple(G.shape) != (dim, dim):
+        raise ValueError(f"als_solve_rows_cg: G must be ({dim}, {dim})")
+    _f32(G, "G")
+    n_rows = off.shape[0] - 1
+    off, idx_ = _csr((off, idx), n_rows, "csr")
+    if conf is not None:
+        if conf.dtype != torch.float32 or not conf.is_cuda or not conf.is_contiguous() or conf.shape != idx.shape:
+            raise TypeError("als_solve_rows_cg: conf must be a contiguous float32 device tensor, one value per idx entry")
+        if conf.numel() == 0:
+            conf = None
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != n_rows or x.shape[1] < dim:
+        raise ValueError(f"als_solve_rows_cg: x must be ({n_rows}, >= {dim})")
+    _rows_f32(x, "x")
+    check(_lib.load().brAlsSolveRowsCg(Y.data_ptr(), _ld(Y), n_y, dim, G.data_ptr(), off.data_ptr(), idx_.data_ptr(), _p(conf), float(alpha),
+                                       float(reg), n_rows, x.data_ptr(), _ld(x), int(steps), _p(err_flag), _stream()), "brAlsSolveRowsCg")
+    return x

@@ -1139,6 +1139,32 @@ int brGram(const float* Y, int64_t ld, int64_t rows, int dim, float* G, void* ws
 int brAlsSolveRows(const float* Y, int64_t ld_y, int64_t n_y, int dim, const float* G, const int64_t* off, const int32_t* idx,
                    const float* conf, float alpha, float reg, int64_t n_rows, float* X, int64_t ld_x, int* err_flag, brStream stream);
 
+/* ALS for rows up to 512 features (csrc/als_wide.hip).  Single device.
+ * brGramWide: brGram's contract for 1 <= dim <= 512: both triangles, G bit-equal to its transpose, the bits a function of (Y, rows, dim)
+ *   alone (two calls, and the 16-byte and the scalar load paths, give the same bits), any ld >= dim, rows == 0 gives G = 0.  G is formed
+ *   in blocks of 128 columns: a workgroup multiplies a slice of rows of one pair of column blocks on the fp32-input MFMA into a partial
+ *   in ws (brGramWideWorkspaceBytes(rows, dim); -1 outside the limits); a second launch adds the slices' partials in index order in
+ *   double, rounds once and writes G[I][J] and G[J][I] from the one value.  No atomics.  (Not the bits of brGram at dim <= 128.)
+ * brAlsSolveRowsCg: one half-step by `steps` conjugate-gradient steps per row from the row's current vector (Takacs, Pilaszy, Tikk
+ *   2011), X in and out.  With A_u and b_u as for brAlsSolveRows, applied as A p = G p + reg p + sum_e c_e y_e (y_e . p), never formed:
+ *       x = X[u]; r = b - A x; p = r; rs = r.r
+ *       `steps` times: stop unless rs >= 1e-20; q = A p; d = p.q; stop unless d is positive and finite;
+ *                      a = rs / d; x += a p; r -= a q; rn = r.r; p = r + (rn / rs) p; rs = rn
+ *       X[u] = x
+ *   "stop" ends that row alone.  G must be symmetric (brGram / brGramWide: it is read through its transpose).  G p runs on the
+ *   fp32 MFMA; the sparse term, the dot products and x, r, p are carried in double and x is rounded to float once, at the end.  A
+ *   workgroup takes 32 consecutive rows (16 above 256 features) and reads G once per application of A; X[u] is a function of (G, reg, alpha, the row's entries in their order,
+ *   the rows of Y they name, X[u] on entry, steps) alone - not of the rows beside it, n_rows or the grid; two calls give the same
+ *   bits; no atomics on floats.  Columns of X past dim are not written.  A row without entries gets exact zeros.  An idx outside
+ *   [0, n_y) is never dereferenced: it sets BR_ERRFLAG_RANGE in *err_flag (may be NULL) and counts as absent.
+ * Limits: 1 <= dim <= 512 (any value), ld >= dim, 1 <= steps <= 64, n_y < 2^31, n_rows < 2^31, reg > 0 and alpha >= 0 finite;
+ * BR_ERR_ARG / BR_ERR_WORKSPACE before any launch; n_rows == 0 is BR_OK; no allocation and no sync inside. */
+int64_t brGramWideWorkspaceBytes(int64_t rows, int dim);
+int brGramWide(const float* Y, int64_t ld, int64_t rows, int dim, float* G, void* ws, int64_t ws_bytes, brStream stream);
+int brAlsSolveRowsCg(const float* Y, int64_t ld_y, int64_t n_y, int dim, const float* G, const int64_t* off, const int32_t* idx,
+                     const float* conf, float alpha, float reg, int64_t n_rows, float* X, int64_t ld_x, int steps, int* err_flag,
+                     brStream stream);
+
 /* Optional launch probe for measurement (bench.py roofline leg): HIP events on the launch stream
  * around every inner launch of brNeumfStepRun, tagged BR_TAG_*.  brProbeEnable(capacity) creates
  * the events (capacity 0 disables and frees them); after synchronising the stream the host reads
