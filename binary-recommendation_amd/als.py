@@ -6,7 +6,9 @@ One half-step solves every row of one side against the other side's table Y (csr
     G = Y^T Y (ops.gram),   x_u = (G + reg I + sum_e c_e y_e y_e^T)^-1 sum_e (1 + c_e) y_e (ops.als_solve_rows),  c_e = alpha * conf_e
 and an epoch is the user half-step followed by the item half-step on the transposed CSR.  solver="cg" replaces the exact solve by a few
 conjugate-gradient steps from the row's current vector (ops.als_solve_rows_cg, csrc/als_wide.hip): no dim x dim matrix
-per row, rows up to 512 features.  The result is a (user table, item table)
+per row, rows up to 512 features.  heavy_rows= takes the few rows with very many entries out of that kernel (one wave per row): their
+normal matrices are formed once by many workgroups and the same recurrence runs on them (split_heavy, ops.als_normal_rows,
+ops.als_solve_rows_dense_cg, csrc/als_heavy.hip).  The result is a (user table, item table)
 pair of float rows: the fused catalogue kernels of the dot-product models (top-k, AUC, exact ranks) serve it unchanged.  Single device.
 """
 from __future__ import annotations
@@ -60,18 +62,101 @@ def _csr3(csr):
     return (csr[0], csr[1], csr[2] if len(csr) > 2 else None)
 
 
+HEAVY_WS_BYTES = 256 << 20      # H, b and the partial workspace of one batch of heavy rows, at most (a row above it stands alone)
+
+
+def heavy_row_bytes(n_slices: int, dim: int) -> int:
+    """H (float32 dim x dim), b (float64 dim) and the partials of a row of n_slices slices: ops.als_normal_rows allocates this much"""
+    nb = (dim + 127) // 128
+    return dim * dim * 4 + dim * 8 + n_slices * (nb * (nb + 1) // 2 * 65536 + dim * 8)
+
+
+class HeavyBatch:
+    """consecutive heavy rows [lo, hi) of a HeavyCSR: their ids (int32 and int64), slice prefix from 0 and slice count"""
+
+    def __init__(self, lo, hi, rows, slice_off, n_slices):
+        self.lo, self.hi, self.rows, self.rows_long, self.slice_off, self.n_slices = lo, hi, rows, rows.long(), slice_off, n_slices
+
+
+class HeavyCSR:
+    """A CSR with its heavy rows (more than `threshold` entries) set apart (split_heavy):
+    csr        the CSR as given, (off, idx, conf or None)
+    rows       int32, ascending: the heavy rows
+    light      (off, idx, conf) over ALL rows with the heavy rows emptied, idx / conf compacted: the kernels of the plain path run it
+               unchanged and give the heavy rows exact zeros (the CSR itself where no row is heavy)
+    slice      entries per slice, slice_off: int64 [len(rows) + 1] prefix of the slices of the heavy rows
+    batches    [HeavyBatch]: consecutive heavy rows whose H, b and partial workspace stay under ws_bytes at `dim` features (plan)"""
+
+    def __init__(self, csr, threshold, rows, light, slice, slice_off, row_slices):
+        self.csr, self.threshold, self.rows, self.light, self.slice, self.slice_off = csr, threshold, rows, light, slice, slice_off
+        self._row_slices = row_slices            # host: slices of every heavy row
+        self.dim = self.ws_bytes = None
+        self.batches = []
+
+    def plan(self, dim: int, ws_bytes: int = HEAVY_WS_BYTES):
+        """the batches for rows of `dim` features under `ws_bytes` (host arithmetic; no sync)"""
+        bounds, lo, used = [], 0, 0
+        for h, ns in enumerate(self._row_slices):
+            need = heavy_row_bytes(ns, dim)
+            if h > lo and used + need > ws_bytes:
+                bounds.append((lo, h))
+                lo, used = h, 0
+            used += need
+        if len(self._row_slices) > lo:
+            bounds.append((lo, len(self._row_slices)))
+        self.batches = [HeavyBatch(lo, hi, self.rows[lo:hi], (self.slice_off[lo:hi + 1] - self.slice_off[lo]).contiguous(),
+                                   sum(self._row_slices[lo:hi])) for lo, hi in bounds]
+        self.dim, self.ws_bytes = int(dim), int(ws_bytes)
+        return self
+
+
+def split_heavy(csr, threshold: int, dim: int = None, heavy_ws_bytes: int = HEAVY_WS_BYTES, slice: int = None) -> HeavyCSR:
+    """Set the rows of `csr` with more than `threshold` entries apart -> HeavyCSR, made once per CSR (host syncs).  dim: the row width the
+    batches are planned for (None: ops.ALS_CG_MAX_DIM, the widest; HeavyCSR.plan re-plans).  torch ops on the CSR's device ("cpu" runs
+    the same code on the host)."""
+    slice = ops.ALS_HEAVY_SLICE if slice is None else int(slice)
+    if int(threshold) < 1:
+        raise ValueError(f"split_heavy: threshold = {threshold} must be >= 1")
+    if slice < 64 or slice % 64:
+        raise ValueError(f"split_heavy: slice = {slice} must be a multiple of 64, at least 64")
+    off, idx, conf = _csr3(csr)
+    lens = off[1:] - off[:-1]
+    heavy = lens > int(threshold)
+    rows = torch.nonzero(heavy).view(-1).to(torch.int32)
+    if rows.numel() == 0:
+        light = (off, idx, conf)
+    else:
+        keep = ~torch.repeat_interleave(heavy, lens)
+        light_off = torch.zeros_like(off)
+        light_off[1:] = torch.cumsum(torch.where(heavy, torch.zeros_like(lens), lens), 0)
+        light = (light_off, idx[keep].contiguous(), None if conf is None else conf[keep].contiguous())
+    slice_off = ops.als_slice_prefix(off, rows, slice)
+    row_slices = (slice_off[1:] - slice_off[:-1]).tolist()
+    h = HeavyCSR((off, idx, conf), int(threshold), rows, light, slice, slice_off, row_slices)
+    return h.plan(ops.ALS_CG_MAX_DIM if dim is None else int(dim), heavy_ws_bytes)
+
+
 class ALSEngine:
     """Tables `user` (num_users x num_factor) and `item` (num_items x num_factor), float32, N(0, 0.01) from init_seed; reg = the
     ridge term lambda > 0, alpha = the confidence slope (an observed pair weighs 1 + alpha * conf).
     solver = "cholesky" (the default): every row is solved exactly, num_factor <= ops.ALS_MAX_DIM = 128.
     solver = "cg": cg_steps (1 .. 64) conjugate-gradient steps per row and half-step, warm-started from the row's vector, num_factor <=
     ops.ALS_CG_MAX_DIM = 512.  Above 128 features only the fused serving forms exist (recommend, full_auc, catalog_ranks,
-    rank_metrics): predict_scores stops at 128, as for BPR."""
+    rank_metrics): predict_scores stops at 128, as for BPR.
+    heavy_rows = None (the default) | int >= 1, solver="cg" only: prepare(csr) sets the rows with more than heavy_rows entries apart
+    and a half-step takes them through their formed normal matrices, in batches of at most heavy_ws_bytes of device memory
+    (ops.ALS_HEAVY_ROWS is the measured recommendation)."""
 
     def __init__(self, num_users: int, num_items: int, num_factor: int, device, reg: float = 0.01, alpha: float = 40.0, init_seed: int = 0,
-                 solver: str = "cholesky", cg_steps: int = 3):
+                 solver: str = "cholesky", cg_steps: int = 3, heavy_rows=None, heavy_ws_bytes: int = HEAVY_WS_BYTES):
         if solver not in ("cholesky", "cg"):
             raise ValueError(f"solver must be 'cholesky' or 'cg', got {solver!r}")
+        if heavy_rows is not None:
+            if isinstance(heavy_rows, bool) or not isinstance(heavy_rows, int) or heavy_rows < 1:
+                raise ValueError(f"heavy_rows = {heavy_rows!r}: None or an int >= 1")
+            if solver != "cg":
+                raise ValueError("heavy_rows needs solver='cg'")
+        self.heavy_rows, self.heavy_ws_bytes = heavy_rows, int(heavy_ws_bytes)
         max_dim = ops.ALS_MAX_DIM if solver == "cholesky" else ops.ALS_CG_MAX_DIM
         if not 1 <= int(num_factor) <= max_dim:
             raise ValueError(f"num_factor = {num_factor}: 1 <= num_factor <= {max_dim} with solver={solver!r}")
@@ -89,19 +174,43 @@ class ALSEngine:
         self.err = ops.new_err_flag(self.device)
 
     # ---- training ----
+    def prepare(self, csr):
+        """What half_step / epoch should be given for `csr`: with heavy_rows set, the HeavyCSR of it (split_heavy, once per CSR; host
+        syncs); else csr itself."""
+        if self.heavy_rows is None:
+            return csr
+        return split_heavy(csr, self.heavy_rows, dim=self.dim, heavy_ws_bytes=self.heavy_ws_bytes)
+
     def half_step(self, side: str, csr):
         """Solve every row of `side` ("user" | "item") against the other table, in place: gram, then the fused per-row solve (Cholesky,
         or cg_steps conjugate-gradient steps from the rows as they stand).  csr:
-        (off, idx[, conf]) over the rows of `side` with positions into the other table (csr_pair).  No host sync."""
+        (off, idx[, conf]) over the rows of `side` with positions into the other table (csr_pair), or the HeavyCSR of one (prepare;
+        solver="cg"): its light rows take the same kernel, its heavy rows ops.als_normal_rows + ops.als_solve_rows_dense_cg.  No host
+        sync."""
         if side not in ("user", "item"):
             raise ValueError(f"side must be 'user' or 'item', got {side!r}")
         X, Y = (self.user, self.item) if side == "user" else (self.item, self.user)
+        heavy = csr if isinstance(csr, HeavyCSR) else None
+        if heavy is not None:
+            if self.solver != "cg":
+                raise ValueError("half_step: a HeavyCSR needs solver='cg'")
+            if heavy.dim != self.dim or heavy.ws_bytes != self.heavy_ws_bytes:
+                heavy.plan(self.dim, self.heavy_ws_bytes)
+            csr = heavy.light
         off, idx, conf = _csr3(csr)
         if off.shape[0] != X.shape[0] + 1:
             raise ValueError(f"half_step({side!r}): the CSR has {off.shape[0] - 1} rows, the table {X.shape[0]}")
+        if heavy is not None and heavy.batches:
+            x0 = X.index_select(0, heavy.rows.long())          # before the light pass zeroes these rows
         G = ops.gram(Y, out=self._gram)
         if self.solver == "cg":
             ops.als_solve_rows_cg(Y, G, off, idx, self.reg, self.alpha, X, steps=self.cg_steps, conf=conf, err_flag=self.err)
+            if heavy is not None:
+                f_off, f_idx, f_conf = heavy.csr
+                for bt in heavy.batches:
+                    H, b = ops.als_normal_rows(Y, f_off, f_idx, self.alpha, bt.rows, conf=f_conf, slice=heavy.slice, err_flag=self.err,
+                                               plan=(bt.slice_off, bt.n_slices))
+                    X.index_copy_(0, bt.rows_long, ops.als_solve_rows_dense_cg(G, H, b, self.reg, x0[bt.lo:bt.hi], steps=self.cg_steps))
         else:
             ops.als_solve_rows(Y, G, off, idx, self.reg, self.alpha, conf=conf, out=X, err_flag=self.err)
 

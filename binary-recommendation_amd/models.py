@@ -678,9 +678,10 @@ class ALSModel(RModel):
         super().__init__("ALSModel", device)
 
     def compileModel(self, distributedConfig, numUser: int, numItem: int, numFactor: int, reg: float = 0.01, alpha: float = 40.0, seed: int = 0,
-                     solver: str = "cholesky", cgSteps: int = 3):
+                     solver: str = "cholesky", cgSteps: int = 3, heavyRows=None):
         self._refuse_sharded(distributedConfig)
-        self.model = ALSEngine(numUser, numItem, numFactor, self.device, reg=reg, alpha=alpha, init_seed=seed, solver=solver, cg_steps=cgSteps)
+        self.model = ALSEngine(numUser, numItem, numFactor, self.device, reg=reg, alpha=alpha, init_seed=seed, solver=solver, cg_steps=cgSteps,
+                               heavy_rows=heavyRows)
         return self.model, None
 
     @staticmethod
@@ -693,10 +694,11 @@ class ALSModel(RModel):
     readData = BPRModel.readData
 
     def train(self, path, rowLimit, metricDict: dict = None, distributedConfig=None, reg: float = 0.01, alpha: float = 40.0, seed: int = 0,
-              solver: str = "cholesky", cgSteps: int = 3):
+              solver: str = "cholesky", cgSteps: int = 3, heavyRows=None):
         """The train/test split of BPRModel.train, then `epochs` ALS epochs (user half-step, item half-step) on the training split's
         pairs, duplicates merged.  -> {'result': 'completed', 'metrics': [last objective], 'history': History} with
-        history['objective'] = the objective after every epoch (ALSEngine.objective).  solver / cgSteps: compileModel."""
+        history['objective'] = the objective after every epoch (ALSEngine.objective).  solver / cgSteps: compileModel; heavyRows
+        (solver="cg" only): rows with more entries than this go through the formed normal matrix (ALSEngine(heavy_rows=))."""
         from sklearn.model_selection import train_test_split
         self._refuse_sharded(distributedConfig)
         numItem, numUser, df = self.readData(path, rowLimit)
@@ -704,12 +706,14 @@ class ALSModel(RModel):
         customerIds = self.trainDf.CUSTOMER_ID.unique().tolist()
         self.productIds = self.trainDf.PRODUCT_ID.unique().tolist()
         nu, ni = max(customerIds) + 1, max(self.productIds) + 1
-        self.compileModel(distributedConfig, nu, ni, self.numFactor, reg=reg, alpha=alpha, seed=seed, solver=solver, cgSteps=cgSteps)
+        self.compileModel(distributedConfig, nu, ni, self.numFactor, reg=reg, alpha=alpha, seed=seed, solver=solver, cgSteps=cgSteps,
+                          heavyRows=heavyRows)
         e = self.model
         user_csr, item_csr = csr_pair(self.trainDf.CUSTOMER_ID.to_numpy(), self.trainDf.PRODUCT_ID.to_numpy(), nu, ni, e.device)
+        user_rows, item_rows = e.prepare(user_csr), e.prepare(item_csr)       # the CSRs themselves unless heavyRows is set
         hist = History()
         for _ in range(self.epochs):
-            e.epoch(user_csr, item_csr)
+            e.epoch(user_rows, item_rows)
             e.check_ids()
             hist.add({"objective": e.objective(user_csr)})
         return {"result": "completed", "metrics": [hist.history["objective"][-1]], "history": hist}

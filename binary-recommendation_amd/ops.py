@@ -1782,3 +1782,92 @@ def als_solve_rows_cg(Y, G, off, idx, reg, alpha, x, steps=3, conf=None, err_fla
     check(_lib.load().brAlsSolveRowsCg(Y.data_ptr(), _ld(Y), n_y, dim, G.data_ptr(), off.data_ptr(), idx_.data_ptr(), _p(conf), float(alpha),
                                        float(reg), n_rows, x.data_ptr(), _ld(x), int(steps), _p(err_flag), _stream()), "brAlsSolveRowsCg")
     return x
+
+
+# ------------------------------------------------------------------------------ ALS, the heavy rows (csrc/als_heavy.hip)
+ALS_HEAVY_SLICE = 4096     # entries of a slice of brAlsNormalRows: one workgroup per slice and pair of 128-column blocks
+ALS_HEAVY_ROWS = 256       # the recommended ALSEngine(heavy_rows=): the best of 256 .. 65 536 measured - a recommendation, not a default
+
+
+def als_slice_prefix(off, rows, slice: int = ALS_HEAVY_SLICE):
+    """-> int64 [len(rows) + 1]: the slices of `slice` entries of every listed row, as a prefix sum (torch ops on off's device)"""
+    r = rows.long()
+    n = (off[r + 1] - off[r] + (int(slice) - 1)) // int(slice)
+    out = torch.zeros(r.shape[0] + 1, dtype=torch.int64, device=off.device)
+    out[1:] = torch.cumsum(n, 0)
+    return out
+
+
+def als_normal_rows(Y, off, idx, alpha, rows, conf=None, slice=ALS_HEAVY_SLICE, err_flag=None, plan=None):
+    """The normal matrix of the listed rows of the CSR, formed once by many workgroups (brAlsNormalRows): with c_e = alpha * conf[e]
+        H[h] = sum_e c_e y_e y_e^T (float32 (n, dim, dim), bit-equal to its transpose),   b[h] = sum_e (1 + c_e) y_e (float64 (n, dim))
+    over the entries of row rows[h].  rows: int32 device tensor, ascending and unique; slice: entries per workgroup, a multiple of 64;
+    plan = (slice prefix int64 [n + 1] on the device, its last value as an int), made once per CSR (als.split_heavy) - None derives
+    it here (a host sync).  CSR, conf and err_flag as for als_solve_rows; H[h] and b[h] do not depend on the other listed rows, and two
+    calls give the same bits.  -> (H, b)"""
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
+        raise ValueError("als_normal_rows: Y must be a 2-D tensor")
+    n_y, dim = Y.shape
+    if not 1 <= dim <= ALS_CG_MAX_DIM:
+        raise ValueError(f"als_normal_rows: dim = {dim}: 1 <= dim <= {ALS_CG_MAX_DIM}")
+    if int(slice) < 64 or int(slice) % 64:
+        raise ValueError(f"als_normal_rows: slice = {slice} must be a multiple of 64, at least 64")
+    _rows_f32(Y, "Y")
+    n_rows = off.shape[0] - 1
+    off, idx_ = _csr((off, idx), n_rows, "csr")
+    if conf is not None:
+        if conf.dtype != torch.float32 or not conf.is_cuda or not conf.is_contiguous() or conf.shape != idx.shape:
+            raise TypeError("als_normal_rows: conf must be a contiguous float32 device tensor, one value per idx entry")
+        if conf.numel() == 0:
+            conf = None
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() != 1:
+        raise TypeError("als_normal_rows: rows must be a contiguous int32 device vector")
+    n = rows.shape[0]
+    if plan is None:
+        pre = als_slice_prefix(off, rows, slice)
+        plan = (pre, int(pre[-1].item()))
+    pre, n_slices = plan
+    if pre.dtype != torch.int64 or not pre.is_cuda or not pre.is_contiguous() or tuple(pre.shape) != (n + 1,):
+        raise TypeError(f"als_normal_rows: the slice prefix must be a contiguous int64 device vector of {n + 1}")
+    H = torch.empty(n, dim, dim, dtype=torch.float32, device=Y.device)
+    b = torch.empty(n, dim, dtype=torch.float64, device=Y.device)
+    lib = _lib.load()
+    ws_bytes = int(lib.brAlsNormalRowsWorkspaceBytes(int(n_slices), dim))
+    if ws_bytes < 0:
+        raise ValueError(f"als_normal_rows: bad sizes slices={n_slices} dim={dim}")
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Y.device)
+    check(lib.brAlsNormalRows(Y.data_ptr(), _ld(Y), n_y, dim, off.data_ptr(), idx_.data_ptr(), _p(conf), float(alpha), n_rows, rows.data_ptr(),
+                              pre.data_ptr(), n, int(n_slices), int(slice), H.data_ptr(), b.data_ptr(), ws.data_ptr(), ws_bytes, _p(err_flag),
+                              _stream()), "brAlsNormalRows")
+    return H, b
+
+
+def als_solve_rows_dense_cg(G, H, b, reg, x0, steps=3, out=None):
+    """`steps` (1 .. 64) conjugate-gradient steps of als_solve_rows_cg on the formed operators A_h = G + reg I + H[h] with right-hand
+    sides b[h] (als_normal_rows), from x0 (n, dim) float32 contiguous (brAlsSolveRowsDenseCg): the sums in double, x rounded once.
+    out: (n, >= dim) float32, any row stride >= dim (columns past dim are left alone).  -> out"""
+    if not isinstance(G, torch.Tensor) or G.dim() != 2 or G.shape[0] != G.shape[1]:
+        raise ValueError("als_solve_rows_dense_cg: G must be (dim, dim)")
+    dim = G.shape[0]
+    if not 1 <= dim <= ALS_CG_MAX_DIM:
+        raise ValueError(f"als_solve_rows_dense_cg: dim = {dim}: 1 <= dim <= {ALS_CG_MAX_DIM}")
+    if not 1 <= int(steps) <= 64:
+        raise ValueError(f"als_solve_rows_dense_cg: steps = {steps}: 1 <= steps <= 64")
+    _f32(G, "G")
+    if not isinstance(H, torch.Tensor) or H.dim() != 3 or tuple(H.shape[1:]) != (dim, dim):
+        raise ValueError(f"als_solve_rows_dense_cg: H must be (n, {dim}, {dim})")
+    _f32(H, "H")
+    n = H.shape[0]
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64 or not b.is_cuda or not b.is_contiguous() or tuple(b.shape) != (n, dim):
+        raise TypeError(f"als_solve_rows_dense_cg: b must be a contiguous float64 device tensor ({n}, {dim})")
+    if not isinstance(x0, torch.Tensor) or tuple(x0.shape) != (n, dim):
+        raise ValueError(f"als_solve_rows_dense_cg: x0 must be ({n}, {dim})")
+    _f32(x0, "x0")
+    if out is None:
+        out = torch.empty(n, dim, dtype=torch.float32, device=G.device)
+    elif out.dim() != 2 or out.shape[0] != n or out.shape[1] < dim:
+        raise ValueError(f"als_solve_rows_dense_cg: out must be ({n}, >= {dim})")
+    _rows_f32(out, "out")
+    check(_lib.load().brAlsSolveRowsDenseCg(G.data_ptr(), H.data_ptr(), b.data_ptr(), dim, float(reg), x0.data_ptr(), n, int(steps),
+                                            out.data_ptr(), _ld(out), _stream()), "brAlsSolveRowsDenseCg")
+    return out

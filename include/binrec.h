@@ -1165,6 +1165,39 @@ int brAlsSolveRowsCg(const float* Y, int64_t ld_y, int64_t n_y, int dim, const f
                      const float* conf, float alpha, float reg, int64_t n_rows, float* X, int64_t ld_x, int steps, int* err_flag,
                      brStream stream);
 
+/* ALS by conjugate gradients, the heavy rows (csrc/als_heavy.hip).  Single device.  A row with very many entries leaves
+ * brAlsSolveRowsCg (one wave walks all of them, once per application of A): its operator is formed once, by many workgroups, and the
+ * same recurrence runs on the dense matrix.
+ * brAlsNormalRows: for every listed row rows[h] (int32, ascending, unique, h < n_heavy) of the CSR (off, idx, conf or NULL = 1, as for
+ *   brAlsSolveRows; n_rows = rows of the CSR) with c_e = alpha * conf[e]:
+ *       H[h] = sum_e c_e y_e y_e^T   (float32 [n_heavy][dim][dim], both triangles, bit-equal to its transpose)
+ *       b[h] = sum_e (1 + c_e) y_e    (double  [n_heavy][dim])
+ *   A row's entries are cut into slices of `slice` entries (a multiple of 64, at least 64); slice_off (int64 [n_heavy + 1], device,
+ *   slice_off[0] = 0, slice_off[h + 1] - slice_off[h] = ceil(len(rows[h]) / slice), slice_off[n_heavy] = n_slices) is planned by the
+ *   caller once per CSR.  First launch: grid = (n_slices, pairs (I, J <= I) of 128-column blocks); a workgroup gathers 64 entries' rows
+ *   of Y through idx, scales one operand by c_e and multiplies on the fp32-input MFMA, each 64-entry chunk's sums from zero, joined to
+ *   the slice's once; partials go to ws (brAlsNormalRowsWorkspaceBytes(n_slices, dim); -1 outside the limits).  Second launch: a row's
+ *   slice partials are added in slice order in double and rounded once, H[i][j] and H[j][i] written from the one value; b is summed in
+ *   double, in the order of the CSR within a slice and in slice order across slices.  H[h] and b[h] are a function of (the row's
+ *   entries in their order, the rows of Y they name, conf, alpha, dim, slice) alone - not of the other listed rows or the grid; two
+ *   calls, and the 16-byte and the scalar load paths, give the same bits; no atomics on floats.  An idx outside [0, n_y), or a listed
+ *   row outside [0, n_rows), is compared, never used as an address: it sets BR_ERRFLAG_RANGE in *err_flag (may be NULL) and counts as
+ *   absent.  A slice_off that promises a row more slices than it has gives zeros for them; fewer, and the row's tail is left out.
+ * brAlsSolveRowsDenseCg: the recurrence of brAlsSolveRowsCg, word for word, on A_h = G + reg I + H[h] and b[h], one workgroup per
+ *   listed row: x = X0[h] (float32, compact rows of dim), `steps` steps with the same stop rules, Xout[h] (row stride ld_out) = x
+ *   rounded to float once.  q = G p + H[h] p + reg p is summed in double in feature order k = 0 .. dim - 1 (thread j owns feature j
+ *   and reads column j through the symmetric transpose); x, r, p and the dot products are doubles.  It takes no ids.  Xout[h] is a
+ *   function of (G, H[h], b[h], reg, X0[h], steps) alone; two calls give the same bits.
+ * Limits: 1 <= dim <= 512, ld >= dim, 1 <= n_y < 2^31 where rows are listed, n_rows, n_heavy, n_slices < 2^31, alpha >= 0 and finite,
+ * reg > 0 and finite, 1 <= steps <= 64; BR_ERR_ARG / BR_ERR_WORKSPACE before any launch; n_heavy == 0 is BR_OK; no allocation and no
+ * sync inside. */
+int64_t brAlsNormalRowsWorkspaceBytes(int64_t n_slices, int dim);
+int brAlsNormalRows(const float* Y, int64_t ld_y, int64_t n_y, int dim, const int64_t* off, const int32_t* idx, const float* conf,
+                    float alpha, int64_t n_rows, const int32_t* rows, const int64_t* slice_off, int64_t n_heavy, int64_t n_slices,
+                    int slice, float* H, double* b, void* ws, int64_t ws_bytes, int* err_flag, brStream stream);
+int brAlsSolveRowsDenseCg(const float* G, const float* H, const double* b, int dim, float reg, const float* X0, int64_t n_heavy, int steps,
+                          float* Xout, int64_t ld_out, brStream stream);
+
 /* Optional launch probe for measurement (bench.py roofline leg): HIP events on the launch stream
  * around every inner launch of brNeumfStepRun, tagged BR_TAG_*.  brProbeEnable(capacity) creates
  * the events (capacity 0 disables and frees them); after synchronising the stream the host reads
